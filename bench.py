@@ -5,6 +5,11 @@ graphs -- the metric of BASELINE.json -- on N MI355X GPUs of one node.
       N > 1 without a torchrun environment: this process starts N fresh ranks itself (torch.distributed.run,
       one per GPU, RCCL over xGMI) BEFORE it touches any GPU, relays rank 0's JSON line and exits with their code.
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W   (the driver's form)
+  --dump-outputs DIR   after the timed steps, what the last timed step computed -> DIR/*.npy (float32): out3.npy = the
+                       vector ``run_steps`` returns [loss, sum of class weights, #correct], param.<name>.npy = the model's
+                       parameters after that step.  Inputs are seeded: the same arguments give the same inputs in every run.
+  --full               everything the record measures besides the headline (the objects listed below); a plain run sets up,
+                       warms up, times the K steps and prints the record.
 
 Workload (BASELINE.json configs[1] / SURVEY 8(d) cfg2): batches of 100 page graphs, 3-layer GraphSAGE-GCN, F0 = 831
 (BBOX+REPR+SCIBERT), hidden 256, 9 classes, fp32, Adam(lr 0.01, wd 5e-4), unweighted cross-entropy.
@@ -16,12 +21,13 @@ while the previous step runs, then forward + loss + backward + (all-reduce) + Ad
 are resident in HBM before the timed region.  Every rank owns DISTINCT pages (weak scaling); the only collective is one
 RCCL all-reduce of the flat gradient per step.  One JSON line is printed by rank 0.
 
-Extra objects in the JSON line:
+Extra objects in the JSON line (with --full; `step_roofline` is in every record):
   roofline      dominant kernel (the forward transform GEMMs: planes GEMM on the bf16 matrix pipe by default), live HIP-event
                 timing of the same steps
   long_run      the same loop for >= 1 s of device time (after a few warm-up steps of its own), run BEFORE the W warm-up + K timed steps (the driver's 20-step
                 region is ~15 ms; measured right after an idle GPU woke up it reads ~7 % low: the chip has not reached its
-                sustained clocks -- a training run is at them)
+                sustained clocks -- a training run is at them).  A plain run runs it too, untimed and not stretched to K
+                steps, so that its headline is taken at the same clocks
   replay        secondary: HIP-graph replay of pre-captured resident batches (round 1's headline mode)
   gather        the aggregation kernel on BASELINE cfg4 (1 M nodes, deg 12, F = 512): HBM GB/s
   cfg3          BASELINE configs[2]: 4-head GAT, bf16 MFMA projection + bf16 gathers (no reference counterpart: parity unpinned)
@@ -68,7 +74,12 @@ def parse():
     ap.add_argument("--pages", type=int, default=100, help="page graphs per batch per GPU")
     ap.add_argument("--resident-pages", type=int, default=1200,
                     help="pages of the resident dataset per GPU; an epoch is resident-pages / pages steps")
-    ap.add_argument("--long-run-seconds", type=float, default=1.0, help="device time of the secondary long run (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (long run figure, roofline and per-kernel timers, probes, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--long-run-seconds", type=float, default=1.0,
+                    help="device time of the long run before the warm-up (0: skip); reported with --full only")
     ap.add_argument("--no-replay", action="store_true", help="skip the HIP-graph replay secondary")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather-probe", action="store_true")
@@ -362,6 +373,30 @@ def inference_probe(args, gte, model, dev, pages, trainer=None):
                                          "predictions_equal_module_path": float((got == ref).float().mean())}
     model.train(was_training)
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """arrays (name -> tensor / array) -> out_dir/<name>.npy as float32 (float64 stays float64).  When they hold more than
+    max_bytes in all, each array above its even share is replaced by a sample of its flattened elements at indices drawn by a
+    fixed seed (the same indices for the same shape in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    if sum(a.nbytes for a in host.values()) > max_bytes:
+        share = max_bytes // len(host)
+        for name, a in host.items():
+            k = share // a.itemsize
+            if a.size > k:
+                idx = np.sort(np.random.default_rng(1234).choice(a.size, size=k, replace=False))
+                host[name] = a.reshape(-1)[idx]
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(host)
 
 
 def timed_loop(trainer, pipe, epochs, loop):
@@ -1021,12 +1056,13 @@ def compact_record(full):
                                                    if cfg.get("input_aggregate_cached") else "")),
                      "pages_per_gpu_per_step": cfg["pages_per_gpu_per_step"], "nodes_per_step_per_gpu": cfg["nodes_per_step_per_gpu"],
                      "resident_pages_per_gpu": cfg["resident_pages_per_gpu"], "parallelism": cfg["parallelism"]}
-    ro = full["roofline"]
-    rec["roofline"] = {"bound": ro["bound"], "achieved": ro["achieved"], "peak": ro["peak"], "unit": ro["unit"], "frac": ro["frac"],
-                       "traffic": ro["traffic"], "kernel": ro["kernel_short"], "avg_launch_ms": ro["avg_launch_ms"],
-                       "launches": ro["launches"], "algorithmic_flops_per_launch": ro["algorithmic_flops_per_launch"]}
-    if ro.get("layer1"):
-        rec["roofline"]["layer1"] = ro["layer1"]
+    if "roofline" in full:
+        ro = full["roofline"]
+        rec["roofline"] = {"bound": ro["bound"], "achieved": ro["achieved"], "peak": ro["peak"], "unit": ro["unit"], "frac": ro["frac"],
+                           "traffic": ro["traffic"], "kernel": ro["kernel_short"], "avg_launch_ms": ro["avg_launch_ms"],
+                           "launches": ro["launches"], "algorithmic_flops_per_launch": ro["algorithmic_flops_per_launch"]}
+        if ro.get("layer1"):
+            rec["roofline"]["layer1"] = ro["layer1"]
     sr = full["step_roofline"]
     rec["step_roofline"] = {k: sr[k] for k in ("bound", "frac", "flops_per_node", "bytes_per_node", "mfma_bound_nodes_per_s",
                                                 "hbm_bound_nodes_per_s", "traffic_bytes_per_node", "traffic_GBs") if k in sr}
@@ -1126,7 +1162,7 @@ def main():
     local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
     workers = max(1, usable_cores() // max(local_world, 1))
     pages = make_pages_parallel(args.resident_pages, args.in_feats, rank * args.resident_pages, workers)
-    extras = rank == 0 and world == 1 and not distributed
+    extras = args.full and rank == 0 and world == 1 and not distributed
     pages13 = None
     if extras and not args.no_secondary and args.in_feats != 13:
         pages13 = make_pages_parallel(min(args.resident_pages, 600), 13, 0, workers)
@@ -1139,7 +1175,7 @@ def main():
     if extras and not args.no_shapes and args.in_feats == 831:
         pages363 = make_pages_parallel(300, 363, 0, workers)
     val_pages = None
-    if rank == 0 and world == 1 and args.val_graph > 0:
+    if args.full and rank == 0 and world == 1 and args.val_graph > 0:
         val_pages = make_pages_parallel(args.val_graph, args.in_feats, 10_000_000, workers)
     gen_s = time.perf_counter() - t_gen
 
@@ -1242,7 +1278,7 @@ def main():
     # the GPU reaches its sustained clocks under them -- a training run is at those clocks; a 20-step region measured
     # seconds after an idle GPU woke up is not (measured: the same 20 steps take 7 % longer right after start-up).
     pre = {}
-    if rank == 0 and world == 1 and not args.no_gather_probe:
+    if args.full and rank == 0 and world == 1 and not args.no_gather_probe:
         pre["gather"] = gather_probe(args, gte, S, dev)
     if val_pages is not None:
         pre["val_graph"] = val_graph_probe(args, gte, S, model, dev, val_pages, trainer)
@@ -1256,7 +1292,9 @@ def main():
         dims_ = [args.in_feats] + [args.hidden] * (args.layers - 1) + [9]
         flops_node_ = sum(2.0 * 2 * dims_[l] * dims_[l + 1] * (3 if l > 0 else 2) for l in range(args.layers))
         t_floor = float(np.mean(sizes)) * args.pages * flops_node_ / (MFMA_F32_PEAK_TF * 1e12)
-        n_long = max(args.steps, int(args.long_run_seconds / max(t_floor, 1e-6)) + 1)
+        n_long = int(args.long_run_seconds / max(t_floor, 1e-6)) + 1
+        if args.full:                                  # (a plain run's clock warm-up does not grow with K)
+            n_long = max(args.steps, n_long)
         if distributed:
             # every rank generates ITS pages, so the mean page size -- and with it this step count -- differs by rank; the
             # ranks must run the same number of steps (one all-reduce per step): take the largest
@@ -1301,6 +1339,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     final_loss = float(out3[0])
+    if args.dump_outputs and rank == 0:
+        # what a caller of the loop receives from its last step: the returned vector and the parameters it left behind
+        write_outputs(args.dump_outputs, {"out3": out3, **{"param." + k: v for k, v in model.state_dict().items()}})
     if step_events is not None:
         evs = step_events[-(args.steps + 1):]
         print("per-step us / nodes:", " ".join(f"{evs[i][0].elapsed_time(evs[i + 1][0]) * 1e3:.0f}/{evs[i + 1][1]}"
@@ -1309,7 +1350,7 @@ def main():
 
     # ---- per-kernel HIP-event timing: the SAME loop with event pairs around the tagged launches, right after -------------
     kt = {}
-    if not args.no_kernel_timers:
+    if args.full and not args.no_kernel_timers:
         run(prof[:1], prof_cnt[:1])              # untimed: settle
         ops.enable_kernel_timers(True)
         run(prof, prof_cnt)
@@ -1328,7 +1369,7 @@ def main():
     # the forward transform GEMMs of the loop the timed region ran (one-call step: events on its launch stream around them)
     kinds_hl = trainer._plan_kinds(args.in_feats, int(np.mean(sizes)) * args.pages, resident.agg_p3 is not None) if args.layers == 3 else None
     fwd_ev = None
-    if kinds_hl is not None and trainer._planes_on():
+    if args.full and kinds_hl is not None and trainer._planes_on():
         more, ep = epoch_steps(sizes, args.pages, seed, ep, 8)
         ms2, fl2, n2 = loop_forward_gemms(trainer, pipe, more, loop, args.in_feats, args.hidden, kinds_hl,
                                           n_global=global_counts(more) if distributed else None)
@@ -1396,10 +1437,12 @@ def main():
                        "resident_pages_per_gpu": args.resident_pages, "nodes_per_step_per_gpu": mean_nodes,
                        "parallelism": f"dp{world}",
                        "input_aggregate_cached": bool(kinds_hl is not None and kinds_hl[0] == 3)},
-            "final_loss": final_loss, "roofline": roofline, "kernels": per_kernel, "host_page_generation_s": gen_s,
+            "final_loss": final_loss, "host_page_generation_s": gen_s,
         }
-        if long_run is not None:
-            line["long_run"] = long_run
+        if args.full:
+            line.update(roofline=roofline, kernels=per_kernel)
+            if long_run is not None:
+                line["long_run"] = long_run
         # whole-step bounds of SURVEY 8(d): per node, layer l (F_l -> F_{l+1}, mean in-degree d), training mode, no recomputation
         dims = [args.in_feats] + [args.hidden] * (args.layers - 1) + [9]
         deg = float(sum(len(p.src) for p in pages)) / max(float(sum(p.num_nodes for p in pages)), 1.0)
@@ -1435,7 +1478,8 @@ def main():
             line["gemm_modes"] = gemm_mode_probe(ops, run, alt, global_counts(alt), dev)
         line.update(pre)
         line["order"] = ("gather / val_graph probes, long_run (its own warm-up steps, then >= 1 s of the same loop), THEN W warm-up + K timed steps = value, "
-                         "then kernel timers, replay, the other GEMM mode, inference, secondary, size_sweep, shapes, residency, cfg3, cpu_baseline")
+                         "then kernel timers, replay, the other GEMM mode, inference, secondary, size_sweep, shapes, residency, cfg3, cpu_baseline"
+                         if args.full else "long run of the same loop (untimed), THEN W warm-up + K timed steps = value")
         if extras and not args.no_inference:
             line["inference"] = inference_probe(args, gte, model, dev, pages, trainer)
         if pages13 is not None:
@@ -1458,7 +1502,7 @@ def main():
             dp = dist_one_rank_probe(args, gte, dev, resident, pipe, sizes, loop, ep)
             if dp is not None:
                 line["dist_1rank"] = dp
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ids = timed[0][0]
             cb = cpu_baseline(args, S.concat_pages([pages[int(i)] for i in ids]), state0)
             line["cpu_baseline"] = cb

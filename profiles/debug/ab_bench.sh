@@ -3,16 +3,16 @@
 export GTE_LIB_PATH=${GTE_LIB_PATH:-$(cd $(dirname $0)/../.. && pwd)/gnn-tableextraction_amd/libgte_hip_measure.so}
 # A/B of environment variants on the bench's train loop (headline + run shapes), interleaved on one box:
 #   bash profiles/debug/ab_bench.sh "GTE_CACHE_AGG=1" "GTE_CACHE_AGG=0"
-# prints value / ms_per_step / shapes per variant and round (bench_extras.json of each run is kept under gpurun_out/ab/)
-mkdir -p gpurun_out/ab
+# prints value / ms_per_step / shapes per variant and round (bench_extras.json of each run is kept under $AB_OUT)
+O=${AB_OUT:?set AB_OUT to the output directory}; mkdir -p $O
 FLAGS="--no-gather-probe --no-cfg3 --no-residency --no-uncached --no-size-sweep --no-inference --no-replay --val-graph 0 --no-cpu-baseline --no-split-probe --no-secondary --no-dist-probe ${AB_FLAGS}"
 for round in 1 2; do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    env $v python bench.py $FLAGS > gpurun_out/ab/out_${i}_${round}.log 2> gpurun_out/ab/err_${i}_${round}.log
-    cp bench_extras.json gpurun_out/ab/extras_${i}_${round}.json 2>/dev/null
-    python - "$v" $round gpurun_out/ab/out_${i}_${round}.log <<'PY'
+    env $v python bench.py --full $FLAGS > $O/out_${i}_${round}.log 2> $O/err_${i}_${round}.log
+    cp bench_extras.json $O/extras_${i}_${round}.json 2>/dev/null
+    python - "$v" $round $O/out_${i}_${round}.log <<'PY'
 import json, sys
 tag, rnd, path = sys.argv[1:4]
 lines = [l for l in open(path) if l.startswith("{")]

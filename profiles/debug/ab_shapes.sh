@@ -7,7 +7,7 @@ F="--no-cpu-baseline --no-gather-probe --no-cfg3 --no-replay --no-split-probe --
 ROUNDS=${ROUNDS:-2}
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
-    env $v timeout 300 python bench.py $F 2>/dev/null | python -c "
+    env $v timeout 300 python bench.py --full $F 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 out = ['headline %.2f' % (d['value'] / 1e6)]

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/gaps; mkdir -p $O
 STEP_ONLY="--no-cpu-baseline --no-gather-probe --no-secondary --no-cfg3 --no-replay --no-split-probe --no-inference --val-graph 0"
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace -d $O/t -o t -- python3 $R/bench.py --long-run-seconds 0.2 $STEP_ONLY > $O/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace -d $O/t -o t -- python3 $R/bench.py --full --long-run-seconds 0.2 $STEP_ONLY > $O/log.txt 2>&1
 DB=$(ls $O/t/*.db | head -1)
 python3 $R/profiles/debug/step_gaps.py $DB | tail -12
 python3 - $DB <<'PY'

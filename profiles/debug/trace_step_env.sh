@@ -8,7 +8,7 @@ STEP_ONLY="--no-cpu-baseline --no-gather-probe --no-secondary --no-cfg3 --no-rep
 cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   tag=$(echo $v | tr '= ' '__')
-  ( export $v; timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_$tag -o t -- python3 $R/bench.py --long-run-seconds 0.2 $STEP_ONLY > $O/trace_$tag.log 2>&1 )
+  ( export $v; timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_$tag -o t -- python3 $R/bench.py --full --long-run-seconds 0.2 $STEP_ONLY > $O/trace_$tag.log 2>&1 )
   python3 $R/profiles/rocpd_summary.py $(ls $O/trace_$tag/*.db | head -1) $O/step_kernel_stats_$tag.csv > /dev/null
   rm -rf $O/trace_$tag
 done

@@ -12,12 +12,12 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 STEP_ONLY="--no-cpu-baseline --no-gather-probe --no-secondary --no-cfg3 --no-replay --no-split-probe --no-inference --no-shapes --no-size-sweep --no-residency --no-uncached --no-dist-probe --val-graph 0"
-timeout 400 python3 $R/bench.py > $O/bench.json 2> $O/bench.err        # the record line (what the driver parses) ...
+timeout 400 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err        # the record line (what the driver parses) ...
 cp $R/bench_extras.json $O/bench_extras.json 2> /dev/null                # ... and the full measurements behind it
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python3 $R/bench.py --long-run-seconds 0.2 --no-cpu-baseline > $O/bench_trace.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_step -o t -- python3 $R/bench.py --long-run-seconds 0.2 $STEP_ONLY > $O/bench_trace_step.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_f32 -o t -- python3 $R/bench.py --gemm-mode f32 --long-run-seconds 0.2 $STEP_ONLY > $O/bench_trace_f32.log 2>&1
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_13 -o t -- python3 $R/bench.py --in-feats 13 --long-run-seconds 0.2 $STEP_ONLY > $O/bench_trace_13.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python3 $R/bench.py --full --long-run-seconds 0.2 --no-cpu-baseline > $O/bench_trace.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_step -o t -- python3 $R/bench.py --full --long-run-seconds 0.2 $STEP_ONLY > $O/bench_trace_step.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_f32 -o t -- python3 $R/bench.py --full --gemm-mode f32 --long-run-seconds 0.2 $STEP_ONLY > $O/bench_trace_f32.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_13 -o t -- python3 $R/bench.py --full --in-feats 13 --long-run-seconds 0.2 $STEP_ONLY > $O/bench_trace_13.log 2>&1
 cd $R
 python3 profiles/rocpd_summary.py $(ls $O/trace_f32/*.db | head -1) $O/f32_step_kernel_stats.csv > /dev/null
 python3 profiles/rocpd_summary.py $(ls $O/trace_13/*.db | head -1) $O/f13_step_kernel_stats.csv > /dev/null

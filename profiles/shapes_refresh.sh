@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 STEP_ONLY="--no-cpu-baseline --no-gather-probe --no-secondary --no-cfg3 --no-replay --no-split-probe --no-inference --no-shapes --no-size-sweep --no-residency --no-uncached --no-dist-probe --val-graph 0 --long-run-seconds 0.1 --resident-pages 400"
 for sh in $SHAPES; do
   F=${sh%%:*}; H=${sh##*:}
-  timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_${F}_${H} -o t -- python3 $R/bench.py --in-feats $F --hidden $H $STEP_ONLY > $O/shape_f${F}_h${H}.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace_${F}_${H} -o t -- python3 $R/bench.py --full --in-feats $F --hidden $H $STEP_ONLY > $O/shape_f${F}_h${H}.log 2>&1
   python3 $R/profiles/rocpd_summary.py $(ls $O/trace_${F}_${H}/*.db | head -1) $O/shape_f${F}_h${H}_kernel_stats.csv > /dev/null
   rm -rf $O/trace_${F}_${H}
 done

@@ -254,6 +254,23 @@ def test_bench_epoch_steps_follow_the_train_loop_plan():
     assert len(set(flat)) == len(flat) == 500                # an epoch never revisits a page
 
 
+def test_bench_output_dump_is_float_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float32 files (float64 kept), and above the size limit a seeded sample -- the same elements in
+    every run -- of each array larger than its share."""
+    b = _bench()
+    big = np.arange(5000, dtype=np.float64).reshape(50, 100)
+    arrays = {"a": torch.arange(6, dtype=torch.int64), "b": big, "c": np.ones(10, np.float16)}
+    assert b.write_outputs(str(tmp_path / "x"), arrays) == ["a", "b", "c"]
+    got = {k: np.load(tmp_path / "x" / f"{k}.npy") for k in "abc"}
+    assert got["a"].dtype == np.float32 and got["c"].dtype == np.float32 and got["b"].dtype == np.float64
+    np.testing.assert_array_equal(got["b"], big)
+    b.write_outputs(str(tmp_path / "y"), arrays, max_bytes=3000)
+    b.write_outputs(str(tmp_path / "z"), arrays, max_bytes=3000)
+    y, z = (np.load(tmp_path / d / "b.npy") for d in "yz")
+    assert y.nbytes <= 1000 and np.array_equal(y, z) and np.isin(y, big).all() and (np.diff(y) > 0).all()
+    np.testing.assert_array_equal(np.load(tmp_path / "y" / "a.npy"), np.arange(6, dtype=np.float32))
+
+
 def test_the_shipped_library_reads_one_environment_variable():
     """no globals besides a read-only device-props cache.  The measurement switches of earlier rounds (17 getenv reads)
     are compiled into libgte_hip_measure.so only; the shipped library holds the name of ONE variable, GTE_GEMM_MODE (include/gte.h),

@@ -113,7 +113,7 @@ def test_bench_self_spawned_two_ranks_share_the_gpu():
     env = dict(os.environ, GTE_BENCH_SHARE_GPU="1", MASTER_PORT=str(_free_port()))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
                         "--long-run-seconds", "0.05", "--resident-pages", "300", "--no-cpu-baseline"],
                        env=env, cwd=root, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{\"metric\"")]
