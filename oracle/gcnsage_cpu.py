@@ -196,24 +196,30 @@ class OracleGraph:
 def layer_forward(graph: OracleGraph, h: torch.Tensor, weight: torch.Tensor,
                   bias: Optional[torch.Tensor], ln_weight: Optional[torch.Tensor],
                   ln_bias: Optional[torch.Tensor], activation: bool,
-                  use_pp: bool = False, eps: float = 1e-5) -> torch.Tensor:
-    """One GcnSAGELayer.forward (models.py:46-72), dropout p=0."""
+                  use_pp: bool = False, eps: float = 1e-5, mask: Optional[torch.Tensor] = None,
+                  layer_norm=None) -> torch.Tensor:
+    """One GcnSAGELayer.forward (models.py:46-72), dropout p=0.
+
+    ``mask`` (optional, [n, fout], nonzero = keep): the ReLU decision given from outside -- the activation is then
+    ``y * mask`` instead of ``relu(y)``, with the same value wherever the mask is y's own sign and the derivative
+    ``mask``.  ``layer_norm`` (optional): replaces ``torch.nn.functional.layer_norm`` (same signature; test hooks)."""
     if not use_pp:
         norm = torch.from_numpy(graph.norm).to(h.dtype)              # :74-78
         ah = _SpMM.apply(h, graph)                                    # :53-57
         h = torch.cat((h, ah * norm), dim=1)                          # :69-72
     z = torch.nn.functional.linear(h, weight, bias)                   # :63
     if ln_weight is not None:
-        z = torch.nn.functional.layer_norm(z, (z.shape[1],), ln_weight, ln_bias, eps)   # :64
+        z = (layer_norm or torch.nn.functional.layer_norm)(z, (z.shape[1],), ln_weight, ln_bias, eps)   # :64
     if activation:
-        z = torch.relu(z)                                             # :65-66
+        z = torch.relu(z) if mask is None else z * torch.as_tensor(mask).to(z.dtype)   # :65-66
     return z
 
 
 def gcnsage_forward(state: Dict[str, torch.Tensor], graph: OracleGraph, x: torch.Tensor,
-                    return_hidden: bool = False):
+                    return_hidden: bool = False, masks: Optional[Sequence] = None, layer_norm=None):
     """GcnSAGE.forward (models.py:105-116) from a reference-format state_dict
-    (keys ``layers.{i}.linear.{weight,bias}``, ``layers.{i}.lynorm.{weight,bias}``)."""
+    (keys ``layers.{i}.linear.{weight,bias}``, ``layers.{i}.lynorm.{weight,bias}``).  ``masks``: one ReLU mask (or None)
+    per hidden layer, see ``layer_forward``; ``layer_norm(i, ...)``: layer i's LayerNorm (test hooks)."""
     n_layers = 1 + max(int(k.split(".")[1]) for k in state)
     h = x
     hidden = []
@@ -223,7 +229,8 @@ def gcnsage_forward(state: Dict[str, torch.Tensor], graph: OracleGraph, x: torch
             graph, h,
             state[f"layers.{i}.linear.weight"], state.get(f"layers.{i}.linear.bias"),
             state.get(f"layers.{i}.lynorm.weight"), state.get(f"layers.{i}.lynorm.bias"),
-            activation=not last)
+            activation=not last, mask=None if (masks is None or last) else masks[i],
+            layer_norm=None if layer_norm is None else (lambda *a, _i=i, **k: layer_norm(_i, *a, **k)))
         hidden.append(h)
     return (h, hidden) if return_hidden else h
 
@@ -269,16 +276,20 @@ def meansage_forward(weights: Sequence[Tuple[torch.Tensor, torch.Tensor]], graph
 
 class OracleTrainer:
     """CE(weight) -> backward -> torch.optim.Adam(lr, weight_decay) on leaf copies
-    of a state_dict.  Adam here is torch's own (L2-coupled decay) = the reference's."""
+    of a state_dict.  Adam here is torch's own (L2-coupled decay) = the reference's.  The arithmetic runs in the dtype of
+    the state (float64 state and features: a float64 oracle; the class weights follow the state's dtype)."""
 
     def __init__(self, state: Dict[str, torch.Tensor], lr: float = 0.01, weight_decay: float = 5e-4,
                  class_weights: Optional[torch.Tensor] = None):
         self.state = {k: v.clone().requires_grad_(True) for k, v in state.items()}
         self.opt = torch.optim.Adam(list(self.state.values()), lr=lr, weight_decay=weight_decay)
-        self.loss_fn = torch.nn.CrossEntropyLoss(weight=class_weights)
+        dtype = next(iter(state.values())).dtype
+        self.loss_fn = torch.nn.CrossEntropyLoss(weight=None if class_weights is None else torch.as_tensor(class_weights).to(dtype))
 
-    def step(self, graph: OracleGraph, x: torch.Tensor, labels: torch.Tensor):
-        logits = gcnsage_forward(self.state, graph, x)
+    def step(self, graph: OracleGraph, x: torch.Tensor, labels: torch.Tensor, masks: Optional[Sequence] = None,
+             layer_norm=None):
+        """``masks``: per-hidden-layer ReLU masks (gcnsage_forward); None: the oracle's own ReLU."""
+        logits = gcnsage_forward(self.state, graph, x, masks=masks, layer_norm=layer_norm)
         loss = self.loss_fn(logits, labels.long())                    # model_train.py:327
         self.opt.zero_grad()
         loss.backward()                                               # :331

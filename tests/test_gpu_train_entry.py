@@ -137,6 +137,16 @@ def test_fused_step_equals_autograd_path_on_random_shapes(seed):
     assert float(out_f[2]) == float(out_a[2])                      # same arg-max decisions
     gf, gr = fused.flat_grad.cpu().numpy(), auto.flat_grad.cpu().numpy()
     np.testing.assert_allclose(gf, gr, rtol=2e-3, atol=2e-5 * np.abs(gr).max() + 1e-9)
+    # third party for the fused engine: the float64 oracle on the ReLU masks its backward used, every gradient at 1e-4 of its max
+    from oracle import gcnsage_cpu as oc
+    from tests import stepcheck
+    state0 = {k: v.detach().cpu() for k, v in ma.state_dict().items()}       # (forward_backward leaves the parameters as they were)
+    masks = stepcheck.device_relu_masks(fused, ga, state0)
+    ref = stepcheck.reference_step(state0, oc.OracleGraph(src, dst, int(off[-1]), w), feat, label, masks,
+                                   None if cw is None else cw.cpu())
+    assert abs(float(out_f[0]) - ref["loss"]) < 1e-5 * max(1.0, abs(ref["loss"]))
+    stepcheck.assert_grads({k: fused._gslice[id(p)].cpu().numpy() for k, p in ma.named_parameters()}, ref["grads"],
+                           what=f"(f0, hid, layers, pages) = {(f0, hid, layers, pages)}: ")
 
 
 @pytest.mark.parametrize("hid,pages", [(512, 2), (1000, 5), (640, 1)])
