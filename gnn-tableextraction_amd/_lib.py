@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTE_LIB_PATH: profiling builds of the same ABI (e.g. ablation variants); default = the in-tree library
@@ -208,6 +208,14 @@ SIGNATURES = {
     "gte_adam_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gte_adam_step_dev_images": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_int, c_void_p, c_void_p]),
+    # dropout (csrc/dropout.hip)
+    "gte_dropout_mask": (c_int, [c_float, c_uint64, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "gte_dropout_mask_host": (c_int, [c_float, c_uint64, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64]),
+    "gte_spmm_dropout_p3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                    c_float, c_uint64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                    c_void_p]),
+    "gte_spmm_dropout_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_float, c_uint64, c_int, c_void_p,
+                                     c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p]),
 }
 
 class P3Desc(ctypes.Structure):
@@ -227,7 +235,8 @@ class StepLayer(ctypes.Structure):
                 ("ahn", c_void_p), ("t", c_void_p), ("stats", c_void_p), ("y", c_void_p), ("yp", c_void_p), ("ldp_y", c_int64),
                 ("dy", c_void_p), ("dzp", c_void_p), ("qp", c_void_p), ("ldp_o", c_int64),
                 ("ws_ln", c_void_p), ("ws_ln_bytes", c_int64), ("ws_dw", c_void_p), ("ws_dw_bytes", c_int64),
-                ("ldf", c_int64), ("ahnp", c_void_p), ("ldp_ahn", c_int64)]
+                ("ldf", c_int64), ("ahnp", c_void_p), ("ldp_ahn", c_int64),
+                ("xp", c_void_p), ("ldp_x", c_int64), ("g", c_void_p), ("ldg", c_int64)]
 
 
 class StepPlan(ctypes.Structure):
@@ -251,7 +260,8 @@ class StepPlan(ctypes.Structure):
                 ("wimg_out_fwd", c_void_p), ("ldp_wout_fwd", c_int64), ("wimg_out_bwd", c_void_p), ("ldp_wout_bwd", c_int64),
                 ("dlqp", c_void_p), ("ldp_dlq", c_int64), ("ws_out", c_void_p), ("ws_out_bytes", c_int64),
                 ("ws_ce", c_void_p), ("ws_ce_bytes", c_int64), ("ws_cs", c_void_p), ("ws_cs_bytes", c_int64),
-                ("fwd_events", c_void_p)]
+                ("fwd_events", c_void_p),
+                ("dropout_p", c_float), ("dropout_seed", c_uint64), ("rank", c_int)]
 
 
 class BatchArrays(ctypes.Structure):

@@ -69,11 +69,18 @@ int forward_hidden(const gte_step_plan& p, void* st, bool fwd_only = false) {
                                             L.fout, L.stats, L.y, L.fout, n, L.fout, st));
             continue;
         }
-        if (L.kind == GTE_LAYER_AGGFIRST) {
+        if (L.kind == GTE_LAYER_AGGFIRST || L.kind == GTE_LAYER_DROPOUT) {
             // z = [x | mean-aggregate(x)] W^T + b on the planes GEMM (two K segments), then LayerNorm + ReLU: the input layer of a
-            // model whose hidden width exceeds its input width (aggregating fin columns is the cheaper order, models.py:53-72)
-            GTE_TRY(gte_p3_from_f32(L.x, L.ldx, n, L.fin, 0, L.hp, L.ldp_h, st));
-            GTE_TRY(gte_spmm_csr_p3(p.indptr, p.indices, p.w_in, L.x, L.ldx, L.ahnp, L.ldp_ahn, n, L.fin, GTE_REDUCE_MEAN, st));
+            // model whose hidden width exceeds its input width (aggregating fin columns is the cheaper order, models.py:53-72).
+            // A dropout layer: both operand images with the layer's mask (and, layer 0, the input dropout) from ONE producer
+            if (L.kind == GTE_LAYER_DROPOUT) {
+                GTE_TRY(gte_spmm_dropout_p3(p.indptr, p.indices, p.w_in, L.x, L.ldx, L.xp, L.ldp_x, L.h_rows, L.n_res_rows, i == 0,
+                                            p.dropout_p, p.dropout_seed, p.rank, p.step_counter, i + 1, L.hp, L.ldp_h, L.ahnp,
+                                            L.ldp_ahn, n, L.fin, st));
+            } else {
+                GTE_TRY(gte_p3_from_f32(L.x, L.ldx, n, L.fin, 0, L.hp, L.ldp_h, st));
+                GTE_TRY(gte_spmm_csr_p3(p.indptr, p.indices, p.w_in, L.x, L.ldx, L.ahnp, L.ldp_ahn, n, L.fin, GTE_REDUCE_MEAN, st));
+            }
             mark(2 * i);
             if ((p.fuse_ln_dx & 16) && gte_gemm_p3_nt_ln_fwd_supported(L.fout)) {      // LayerNorm + ReLU as the GEMM's epilogue
                 GTE_TRY(gte_gemm_p3_nt_ln_fwd(L.hp, L.ldp_h, L.fin, L.ahnp, L.ldp_ahn, L.fin, L.wimg_fwd, L.ldp_wfwd, L.bias, L.gamma, L.beta,
@@ -244,6 +251,18 @@ int backward_a(const gte_step_plan& p, void* st) {
                                        L.gbeta, L.gbias, n, L.fout, L.ws_ln, L.ws_ln_bytes, st));
         ln_done = false;
         if (L.kind == GTE_LAYER_AGGFIRST || L.kind == GTE_LAYER_CACHED) break;       // (layer 0: dW = dz^T [x | ahn] is the step's last GEMM: phase 2)
+        if (L.kind == GTE_LAYER_DROPOUT) {
+            if (i == 0) break;                         // (dW = dz^T [D(x') | D(ahn')]: phase 2, as an aggregate-first layer 0)
+            // dW = dz^T [self | agg] on the forward's images; G = dz W (both halves); dy of the layer below = the mask's backward of
+            // G's self half + the transpose aggregation of its masked agg half (then the LayerNorm backward of that layer)
+            GTE_TRY(gte_gemm_p3_tn(L.dzp, L.ldp_o, nullptr, 0, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n,
+                                   L.ws_dw, L.ws_dw_bytes, st));
+            GTE_TRY(gte_gemm_p3_nt(L.dzp, L.ldp_o, L.fout, nullptr, 0, 0, L.wimg_bwd, L.ldp_wbwd, nullptr, 0, L.g, L.ldg, n, L.ldg, 0, 0, st));
+            const gte_step_layer& B = p.layer[i - 1];
+            GTE_TRY(gte_spmm_dropout_bwd(p.rindptr, p.rindices, p.w_out, L.g, L.ldg, L.ldg / 2, p.dropout_p, p.dropout_seed, p.rank,
+                                         p.step_counter, i + 1, B.dy, ldf(B), n, L.fin, st));
+            continue;
+        }
         GTE_TRY(gte_spmm_csr_p3(p.rindptr, p.rindices, p.w_out, L.dy, ld, L.qp, L.ldp_o, n, L.fout, GTE_REDUCE_SUM, st));
         if (i == 0) break;                             // layer 0's dW is the step's last GEMM: phase 2
         GTE_TRY(gte_gemm_p3_tn(L.dzp, L.ldp_o, L.qp, L.ldp_o, L.hp, L.ldp_h, nullptr, 0, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n, L.ws_dw,
@@ -288,7 +307,7 @@ int backward_b(const gte_step_plan& p, void* st) {
     if (L.kind == GTE_LAYER_CACHED)                    // dW = [dz^T x | dz^T ahn], both operands resident behind the row map
         return gte_gemm_p3_tn_rows2(L.dzp, L.ldp_o, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.h_rows, L.n_res_rows, L.fin, L.gW, 2 * L.fin,
                                     L.fout, 2 * L.fin, n, L.ws_dw, L.ws_dw_bytes, st);
-    if (L.kind == GTE_LAYER_AGGFIRST)                  // dW = [dz^T x | dz^T ahn]
+    if (L.kind == GTE_LAYER_AGGFIRST || L.kind == GTE_LAYER_DROPOUT)      // dW = [dz^T x | dz^T ahn] (dropout: the masked images)
         return gte_gemm_p3_tn(L.dzp, L.ldp_o, nullptr, 0, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n,
                               L.ws_dw, L.ws_dw_bytes, st);
     if (L.h_rows)
@@ -316,11 +335,25 @@ int check_plan(const gte_step_plan& p) {
     if (p.n_hidden < 1 || p.n_hidden > 7 || p.n_nodes < 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: bad plan");
     for (int i = 0; i < p.n_hidden; ++i) {
         const gte_step_layer& L = p.layer[i];
-        if (L.kind != GTE_LAYER_PLANES && L.kind != GTE_LAYER_SMALLK && L.kind != GTE_LAYER_AGGFIRST && L.kind != GTE_LAYER_CACHED)
+        if (L.kind != GTE_LAYER_PLANES && L.kind != GTE_LAYER_SMALLK && L.kind != GTE_LAYER_AGGFIRST && L.kind != GTE_LAYER_CACHED &&
+            L.kind != GTE_LAYER_DROPOUT)
             return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: layer kind");
+        if ((L.kind == GTE_LAYER_DROPOUT) != (p.dropout_p != 0.f))
+            return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: a plan with dropout_p != 0 runs every hidden layer as GTE_LAYER_DROPOUT, "
+                                                       "and only such a plan");
+        if (L.kind == GTE_LAYER_DROPOUT) {
+            if (!(p.dropout_p > 0.f && p.dropout_p < 1.f) || !p.step_counter || !L.hp || !L.ahnp || !L.wimg_fwd || !L.dzp)
+                return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: a dropout layer needs 0 < dropout_p < 1, the step counter, its "
+                                                           "operand / weight / dz images");
+            if (i == 0 ? (!L.x == !L.xp) : (!L.x || !L.g || !L.wimg_bwd || L.ldg != 2 * ((L.fin + 15) / 16 * 16)))
+                return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: dropout layer input (layer 0: x or xp) / G [n][2 ceil16(fin)] / "
+                                                           "backward weight image");
+            if (i > 0 && (!p.layer[i - 1].y || !p.layer[i - 1].dy))
+                return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: the layer below a dropout layer writes y as fp32 rows");
+        }
         if (L.kind == GTE_LAYER_CACHED && (!L.hp || !L.ahnp || (L.h_rows && L.n_res_rows <= 0)))
             return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: a cached-aggregate layer needs the images of the input and of its aggregate");
-        if (L.kind != GTE_LAYER_PLANES && i != 0)
+        if (L.kind != GTE_LAYER_PLANES && L.kind != GTE_LAYER_DROPOUT && i != 0)
             return gte::fail(GTE_ERR_UNSUPPORTED, "gcnsage_step: a short-input / aggregate-first layer must be layer 0");
         if (!L.gamma || !L.beta || !L.bias) return gte::fail(GTE_ERR_UNSUPPORTED, "gcnsage_step: hidden layers need bias and LayerNorm");
         if (L.ldf != 0 && (L.ldf < L.fout || L.ldf % 4 != 0)) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: ldf < fout or not a multiple of 4");
@@ -365,6 +398,9 @@ extern "C" int gte_gcnsage_forward(const gte_step_plan* plan, void* stream) {
     if (!plan) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_forward: null plan");
     const gte_step_plan& p = *plan;
     GTE_TRY(check_plan(p));
+    if (p.dropout_p != 0.f)          // (evaluation applies no dropout: models.py in eval mode -- bind a plan without it)
+        return gte::fail(GTE_ERR_UNSUPPORTED, "gcnsage_forward: the forward alone is the evaluation forward and applies no dropout; "
+                                             "the plan has dropout_p != 0");
     GTE_TRY(gte_gemm_set_tail_workspace(p.tail_ws, p.tail_ws ? p.tail_ws_bytes : 0));
     const int64_t n = p.n_nodes, C = p.n_classes;
     int rc = forward_hidden(p, stream, true);

@@ -121,19 +121,34 @@ class FusedGcnSageStep(TrainStep):
     * nothing in a step synchronises or allocates, so a step on a resident batch can be captured
       into a HIP graph (:meth:`capture`) and replayed with one launch -- the page-batch regime is a few
       dozen 10-300 us kernels, where per-launch host time would otherwise bound the step.
-    Requires the configuration every shipped reference run uses: ReLU (or no) activation, dropout 0,
-    use_pp False; anything else goes through the autograd path (:class:`TrainStep`).
+    Requires ReLU (or no) activations and use_pp False; anything else goes through the autograd path (:class:`TrainStep`).
+    Dropout 0 < p < 1 (``GcnSAGE(..., dropout=p)``, the reference's ``--dropout``) runs on the one-call plan with every hidden
+    layer as GTE_LAYER_DROPOUT: counter-based masks (csrc/dropout.h) of ``dropout_seed`` (default: torch.initial_seed()), the
+    data-parallel rank and the device step counter, regenerated by the kernels that need them -- captured replays draw fresh masks.
+    Evaluation (forward_logits) applies no dropout.
     """
 
-    def __init__(self, model: GcnSAGE, **kw):
+    def __init__(self, model: GcnSAGE, dropout_seed: Optional[int] = None, **kw):
         if not isinstance(model, GcnSAGE):
             raise TypeError("FusedGcnSageStep needs a GcnSAGE model")
         for layer in model.layers:
-            if layer.use_pp or (layer.dropout and layer.dropout.p > 0) or not (layer.activation is None or _is_relu(layer.activation)):
-                raise ValueError("FusedGcnSageStep supports ReLU/None activations, dropout 0, use_pp False")
-        if model.dropout.p > 0:
-            raise ValueError("FusedGcnSageStep supports dropout 0 only")
+            if layer.use_pp or not (layer.activation is None or _is_relu(layer.activation)):
+                raise ValueError("FusedGcnSageStep supports ReLU/None activations and use_pp False")
+        # dropout: the input dropout (models.py:105-113) and every hidden layer's mask over cat(h, ah * norm) share ONE p (GcnSAGE's
+        # constructor); the output layer has none
+        ps = {float(model.dropout.p)} | {float(l.dropout.p) if l.dropout else 0.0 for l in model.layers[:-1]}
+        if len(ps) != 1 or (model.layers[-1].dropout and model.layers[-1].dropout.p > 0):
+            raise ValueError("FusedGcnSageStep: the input and every hidden layer need the same dropout p, the output layer none")
+        p = ps.pop()
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"FusedGcnSageStep supports dropout 0 <= p < 1 (got {p}): p = 1 drops every input")
+        self.dropout_p = p
+        self.dropout_seed = int(torch.initial_seed() if dropout_seed is None else dropout_seed) & ((1 << 64) - 1)
         super().__init__(model, **kw)
+        self.rank = 0
+        if self.distributed:
+            import torch.distributed as dist
+            self.rank = int(dist.get_rank(self.group))
         self.lib = _lib.load()
         # slices of the flat gradient, in model.parameters() order
         self._gslice = {}
@@ -148,7 +163,7 @@ class FusedGcnSageStep(TrainStep):
         # about what hiding a 0.5 MB all-reduce can win back on 8 GPUs.  To be re-measured on a multi-GPU node.
         self._n0 = sum(p.numel() for p in model.layers[0].parameters() if p.requires_grad)
         first_upper = next((p for p in model.layers[1].parameters() if p.requires_grad), None) if len(model.layers) > 1 else None
-        self._dp_split = (os.environ.get("GTE_DP_OVERLAP", "0") == "1" and first_upper is not None
+        self._dp_split = (os.environ.get("GTE_DP_OVERLAP", "0") == "1" and first_upper is not None and self.dropout_p == 0
                           and self._gslice[id(first_upper)].storage_offset() == self._n0)
         self._bufs = {}
         self._graph_bufs = {}
@@ -210,6 +225,12 @@ class FusedGcnSageStep(TrainStep):
         # around the forward transform GEMM of every hidden layer of the NEXT steps (None: off)
         self.fwd_events = None
         self._fwd_ev_arr = None
+        if self.dropout_p > 0 and self._plan_kinds(model.layers[0].in_feats, 0) is None:
+            # dropout runs on the one-call plan only (the call-by-call schedule has no masks): a model the plan does not cover --
+            # hidden width > 1024, more than 8 layers or 16 classes, GTE_C_STEP=0, GTE_PLANES_GENERAL=0, op timers -- is refused
+            # here, where the caller can still take the autograd path (model_train.train does)
+            raise ValueError(f"FusedGcnSageStep: dropout {self.dropout_p} runs on the one-call plan, which does not cover this model / "
+                             "configuration; use TrainStep")
 
     # -- buffers -------------------------------------------------------------------------------------
     def _alloc(self, cap: int, f0: int):
@@ -301,7 +322,9 @@ class FusedGcnSageStep(TrainStep):
         b["dy"] = [z32(cap, ld[i]) for i in range(nh)]
         b["stats"] = [z32(2 * cap) for _ in range(nh)]
         b["ahn"] = [z32(cap, dims[0]) if kinds[i] == 1 else None for i in range(nh)]
-        b["ahnp"] = [img(cap, dims[0]) if kinds[i] == 2 else None for i in range(nh)]
+        b["ahnp"] = [img(cap, dims[i]) if kinds[i] in (2, 4) else None for i in range(nh)]
+        # a dropout layer above layer 0: G = dz W [n][2 ceil16(fin)] (self half, then the aggregate half from column ceil16(fin))
+        b["g"] = [z32(cap, 2 * _c16(dims[i])) if (kinds[i] == 4 and i > 0) else None for i in range(nh)]
         b["hp"] = [img(cap, dims[i]) if kinds[i] not in (1, 3) else None for i in range(nh)]      # (3: both operands are resident)
         b["dzp"] = [img(cap, dims[i + 1]) if kinds[i] != 1 else None for i in range(nh)]
         b["qp"] = [img(cap, dims[i + 1]) if kinds[i] == 0 else None for i in range(nh)]
@@ -513,6 +536,8 @@ class FusedGcnSageStep(TrainStep):
         """True when the train loop should keep the image of the input's mean aggregate next to the feature image
         (graph.ResidentPages.enable_p3(agg=True))."""
         L = self.model.layers[0]
+        if self.dropout_p > 0:
+            return False                  # (layer 0 aggregates the DROPPED input: a cached aggregate of x is of no use)
         return len(self.model.layers) >= 2 and self._cached_layer0(L, f0) and self._layer_kind(0, L, f0) in (0, 2)
 
     def wants_resident_images(self, f0: int) -> bool:
@@ -520,15 +545,23 @@ class FusedGcnSageStep(TrainStep):
         input as an image (wants_p3_features), or it is a widening aggregate-first layer that can run on the cached aggregate --
         63 / 313 / 363 -> 1000, 63 -> 206 of the reference's runs: without the cache such a layer copies its fp32 rows per batch and
         makes both images per step."""
+        if self.dropout_p > 0:            # a dropout layer 0 reads the resident feature image through the batch's row map
+            return self._layer_kind(0, self.model.layers[0], f0) == 4
         return self.wants_p3_features(f0) or self.wants_agg_image(f0)
 
-    def _layer_kind(self, i: int, L, fin: int, n: int = 0, cached: bool = False):
+    def _layer_kind(self, i: int, L, fin: int, n: int = 0, cached: bool = False, train: bool = True):
         """How hidden layer i runs on the one-call plan (gte_step_layer.kind): 0 planes layer in transform-first order, 1 the
         one-pass short-input layer (BBOX features), 2 aggregate-first planes input layer (fin < fout), 3 (``cached``: the batch
         brings the resident image of the input's mean aggregate) the input layer on [x | ahn] from two resident images; None: not on the plan.
         Every shape the reference's runs produce is covered (run_multiple_train.sh:8-113: hidden 1000, or
         int(calculate_hidden) = 96 ... 218, with F0 = 13 ... 831): hidden widths up to 1024, any input width."""
         fout = L.out_feats
+        if train and self.dropout_p > 0:
+            # 4 (GTE_LAYER_DROPOUT): every hidden layer of a training step with dropout, aggregate-first at any depth (the mask sits
+            # between the aggregation and W).  Its GEMMs are the planes GEMMs whatever the GEMM mode: the only dropout path
+            ok = (isinstance(L.lynorm, nn.LayerNorm) and L.linear.bias is not None and (L.activation is None or _is_relu(L.activation))
+                  and self.general_planes and fout <= 1024)
+            return 4 if ok else None
         if not (self._planes_on() and isinstance(L.lynorm, nn.LayerNorm) and L.linear.bias is not None
                 and (L.activation is None or _is_relu(L.activation))):
             return None
@@ -546,11 +579,13 @@ class FusedGcnSageStep(TrainStep):
         # map); aggregate-first for a widening input layer (13 / 63 / 313 / 363 -> 1000: aggregate fin columns)
         return up if (i > 0 or 4 * fout <= 5 * fin) else (3 if up == 3 else 2)
 
-    def _plan_kinds(self, f0: int, n: int, cached: bool = False):
+    def _plan_kinds(self, f0: int, n: int, cached: bool = False, train: bool = True):
         """Layer kinds of the one-call step (gte_gcnsage_step) or None when the configuration needs the call-by-call path.
-        ``cached``: the batch carries ``agg_p3`` (the resident image of the input's mean aggregate behind its row map)."""
+        ``cached``: the batch carries ``agg_p3`` (the resident image of the input's mean aggregate behind its row map).
+        ``train`` False: the evaluation forward (no dropout layers)."""
         layers = list(self.model.layers)
-        if (not self.use_c_step or not self._planes_on() or len(layers) < 2 or len(layers) > 8 or ops._timers is not None):
+        drop = train and self.dropout_p > 0
+        if (not self.use_c_step or not (drop or self._planes_on()) or len(layers) < 2 or len(layers) > 8 or ops._timers is not None):
             return None
         dims = [f0] + [l.out_feats for l in layers]
         last = len(layers) - 1
@@ -562,11 +597,12 @@ class FusedGcnSageStep(TrainStep):
             return None
         kinds = []
         for i, L in enumerate(layers[:-1]):
-            k = self._layer_kind(i, L, dims[i], n, cached)
+            k = self._layer_kind(i, L, dims[i], n, cached, train)
             if k is None:
                 return None
-            # (the planes GEMMs address their output through 32-bit buffer offsets: [n][2 ld] fp32 must stay below 2 GB)
-            if k != 1 and (n + 256) * 2 * _c16(L.out_feats) * 4 >= (1 << 31):
+            # (the planes GEMMs address their output through 32-bit buffer offsets: [n][2 ld] fp32 must stay below 2 GB; a dropout
+            # layer's G is [n][2 ceil16(fin)])
+            if k != 1 and (n + 256) * 2 * max(_c16(L.out_feats), _c16(dims[i]) if k == 4 else 0) * 4 >= (1 << 31):
                 return None
             kinds.append(k)
         return kinds
@@ -603,7 +639,7 @@ class FusedGcnSageStep(TrainStep):
         last = len(layers) - 1
         out_gemm = not (self._narrow(layers[last], dims[last]) and
                         (self._fused_head(last, layers[last], dims[last]) or self._narrow_padded(layers[last], dims[last])))
-        gen = out_gemm or any(k in (2, 3) or (k == 0 and not self._planes_layer(i, layers[i], dims[i])) for i, k in enumerate(kinds))
+        gen = out_gemm or any(k in (2, 3, 4) or (k == 0 and not self._planes_layer(i, layers[i], dims[i])) for i, k in enumerate(kinds))
         return gen, out_gemm
 
     def _weight_images_gen(self, dims, kinds, out_gemm: bool):
@@ -640,12 +676,18 @@ class FusedGcnSageStep(TrainStep):
                     descs.append(_lib.P3Desc(wp, ldw, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
                     descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fin, fout, 1, bwd.at(0, ld // 16), bwd.ldp))
                 imgs[i] = (fwd, bwd)
-            elif k in (2, 3):
+            elif k in (2, 3, 4):
                 kp = _c16(fin)
                 fwd = img(fout, 2 * kp)
                 descs.append(_lib.P3Desc(wp, ldw, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
                 descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fout, fin, 0, fwd.at(0, kp // 16), fwd.ldp))
-                imgs[i] = (fwd, None)
+                bwd = None
+                if k == 4 and i > 0:
+                    # G = dz W: the image [2 kp][fout] = [W_s^T ; zero rows ; W_n^T from row kp ; zero rows] (B operand of an NT GEMM)
+                    bwd = img(2 * kp, fout)
+                    descs.append(_lib.P3Desc(wp, ldw, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
+                    descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fin, fout, 1, bwd.at(kp, 0), bwd.ldp))
+                imgs[i] = (fwd, bwd)
         if out_gemm:
             Lo = layers[-1]
             H, C = dims[-2], Lo.out_feats
@@ -716,6 +758,13 @@ class FusedGcnSageStep(TrainStep):
                 if kinds[i] == 3:
                     continue                                      # (both operand images are the batch's: bound per call)
                 sl.hp, sl.ldp_h = P(b["hp"][i].data), b["hp"][i].ldp
+                if kinds[i] == 4:
+                    # the masked operand images [D(x') | D(ahn')]; above layer 0 the input is y of the layer below, and G
+                    sl.ahnp, sl.ldp_ahn = P(b["ahnp"][i].data), b["ahnp"][i].ldp
+                    if i > 0:
+                        sl.x, sl.ldx = P(b["y"][i - 1]), b["ld"][i - 1]
+                        sl.g, sl.ldg = P(b["g"][i]), b["g"][i].shape[1]
+                    continue
                 if kinds[i] == 0:
                     sl.qp = P(b["qp"][i].data)
                 else:
@@ -762,7 +811,18 @@ class FusedGcnSageStep(TrainStep):
         plan.fuse_ln_dx = (int(self.fuse_ln_dx) | (2 if self.fuse_ln_narrow else 0) | (8 if self.fuse_smallk_dx else 0)
                            | (4 if self.fuse_head_gemm else 0) | (16 if self.fuse_ln_fwd else 0))
         L0 = plan.layer[0]
-        if kinds[0] == 3:
+        if kinds[0] == 4:
+            # dropout: the input as fp32 rows or as the (resident) image; the masks of this seed / rank at the device step counter
+            if xp is not None:
+                L0.xp, L0.ldp_x, L0.x, L0.ldx = P(xp.data), xp.ldp, None, 0
+                L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
+            else:
+                L0.xp, L0.ldp_x, L0.h_rows, L0.n_res_rows = None, 0, None, 0
+                L0.x, L0.ldx = P(x), ops._ld(x)
+            self._adam_state()
+            plan.dropout_p, plan.dropout_seed, plan.rank = float(self.dropout_p), self.dropout_seed, self.rank
+            plan.step_counter = P(self._step_dev)
+        elif kinds[0] == 3:
             ap = getattr(g, "agg_p3", None)
             if xp is None or ap is None:
                 raise _lib.GteError("a cached-aggregate input layer needs feat_p3 and agg_p3 (resident images behind a row map, or the graph's own)")
@@ -963,7 +1023,7 @@ class FusedGcnSageStep(TrainStep):
         self._last_wimg = None
         xp = getattr(g, "feat_p3", None)
         n, f0 = (xp.rows, xp.cols) if xp is not None else g.ndata['feat'].shape
-        kinds = self._plan_kinds(f0, n, self._batch_cached(g)) if n > 0 else None
+        kinds = self._plan_kinds(f0, n, self._batch_cached(g), train=False) if n > 0 else None
         if kinds is not None and xp is None and kinds[0] == 0 and n * f0 > self.FORWARD_IMAGE_MAX_ELEMS:
             # fp32 features under a planes input layer: the one-call plan would first write their P3 image (65 us at 21.5 k x 831)
             # -- more than the call saves on a graph of this size; the module path multiplies the fp32 rows directly
@@ -974,8 +1034,13 @@ class FusedGcnSageStep(TrainStep):
                 # a resident batch in image mode carries its features as a P3 image only: the module path reads fp32 rows (the
                 # image holds exactly the fp32 values)
                 g.ndata['feat'] = ops.p3_to_f32(xp)
-            with torch.no_grad():
-                return self.model(g)
+            was = self.model.training
+            self.model.eval()                 # (no dropout in the evaluation forward)
+            try:
+                with torch.no_grad():
+                    return self.model(g)
+            finally:
+                self.model.train(was)
         plan, _fused, b, n, keep = self._bind_plan(g, kinds, with_adam=False)
         capturing = torch.cuda.is_current_stream_capturing()
         sig = (self._param_sig(), b["_wkey"])
@@ -996,10 +1061,20 @@ class FusedGcnSageStep(TrainStep):
             kinds = self._plan_kinds(f0, n, self._batch_cached(g))
             if kinds is not None:
                 return self._c_step(g, labels, grad_scale, kinds, with_adam=bool(self._fuse_adam_req))
+        self._refuse_dropout()
         return self._run(g, labels, grad_scale, len(self.model.layers) - 1, upto_layer, forward=True)
+
+    def _refuse_dropout(self) -> None:
+        if self.dropout_p > 0:
+            raise RuntimeError(f"FusedGcnSageStep: dropout {self.dropout_p} runs on the one-call plan only (gte_gcnsage_step with "
+                               "GTE_LAYER_DROPOUT layers); this step would take the call-by-call schedule, which applies no masks: "
+                               "a switch changed after construction (use_c_step, op timers) or a batch past the plan's size limit "
+                               "((nodes + 256) x 2 x max(ceil16(hidden), ceil16(fin)) fp32 values must stay below 2 GB). "
+                               "Use TrainStep for it.")
 
     def backward_rest(self, g, from_layer: int) -> None:
         """Backward of layers from_layer-1 .. 0 after ``forward_backward(..., upto_layer=from_layer)`` on the same batch."""
+        self._refuse_dropout()
         self._run(g, None, 1.0, from_layer - 1, 0, forward=False)
 
     def _run(self, g, labels, grad_scale, hi, lo, forward):
@@ -1382,6 +1457,12 @@ class FusedGcnSageStep(TrainStep):
     def step(self, g, labels: torch.Tensor, n_global: Optional[int] = None,
              loss_scale: Optional[float] = None) -> torch.Tensor:
         scale = self._dp_scale(labels.shape[0], n_global, loss_scale)
+        if self.distributed and self.dropout_p > 0:
+            # the masks read the device step counter (completed steps) in the forward: bring it up to date first -- what the
+            # optimiser launch behind the all-reduce would do (idempotent there)
+            self.t += 1
+            self._sync_adam_state()
+            self.t -= 1
         if self.distributed and self._dp_split:
             out3 = self.forward_backward(g, labels, scale, upto_layer=1)
             pending = [self._all_reduce_async(self.flat_grad[self._n0:])]    # layers 1.. : in flight under layer 0's backward
@@ -1429,11 +1510,14 @@ class FusedGcnSageStep(TrainStep):
         return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
 
     # -- optimiser: hyper-parameters and step count live on the device, so the launch is graph-capturable ----------
-    def _adam_host_state(self, t_next: int):
-        """{lr, b1, b2, eps, wd, grad_scale, bc1, sqrt(bc2)} for step t_next, bias corrections in double (gte_adam_step)"""
+    def _adam_host_state(self, t_next: int, device_bc: bool = False):
+        """{lr, b1, b2, eps, wd, grad_scale, bc1, sqrt(bc2)} for step t_next, bias corrections in double (gte_adam_step).
+        ``device_bc``: the bias corrections as the optimiser launch advances them on the device after a step (csrc/gte_common.h:
+        from the fp32 betas) -- what a restored step count t_next > 1 must reproduce for a resumed run to equal an uninterrupted one."""
         b1, b2 = float(self.betas[0]), float(self.betas[1])
+        c1, c2 = (float(np.float32(b1)), float(np.float32(b2))) if device_bc else (b1, b2)
         return (float(self.lr), b1, b2, float(self.eps), float(self.weight_decay), 1.0,
-                float(np.float32(1.0 - b1 ** t_next)), float(np.float32(np.sqrt(1.0 - b2 ** t_next))))
+                float(np.float32(1.0 - c1 ** t_next)), float(np.float32(np.sqrt(1.0 - c2 ** t_next))))
 
     def _adam_state(self) -> None:
         if getattr(self, "_hyper", None) is None:
@@ -1448,8 +1532,8 @@ class FusedGcnSageStep(TrainStep):
         """Eager-only: push changed hyper-parameters (lr_scale) / a changed step count (checkpoint restore) to the device.
         The device advances the counter and the bias corrections itself; the host only mirrors the expected values."""
         self._adam_state()
-        want = self._adam_host_state(self.t)
         stale_t = self._step_dev_host != self.t - 1
+        want = self._adam_host_state(self.t, device_bc=stale_t and self.t > 1)
         if stale_t or want[:6] != self._hyper_host[:6]:
             if stale_t:
                 self._step_dev.fill_(self.t - 1)

@@ -115,6 +115,20 @@ def evaluate(model, graph, labels, class_weights=None, engine=None):
     return o[0], o[2] / max(labels.shape[0], 1), pred
 
 
+def train_engine(model, p_drop: float, seed: int, say=print, **kw):
+    """The step engine of train(): the hand-scheduled FusedGcnSageStep (no autograd, gradients written into the flat buffer) for
+    the models it covers -- ReLU, and with 0 < dropout < 1 only where its one-call plan runs the model (counter-based masks
+    seeded by the run's seed: csrc/dropout.h) --, the autograd path (TrainStep) for everything else."""
+    if 0.0 <= p_drop < 1.0:
+        try:
+            return FusedGcnSageStep(model, dropout_seed=seed, **kw)
+        except ValueError as e:
+            if p_drop == 0.0:
+                raise
+            say(f"MODE: dropout {p_drop} on the autograd path ({e})")
+    return TrainStep(model, **kw)
+
+
 LAST_RUN = None          # {"model", "step", "rank", "world"} of the last train() call in this process
 
 
@@ -181,11 +195,9 @@ def train(data, config, name_time=None):
     model = GcnSAGE(in_feats, int(h_layer_dim), n_classes, config.TRAINING.n_layers, F.relu,
                     config.TRAINING.dropout).to(device)
     say(model)
-    # hand-scheduled step (no autograd, gradients written into the flat buffer) for the configuration every
-    # shipped run uses (ReLU, dropout 0); anything else goes through the autograd nodes
-    engine_cls = FusedGcnSageStep if not config.TRAINING.dropout else TrainStep
-    step = engine_cls(model, lr=config.TRAINING.lr, weight_decay=config.TRAINING.weight_decay,
-                      class_weights=class_weights, distributed=distributed)
+    step = train_engine(model, float(config.TRAINING.dropout or 0.0), config.PREPROCESS.get('seed', 42), say=say,
+                        lr=config.TRAINING.lr, weight_decay=config.TRAINING.weight_decay, class_weights=class_weights,
+                        distributed=distributed)
     stopper = EarlyStopping(weights=weights_dir, name=logs, patience=config.TRAINING.es_patience)
     # ReduceLROnPlateau('min', factor=0.5) drives a stand-in optimiser whose lr is mirrored into the engine
     _lr_holder = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=config.TRAINING.lr)
@@ -200,6 +212,9 @@ def train(data, config, name_time=None):
         start_epoch = ck['epoch']
         model.load_state_dict(ck['state_dict'])             # parameters are views of the flat buffer: copies in place
         load_adam_state_dict(step, model, ck['optimizer'])
+        if ck.get('dropout_seed') is not None and hasattr(step, 'dropout_seed'):
+            # (the device step counter comes back from Adam's step count: the resumed run draws the masks of the uninterrupted one)
+            step.dropout_seed = int(ck['dropout_seed'])
         metrics = AttrDict(ck['metrics'])
         ck_layout = ck.get('residency')
         _lr_holder.param_groups[0]['lr'] = step.lr
@@ -419,9 +434,12 @@ def train(data, config, name_time=None):
                 metrics['f1_vect'] = f1_vect.tolist()
             if rank == 0:
                 os.makedirs(ckpt_dir, exist_ok=True)
-                torch.save({'epoch': epoch + 1,
-                            'state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
-                            'optimizer': adam_state_dict(step, model), 'metrics': dict(metrics), 'residency': layout}, ckpt_path)
+                ck_out = {'epoch': epoch + 1,
+                          'state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+                          'optimizer': adam_state_dict(step, model), 'metrics': dict(metrics), 'residency': layout}
+                if getattr(step, 'dropout_p', 0) > 0:
+                    ck_out['dropout_seed'] = step.dropout_seed      # (the masks of a resumed run: csrc/dropout.h)
+                torch.save(ck_out, ckpt_path)
     finally:
         gc.unfreeze()          # a library entry point must not leave the caller's objects in the permanent generation
 

@@ -263,6 +263,64 @@ def spmm_csr_p3(indptr, indices, weight, x: torch.Tensor, n_rows: int, mean: boo
     return out
 
 
+# ---- dropout (csrc/dropout.hip; keep bits of csrc/dropout.h) -------------------------------------------------------------
+def dropout_mask(p: float, seed: int, rank: int, step: int, site: int, n_rows: int, n_cols: int, device=None) -> torch.Tensor:
+    """Keep mask (uint8 [n_rows, n_cols], 1 = kept) of one mask site at one step -- on ``device`` through gte_dropout_mask, or
+    with ``device`` None on the host through gte_dropout_mask_host (no GPU needed).  site 0 = the model's input dropout, i + 1 =
+    hidden layer i's mask over cat(h, ah * norm) (2 fin columns); step = completed optimiser steps at the step that drew it."""
+    lib = _lib.load()
+    seed = int(seed) & ((1 << 64) - 1)
+    if device is None:
+        m = torch.zeros(n_rows, n_cols, dtype=torch.uint8)
+        check(lib.gte_dropout_mask_host(float(p), seed, int(rank), int(step), int(site), n_rows, n_cols, m.data_ptr(), n_cols),
+              "gte_dropout_mask_host")
+        return m
+    m = torch.zeros(n_rows, n_cols, dtype=torch.uint8, device=device)
+    check(lib.gte_dropout_mask(float(p), seed, int(rank), int(step), int(site), n_rows, n_cols, ptr(m), n_cols, current_stream()),
+          "gte_dropout_mask")
+    return m
+
+
+def spmm_dropout_p3(indptr, indices, weight, x, n_rows: int, p: float, seed: int, rank: int, step_counter: torch.Tensor, site: int,
+                    in_dropout: bool, self_out: Optional["P3"] = None, agg_out: Optional["P3"] = None):
+    """The operand images of a dropout layer (gte_spmm_dropout_p3): (D_site(x'[v]), D_site(mean-aggregate(x')[v])) as two P3
+    images, x' = D_0(x) when ``in_dropout``.  ``x``: fp32 rows, or a P3 image (with its row map when resident).
+    ``step_counter``: int64 device tensor holding the step."""
+    lib = _lib.load()
+    if isinstance(x, P3):
+        f, xf, ldx = x.cols, None, 0
+        xp, ldpx, rows, res = ptr(x.data), x.ldp, ptr(x.row_map), x.res_rows
+        dev = x.data.device
+    else:
+        require_device(x, "spmm_dropout_p3")
+        xf = _row_major(x)
+        f, ldx, xp, ldpx, rows, res = xf.shape[1], _ld(xf), None, 0, None, 0
+        dev = xf.device
+    if self_out is None:
+        self_out = P3.empty(n_rows, f, dev)
+    if agg_out is None:
+        agg_out = P3.empty(n_rows, f, dev)
+    check(lib.gte_spmm_dropout_p3(ptr(indptr), ptr(indices), ptr(weight), ptr(xf), ldx, xp, ldpx, rows, res, int(bool(in_dropout)),
+                                  float(p), int(seed) & ((1 << 64) - 1), int(rank), ptr(step_counter), int(site), ptr(self_out.data),
+                                  self_out.ldp, ptr(agg_out.data), agg_out.ldp, n_rows, f, current_stream()), "gte_spmm_dropout_p3")
+    return self_out, agg_out
+
+
+def spmm_dropout_bwd(rindptr, rindices, w_out, g: torch.Tensor, agg_col: int, n_feat: int, p: float, seed: int, rank: int,
+                     step_counter: torch.Tensor, site: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dx = D_site(G[:, :n_feat]) + A_w^T (norm D_site(G[:, agg_col:agg_col + n_feat])) (gte_spmm_dropout_bwd): the gradient
+    of a dropout layer's input from G = dz W.  Returns fp32 [n, round_up(n_feat, 4)] (columns past n_feat zero)."""
+    require_device(g, "spmm_dropout_bwd")
+    lib = _lib.load()
+    n = g.shape[0]
+    if out is None:
+        out = torch.empty(n, -(-n_feat // 4) * 4, dtype=torch.float32, device=g.device)
+    check(lib.gte_spmm_dropout_bwd(ptr(rindptr), ptr(rindices), ptr(w_out), ptr(g), _ld(g), int(agg_col), float(p),
+                                   int(seed) & ((1 << 64) - 1), int(rank), ptr(step_counter), int(site), ptr(out), _ld(out), n, n_feat,
+                                   current_stream()), "gte_spmm_dropout_bwd")
+    return out
+
+
 def gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b: bool = False,
          out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """C = op(A) op(B) in fp32 on the MFMA path.  ``a``/``b`` are the STORED matrices."""

@@ -458,10 +458,43 @@ int gte_batch_assemble_rows(const int32_t* pages, int64_t n_batch, const int32_t
                             int64_t ld_feat, int64_t n_cols, float* feat_out, const float* label, float* label_out,
                             int64_t n_out, int32_t* row_map, int64_t row_map_pad, int64_t n_res_rows, void* stream);
 
+/* ---- dropout (models.py:60-61 and :105-113 of the reference in training mode, 0 < p < 1) ---------------------------------------
+ * Counter-based keep bits (csrc/dropout.h): keep(seed, rank, step, site, row, col) = Philox4x32-10 of counter {col / 4, row, step,
+ * site} under key {seed_lo, seed_hi ^ rank 0x9E3779B9}, word col % 4, >= round(p 2^32).  step = completed optimiser steps (the
+ * plan's device step_counter), site 0 = the model's input dropout, i + 1 = the one mask of hidden layer i over its [n][2 fin]
+ * concatenation cat(h, ah * norm) (columns fin + c = the aggregate half), row = the node's position in the batch.  The bits depend
+ * on nothing else: producers and consumers regenerate them, no mask is stored.  A kept value is v * fp32(1 / (1 - p)) in fp32.
+ * Matching torch's own dropout stream is not a goal (its element-to-counter mapping follows its launch grid).
+ * gte_dropout_mask: TEST HOOK -- mask [n_rows][ldm] (uint8, 1 = kept) of one site at a host-given step, on the device.
+ * gte_dropout_mask_host: the same bits from plain C++ (no HIP call: usable without a GPU). */
+int gte_dropout_mask(float p, uint64_t seed, int rank, int64_t step, int site, int64_t n_rows, int64_t n_cols, uint8_t* mask,
+                     int64_t ldm, void* stream);
+int gte_dropout_mask_host(float p, uint64_t seed, int rank, int64_t step, int site, int64_t n_rows, int64_t n_cols, uint8_t* mask,
+                          int64_t ldm);
+/* Producer of a dropout layer's operands (models.py:53-61 in training mode): with x' = D_0(x) when in_dropout (layer 0: the
+ * model's input dropout applied to every gathered row and to the row's own features) else x,
+ *     selfp3 = D_site(x'[v]),   aggp3 = D_site(scale_v sum_{u -> v} w_e x'[u])     (scale_v = 1 / in-degree, 0 without in-edges)
+ * as two P3 images [n_rows][n_feat] (columns up to the next multiple of 16 written as zeros), the mask of the agg half at columns
+ * n_feat + c.  The aggregation is gte_spmm_csr_p3's (same weights, norm, CSR summation order).  Input: fp32 rows x (ldx) OR a P3
+ * image xp (ldpx bytes per row) whose row u is resident row x_rows[u] (x_rows NULL: row u) -- the resident feature images of the
+ * train loop, decoded exactly.  step = *step_counter (device memory: captured replays draw fresh masks).  site >= 1. */
+int gte_spmm_dropout_p3(const int32_t* indptr, const int32_t* indices, const float* eweight, const float* x, int64_t ldx,
+                        const void* xp, int64_t ldpx, const int32_t* x_rows, int64_t n_res_rows, int in_dropout, float p, uint64_t seed,
+                        int rank, const int64_t* step_counter, int site, void* selfp3, int64_t ldp_self, void* aggp3, int64_t ldp_agg,
+                        int64_t n_rows, int64_t n_feat, void* stream);
+/* Backward of the above through the masks, for a layer whose input has a gradient (layer > 0): with G = dz W [n_rows][ldg]
+ * (columns 0 .. n_feat the self half, agg_col .. agg_col + n_feat the aggregate half),
+ *     dx[v] = D_site(G[v, self]) + sum_{v -> u} w_out D_site(G[u, agg])   (out-edge CSR, w_out = w / in_degree(dst); row u's mask)
+ * dx [n_rows][lddx] fp32, columns n_feat .. round_up(n_feat, 4) written as zeros.  g, dx 16-byte aligned; agg_col, ldg, lddx
+ * multiples of 4; agg_col >= round_up(n_feat, 4), ldg >= agg_col + round_up(n_feat, 4). */
+int gte_spmm_dropout_bwd(const int32_t* rindptr, const int32_t* rindices, const float* w_out, const float* g, int64_t ldg,
+                         int64_t agg_col, float p, uint64_t seed, int rank, const int64_t* step_counter, int site, float* dx,
+                         int64_t lddx, int64_t n_rows, int64_t n_feat, void* stream);
+
 /* ---- one optimisation step from a prepared plan -------------------------------------------------------------------------
  * replaces the batch loop body of model_train.py:320-332 (logits = model(g); loss; zero_grad; backward; optimizer.step())
- * for the configuration every shipped run of the reference uses -- GcnSAGE with ReLU + LayerNorm hidden layers, dropout 0,
- * a class-count-wide output layer -- as ONE host call: the launches of a step (see models/engine.py for the same sequence
+ * for GcnSAGE with ReLU + LayerNorm hidden layers and a class-count-wide output layer -- dropout 0 (every shipped run of the
+ * reference), or 0 < p < 1 with every hidden layer a GTE_LAYER_DROPOUT layer (dropout_p below) -- as ONE host call: the launches of a step (see models/engine.py for the same sequence
  * issued call by call) are issued from here, so the host cost of a step no longer grows with its ~17 launches (the
  * BBOX-only configurations, F0 = 13, were host-bound at ~0.25 ms of ctypes calls per 0.37 ms step).
  * The plan only borrows device pointers; nothing is allocated or synchronised.  Layer kinds:
@@ -481,8 +514,15 @@ int gte_batch_assemble_rows(const int32_t* pages, int64_t n_batch, const int32_t
  *   GTE_LAYER_CACHED  input layer whose input AND its mean aggregate are RESIDENT P3 images read through the batch's row map
  *                     (hp / ahnp + h_rows): z = [x | ahn] W^T + b (gte_gemm_p3_nt_rows2), LayerNorm + ReLU; dW = [dz^T x | dz^T ahn]
  *                     (gte_gemm_p3_tn_rows2).  No aggregation, no q, no copy of the input in the step.  Any fin >= 16, fout <= 1024
+ *   GTE_LAYER_DROPOUT hidden layer of a plan with dropout_p > 0 (then EVERY hidden layer is one; any depth, any fin, fout <= 1024):
+ *                     aggregate-first, because the mask sits between the aggregation and W.  gte_spmm_dropout_p3 writes hp = D(x')
+ *                     and ahnp = D(norm A_w x') (layer 0 also applies the input dropout; its input is x, or the image xp through
+ *                     h_rows; a layer above reads x = y of the layer below), then the GEMM + LayerNorm + ReLU of AGGFIRST, z in t.
+ *                     Backward: dW = dz^T [hp | ahnp] (TN, two segments); layer > 0 also G = dz W (planes NT on wimg_bwd = P3
+ *                     [2 ceil16(fin)][fout] = [W_s^T ; W_n^T], the W_n^T rows from ceil16(fin)) into g, then gte_spmm_dropout_bwd
+ *                     writes dy of the layer below.  No fused dX + LayerNorm-backward GEMM across a dropout layer.
  */
-enum gte_layer_kind { GTE_LAYER_PLANES = 0, GTE_LAYER_SMALLK = 1, GTE_LAYER_AGGFIRST = 2, GTE_LAYER_CACHED = 3 };
+enum gte_layer_kind { GTE_LAYER_PLANES = 0, GTE_LAYER_SMALLK = 1, GTE_LAYER_AGGFIRST = 2, GTE_LAYER_CACHED = 3, GTE_LAYER_DROPOUT = 4 };
 typedef struct gte_step_layer {
     int kind;
     int64_t fin, fout;
@@ -505,6 +545,8 @@ typedef struct gte_step_layer {
     void* ws_dw; int64_t ws_dw_bytes;      /* split-K workspace of the layer's dW                           */
     int64_t ldf;                           /* floats per row of y / dy / z (t: 2 ldf): fout rounded up to 16; 0 = fout */
     void* ahnp; int64_t ldp_ahn;           /* AGGFIRST: P3 image of the aggregated input [n][fin]; CACHED: the RESIDENT image of it */
+    const void* xp; int64_t ldp_x;         /* DROPOUT layer 0: the input as a P3 image (through h_rows when set) instead of x  */
+    float* g; int64_t ldg;                 /* DROPOUT layer > 0: G = dz W [n][ldg = 2 ceil16(fin)]                            */
 } gte_step_layer;
 typedef struct gte_step_plan {
     int n_hidden;                          /* hidden layers (1 .. 7), followed by the output layer          */
@@ -545,6 +587,9 @@ typedef struct gte_step_plan {
     /* measurement (NULL: off): hipEvent_t handles, recorded on `stream` in front of ([2 i]) and behind ([2 i + 1]) the forward
      * transform GEMM of hidden layer i -- the roofline figure of a shape is timed inside the loop it belongs to */
     void* const* fwd_events;
+    /* dropout (0 = off): 0 < dropout_p < 1 runs every hidden layer as GTE_LAYER_DROPOUT with the masks of seed / rank at step =
+     * *step_counter (which must then be set, with or without the fused optimiser) */
+    float dropout_p; uint64_t dropout_seed; int rank;
 } gte_step_plan;
 /* *adam_fused: bit 0 = the optimiser step ran inside the fold launch, bit 1 = ... and it wrote the weight images */
 int gte_gcnsage_step(const gte_step_plan* plan, int phase, int* adam_fused, void* stream);
