@@ -272,6 +272,8 @@ class BatchArrays(ctypes.Structure):
 
 GTE_F32, GTE_BF16 = 0, 1
 REDUCE_SUM, REDUCE_MEAN = 0, 1
+# enum gte_layer_kind of include/gte.h (gte_step_layer.kind)
+LAYER_PLANES, LAYER_SMALLK, LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT = 0, 1, 2, 3, 4
 
 _lib = None
 

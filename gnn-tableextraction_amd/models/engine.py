@@ -102,6 +102,7 @@ class TrainStep:
 # Hand-scheduled step for GcnSAGE: no autograd, no per-step allocation, HIP-graph capturable
 # ======================================================================================================
 from .. import _lib                                                     # noqa: E402
+from .._lib import LAYER_PLANES, LAYER_SMALLK, LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT      # noqa: E402
 from ..components.graphs.models import GcnSAGE, _is_relu               # noqa: E402
 import torch.nn as nn                                                  # noqa: E402
 
@@ -179,7 +180,7 @@ class FusedGcnSageStep(TrainStep):
         self._fuse_adam_req, self._adam_fused = False, False
         self.adam_fused_steps = 0                     # steps whose optimiser update ran inside the fold launch
         self.fused_head = os.environ.get("GTE_FUSED_HEAD", "1") == "1"
-        self.fuse_head_gemm = os.environ.get("GTE_FUSE_HEAD_GEMM", "1") == "1"     # (general plans: the fused head on the GEMM output path)
+        self.fuse_head_gemm = os.environ.get("GTE_FUSE_HEAD_GEMM", "1") == "1"     # (out_gemm plans: the fused head on the GEMM output path)
         # dX of a planes layer with the LayerNorm(+ReLU) backward of the planes layer below as its epilogue (gte_gemm_p3_nt_ln_bwd)
         self.fuse_ln_dx = os.environ.get("GTE_FUSE_LN_DX", "1") == "1"
         # ... and of the last hidden layer inside the output layer's backward (gte_sage_narrow_bwd_ln_p3)
@@ -203,7 +204,8 @@ class FusedGcnSageStep(TrainStep):
         # run): z = [x | ahn] W^T from two resident images behind the batch's row map, no aggregation / q / feature copy in the
         # step for layer 0 (GTE_LAYER_CACHED).  Costs a second resident image; GTE_CACHE_AGG=0 turns it off
         self.cache_input_agg = os.environ.get("GTE_CACHE_AGG", "1") == "1"
-        self._wimg = {}                               # layer index -> (forward image, backward image or None)
+        # call-by-call schedule: layer index -> (forward image, backward image or None); one-call plans: _plan_key -> their image set
+        self._wimg = {}
         # weight images in the block-major layout (ops.P3): a K block of the weights is ONE contiguous run, whole cache lines for
         # every NT planes GEMM, and the block-major-weights kernel (gemm_p3_nt_sq_kernel) loads its fragments straight into
         # registers.  GTE_WIMG_BLOCK_MAJOR=0: row-major images (the layout up to round 5; A/B measurements, tests)
@@ -234,6 +236,7 @@ class FusedGcnSageStep(TrainStep):
 
     # -- buffers -------------------------------------------------------------------------------------
     def _alloc(self, cap: int, f0: int):
+        """Buffer set of the call-by-call schedule (_run) only; a one-call plan has its own (_alloc_plan)."""
         dev = self.flat_param.device
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         layers = self.model.layers
@@ -299,11 +302,11 @@ class FusedGcnSageStep(TrainStep):
             need.append(lib.gte_gemm_p3_nt_smallk_bwd_workspace_bytes(cap, 2 * dims[0], dims[1]))
         return max(need)
 
-    # -- buffers of the one-call plan on general widths (padded rows) ----------------------------------
-    def _alloc_gen(self, cap: int, f0: int, kinds, out_gemm: bool):
-        """Buffer set of a one-call plan whose layers are not all in the tuned range (128 <= hidden <= 256, hidden % 16 == 0):
-        the fp32 row buffers of a hidden layer are PADDED to ld = hidden rounded up to 16 floats (include/gte.h, gte_step_layer.ldf),
-        zero-initialised once (the kernels keep the padding zero); images are padded to 16-column blocks by construction."""
+    # -- buffers of the one-call plan (padded rows) -----------------------------------------------------
+    def _alloc_plan(self, cap: int, f0: int, kinds, out_gemm: bool):
+        """Buffer set of a one-call plan: the fp32 row buffers of a hidden layer are PADDED to ld = hidden rounded up to 16 floats
+        (include/gte.h, gte_step_layer.ldf; no padding at a 16-aligned width), zero-initialised once (the kernels keep the padding
+        zero); images are padded to 16-column blocks by construction."""
         dev, lib = self.flat_param.device, self.lib
         layers = list(self.model.layers)
         dims = [f0] + [l.out_feats for l in layers]
@@ -316,19 +319,20 @@ class FusedGcnSageStep(TrainStep):
             t = ops.P3.empty(rows, cols, dev)
             t.data.zero_()
             return t
-        b = {"cap": cap, "gen": True, "kinds": tuple(kinds), "out_gemm": bool(out_gemm), "ld": ld, "pl": [k == 0 for k in kinds]}
-        b["t"] = [z32(cap, 2 * ld[i]) if kinds[i] == 0 else z32(cap, ld[i]) for i in range(nh)]       # [t_self | t_neigh], or z
+        b = {"cap": cap, "ld": ld}
+        b["t"] = [z32(cap, 2 * ld[i]) if kinds[i] == LAYER_PLANES else z32(cap, ld[i]) for i in range(nh)]     # [t_self | t_neigh], or z
         b["y"] = [z32(cap, ld[i]) for i in range(nh)]
         b["dy"] = [z32(cap, ld[i]) for i in range(nh)]
         b["stats"] = [z32(2 * cap) for _ in range(nh)]
-        b["ahn"] = [z32(cap, dims[0]) if kinds[i] == 1 else None for i in range(nh)]
-        b["ahnp"] = [img(cap, dims[i]) if kinds[i] in (2, 4) else None for i in range(nh)]
+        b["ahn"] = [z32(cap, dims[0]) if kinds[i] == LAYER_SMALLK else None for i in range(nh)]
+        b["ahnp"] = [img(cap, dims[i]) if kinds[i] in (LAYER_AGGFIRST, LAYER_DROPOUT) else None for i in range(nh)]
         # a dropout layer above layer 0: G = dz W [n][2 ceil16(fin)] (self half, then the aggregate half from column ceil16(fin))
-        b["g"] = [z32(cap, 2 * _c16(dims[i])) if (kinds[i] == 4 and i > 0) else None for i in range(nh)]
-        b["hp"] = [img(cap, dims[i]) if kinds[i] not in (1, 3) else None for i in range(nh)]      # (3: both operands are resident)
-        b["dzp"] = [img(cap, dims[i + 1]) if kinds[i] != 1 else None for i in range(nh)]
-        b["qp"] = [img(cap, dims[i + 1]) if kinds[i] == 0 else None for i in range(nh)]
-        b["ws_dw"] = [u8(lib.gte_gemm_p3_tn_workspace_bytes(dims[i + 1], 2 * dims[i], dims[i], cap) if kinds[i] != 1
+        b["g"] = [z32(cap, 2 * _c16(dims[i])) if (kinds[i] == LAYER_DROPOUT and i > 0) else None for i in range(nh)]
+        # (a cached layer reads both operands from resident images)
+        b["hp"] = [img(cap, dims[i]) if kinds[i] not in (LAYER_SMALLK, LAYER_CACHED) else None for i in range(nh)]
+        b["dzp"] = [img(cap, dims[i + 1]) if kinds[i] != LAYER_SMALLK else None for i in range(nh)]
+        b["qp"] = [img(cap, dims[i + 1]) if kinds[i] == LAYER_PLANES else None for i in range(nh)]
+        b["ws_dw"] = [u8(lib.gte_gemm_p3_tn_workspace_bytes(dims[i + 1], 2 * dims[i], dims[i], cap) if kinds[i] != LAYER_SMALLK
                          else self._ws_dw_bytes(i, dims, cap)) for i in range(nh)]
         b["ws_ln"] = [u8(max(lib.gte_ln_relu_bwd_workspace_bytes(cap, dims[i + 1]),
                              lib.gte_gemm_p3_nt_ln_bwd_workspace_bytes(cap, dims[i + 1]) if dims[i + 1] <= 256 else 0,
@@ -348,43 +352,61 @@ class FusedGcnSageStep(TrainStep):
             b["ws_nar"] = u8(lib.gte_sage_narrow_bwd_workspace_bytes(cap, min(_c16(dims[-2]), 256), min(C, 16)))
         return b
 
-    def _buffers_gen(self, n: int, f0: int, kinds, out_gemm: bool):
-        """The (capacity-sized, shared or captured-batch-private) buffer set of a general plan; see _buffers."""
-        key = ("gen", f0, tuple(kinds), bool(out_gemm))
+    def _private_set(self, key, n: int, alloc):
+        """The exact-size buffer set ``key`` of the batch being captured (made by ``alloc(n)`` at first use, never reallocated)."""
+        k2 = (self._private_key, key)
+        full = self._graph_bufs.get(k2)
+        if full is None:
+            full = self._graph_bufs[k2] = alloc(n)
+        if full["cap"] < n:
+            raise RuntimeError(f"captured batch buffers hold {full['cap']} nodes; asked for {n} (a captured batch must not change)")
+        return full
+
+    @staticmethod
+    def _plan_key(f0: int, kinds, out_gemm: bool):
+        """What names a one-call plan's layout: the key of its buffer set and the tag of its weight-image set."""
+        return ("gen", f0, tuple(kinds), bool(out_gemm))
+
+    def _buffers_plan(self, n: int, f0: int, kinds, out_gemm: bool):
+        """The (capacity-sized, shared or captured-batch-private) buffer set of a one-call plan; see _buffers."""
+        key = self._plan_key(f0, kinds, out_gemm)
         if self._private_key is not None:
-            store, k2 = self._graph_bufs, (self._private_key, key)
-            full = store.get(k2)
-            if full is None:
-                full = store[k2] = self._alloc_gen(n, f0, kinds, out_gemm)
-            if full["cap"] < n:
-                raise RuntimeError(f"captured batch buffers hold {full['cap']} nodes; asked for {n} (a captured batch must not change)")
-            return full
+            return self._private_set(key, n, lambda m: self._alloc_plan(m, f0, kinds, out_gemm))
         full = self._bufs.get(key)
         if full is None or full["cap"] < n:
             cap = max(-(-int(n * 1.125) // 4096) * 4096, getattr(self, "_reserved", {}).get(f0, 0))
             self._bufs.pop(key, None)
-            full = self._bufs[key] = self._alloc_gen(cap, f0, kinds, out_gemm)
+            full = self._bufs[key] = self._alloc_plan(cap, f0, kinds, out_gemm)
         return full
 
-    def _buffers(self, n: int, f0: int, private=None):
-        """Row views [0:n] of buffers allocated for a CAPACITY, not for n: in the real loop every batch has a
-        different node count, and per-count buffers would grow without bound (~300 MB per new count at F0=831).
+    def plan_buffers(self, batch, private_key=None):
+        """(buffer set, layer kinds, out_gemm) of the one-call plan a training step on ``batch`` runs on -- the shared set, or the
+        private set of the batch captured under ``private_key`` (capture(): ``id`` of its graph) -- for tests and tools that read
+        what a step left behind.  None when that step is not on a plan (call-by-call schedule), or no such step has run yet."""
+        xp = getattr(batch, "feat_p3", None)
+        n, f0 = (xp.rows, xp.cols) if xp is not None else batch.ndata['feat'].shape
+        kinds = self._plan_kinds(f0, n, self._batch_cached(batch))
+        if kinds is None:
+            return None
+        out_gemm = self._plan_mode(kinds, f0)[1]
+        key = self._plan_key(f0, kinds, out_gemm)
+        full = self._bufs.get(key) if private_key is None else self._graph_bufs.get((private_key, key))
+        return None if full is None else (full, kinds, out_gemm)
+
+    def _buffers(self, n: int, f0: int):
+        """Row views [0:n] of the call-by-call schedule's (_run) buffers, allocated for a CAPACITY, not for n: in the real loop
+        every batch has a different node count, and per-count buffers would grow without bound (~300 MB per new count at F0=831).
         The shared set grows geometrically to the largest batch seen.  A captured HIP graph bakes pointers in,
-        so each captured batch owns a private exact-size set (``private`` = its key) that is never reallocated."""
-        if private is not None:
-            full = self._graph_bufs.get(private)
-            if full is None:
-                full = self._graph_bufs[private] = self._alloc(n, f0)
-                full["f0"] = f0
-            if full["cap"] < n or full["f0"] != f0:
-                raise RuntimeError(f"captured batch buffers hold {full['cap']} nodes x {full['f0']} features; "
-                                   f"asked for {n} x {f0} (a captured batch must not change)")
+        so each captured batch owns a private exact-size set that is never reallocated."""
+        key = (f0, self._planes_on())                  # the layer plan (which layers take P3 operands) depends on the GEMM mode
+        if self._private_key is not None:
+            full = self._private_set(key, n, lambda m: self._alloc(m, f0))
         else:
-            key = (f0, self._planes_on())              # the layer plan (which layers take P3 operands) depends on the GEMM mode
             full = self._bufs.get(key)
             if full is None or full["cap"] < n:
-                cap = -(-int(n * 1.125) // 4096) * 4096
-                self._bufs = {k: v for k, v in self._bufs.items() if k[0] != f0}     # one set per input width alive
+                # (at least the reserved capacity: a shape whose steps usually run on a plan is not sized by reserve())
+                cap = max(-(-int(n * 1.125) // 4096) * 4096, getattr(self, "_reserved", {}).get(f0, 0))
+                self._bufs = {k: v for k, v in self._bufs.items() if k[0] != f0}     # one call-by-call set per input width alive
                 full = self._bufs[key] = self._alloc(cap, f0)
         v = lambda t: None if t is None else t[:n]
         return {"ahn": [v(t) for t in full["ahn"]], "t": [v(t) for t in full["t"]], "z": [v(t) for t in full["z"]],
@@ -398,16 +420,16 @@ class FusedGcnSageStep(TrainStep):
                 "qp": [None if t is None else t.view_rows(n) for t in full["qp"]]}
 
     def reserve(self, n_nodes: int, f0: int, cached: bool = False) -> None:
-        """Size the shared per-batch buffers for batches of up to ``n_nodes`` nodes now (the train loop knows the largest batch
+        """Size the shared per-batch buffers for batches of up to ``n_nodes`` nodes (the train loop knows the largest batch
         its page table can produce): no reallocation -- a device synchronisation plus ~12 KB per node of new buffers -- later,
-        in the middle of an epoch."""
+        in the middle of an epoch.  A one-call plan takes the recorded capacity when it allocates its set at the first step
+        (``cached``: the batches bring the aggregate image); the call-by-call schedule's set is allocated here."""
         cap = -(-int(n_nodes) // 4096) * 4096
         if not hasattr(self, "_reserved"):
             self._reserved = {}
         self._reserved[f0] = max(self._reserved.get(f0, 0), cap)
-        kinds = self._plan_kinds(f0, 0, cached)     # (cached: the batches bring the aggregate image -> the general plan's buffer set)
-        if kinds is not None and self._plan_mode(kinds, f0)[0]:
-            return                      # a general plan allocates its own (padded) set at this capacity on first use
+        if self._plan_kinds(f0, 0, cached) is not None:
+            return                      # a one-call plan allocates its own set (_buffers_plan) at this capacity on first use
         key = (f0, self._planes_on())
         full = self._bufs.get(key)
         if n_nodes > 0 and (full is None or full["cap"] < n_nodes):
@@ -468,7 +490,7 @@ class FusedGcnSageStep(TrainStep):
         """True when layer 0 takes its input as a P3 image: the train loop then keeps the resident features as images and
         assembles batches of image rows (graph.ResidentPages.enable_p3)."""
         L = self.model.layers[0]
-        return self._layer_kind(0, L, f0) == 0
+        return self._layer_kind(0, L, f0) == LAYER_PLANES
 
     def _param_sig(self):
         return (self.flat_param._version,) + tuple(p._version for p in self.model.parameters())
@@ -478,9 +500,10 @@ class FusedGcnSageStep(TrainStep):
         forward converts the weight images again."""
         self._wimg_sig = None
 
-    def _weight_images(self, dims, launch=True):
-        """P3 images of the planes layers' weights: forward [W_s rows ; W_n rows] x fin, backward (dX) [fin rows] x [W_s^T | W_n^T].
-        ONE launch in front of every forward (the parameters change every step; the launch is part of a captured step)."""
+    def _weight_images(self, dims):
+        """The call-by-call schedule's (_run) conversion launch: P3 images of the planes layers' weights, forward [W_s rows ; W_n rows]
+        x fin, backward (dX) [fin rows] x [W_s^T | W_n^T].  ONE launch in front of every forward (the parameters change every step;
+        the launch is part of a captured step).  A one-call plan has its own images and descriptors (_weight_images_gen)."""
         layers = self.model.layers
         descs = []
         for i, L in enumerate(layers):
@@ -505,13 +528,11 @@ class FusedGcnSageStep(TrainStep):
             if bwd is not None:
                 descs.append(_lib.P3Desc(wp, ld, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
                 descs.append(_lib.P3Desc(wp + 4 * fin, ld, fin, fout, 1, bwd.at(0, fout // 16), bwd.ldp))
-        self._wimg_descs = descs
-        if launch:
-            st = _lib.current_stream()
-            for k in range(0, len(descs), 16):
-                chunk = descs[k:k + 16]
-                arr = (_lib.P3Desc * len(chunk))(*chunk)
-                _lib.check(self.lib.gte_p3_from_f32_batch(ctypes.addressof(arr), len(chunk), st), "gte_p3_from_f32_batch")
+        st = _lib.current_stream()
+        for k in range(0, len(descs), 16):
+            chunk = descs[k:k + 16]
+            arr = (_lib.P3Desc * len(chunk))(*chunk)
+            _lib.check(self.lib.gte_p3_from_f32_batch(ctypes.addressof(arr), len(chunk), st), "gte_p3_from_f32_batch")
 
     # -- the whole step as one host call (gte_gcnsage_step) ---------------------------------------------
     def _smallk_bwd(self, i: int, layer, fin: int) -> bool:
@@ -538,7 +559,8 @@ class FusedGcnSageStep(TrainStep):
         L = self.model.layers[0]
         if self.dropout_p > 0:
             return False                  # (layer 0 aggregates the DROPPED input: a cached aggregate of x is of no use)
-        return len(self.model.layers) >= 2 and self._cached_layer0(L, f0) and self._layer_kind(0, L, f0) in (0, 2)
+        return (len(self.model.layers) >= 2 and self._cached_layer0(L, f0)
+                and self._layer_kind(0, L, f0) in (LAYER_PLANES, LAYER_AGGFIRST))
 
     def wants_resident_images(self, f0: int) -> bool:
         """True when the train loop should keep the resident features as images (and hand out row-map batches): layer 0 takes its
@@ -546,7 +568,7 @@ class FusedGcnSageStep(TrainStep):
         63 / 313 / 363 -> 1000, 63 -> 206 of the reference's runs: without the cache such a layer copies its fp32 rows per batch and
         makes both images per step."""
         if self.dropout_p > 0:            # a dropout layer 0 reads the resident feature image through the batch's row map
-            return self._layer_kind(0, self.model.layers[0], f0) == 4
+            return self._layer_kind(0, self.model.layers[0], f0) == LAYER_DROPOUT
         return self.wants_p3_features(f0) or self.wants_agg_image(f0)
 
     def _layer_kind(self, i: int, L, fin: int, n: int = 0, cached: bool = False, train: bool = True):
@@ -561,23 +583,23 @@ class FusedGcnSageStep(TrainStep):
             # between the aggregation and W).  Its GEMMs are the planes GEMMs whatever the GEMM mode: the only dropout path
             ok = (isinstance(L.lynorm, nn.LayerNorm) and L.linear.bias is not None and (L.activation is None or _is_relu(L.activation))
                   and self.general_planes and fout <= 1024)
-            return 4 if ok else None
+            return LAYER_DROPOUT if ok else None
         if not (self._planes_on() and isinstance(L.lynorm, nn.LayerNorm) and L.linear.bias is not None
                 and (L.activation is None or _is_relu(L.activation))):
             return None
         # (an input layer on images -- kind 0 or 2 -- moves to the cached form when the batch brings the second image)
-        up = 3 if (i == 0 and cached and self._cached_layer0(L, fin)) else 0
+        up = LAYER_CACHED if (i == 0 and cached and self._cached_layer0(L, fin)) else LAYER_PLANES
         if self._planes_layer(i, L, fin, n):
             return up                                            # the tuned range: 128 <= fout <= 256, fout % 16 == 0
         if (i == 0 and not self._transform_first(L, fin) and fout % 16 == 0
                 and bool(self.lib.gte_sage_linear_fwd_fuses_ln(2 * fin, fout)) and not ops.use_tiled(n, fin, None)):
-            return 1
+            return LAYER_SMALLK
         if not self.general_planes or fout > 1024:
             return None
         # transform-first while the layer does not widen by more than a quarter (the aggregation then moves fout columns: 1000
         # against 831 costs less than a per-batch fp32 copy of the input rows, and layer 0 reads the RESIDENT image through the row
         # map); aggregate-first for a widening input layer (13 / 63 / 313 / 363 -> 1000: aggregate fin columns)
-        return up if (i > 0 or 4 * fout <= 5 * fin) else (3 if up == 3 else 2)
+        return up if (i > 0 or 4 * fout <= 5 * fin) else (LAYER_CACHED if up == LAYER_CACHED else LAYER_AGGFIRST)
 
     def _plan_kinds(self, f0: int, n: int, cached: bool = False, train: bool = True):
         """Layer kinds of the one-call step (gte_gcnsage_step) or None when the configuration needs the call-by-call path.
@@ -602,7 +624,8 @@ class FusedGcnSageStep(TrainStep):
                 return None
             # (the planes GEMMs address their output through 32-bit buffer offsets: [n][2 ld] fp32 must stay below 2 GB; a dropout
             # layer's G is [n][2 ceil16(fin)])
-            if k != 1 and (n + 256) * 2 * max(_c16(L.out_feats), _c16(dims[i]) if k == 4 else 0) * 4 >= (1 << 31):
+            ld_max = max(_c16(L.out_feats), _c16(dims[i]) if k == LAYER_DROPOUT else 0)
+            if k != LAYER_SMALLK and (n + 256) * 2 * ld_max * 4 >= (1 << 31):
                 return None
             kinds.append(k)
         return kinds
@@ -631,24 +654,25 @@ class FusedGcnSageStep(TrainStep):
         return xp is not None and ap is not None and (xp.row_map is None) == (ap.row_map is None)
 
     def _plan_mode(self, kinds, f0: int):
-        """(general, out_gemm) of a plan: ``general`` = it runs on the padded buffer set (_alloc_gen) -- some hidden layer lies
-        outside the tuned range or the output layer runs on the planes GEMMs; ``out_gemm`` = the latter (hidden width beyond the
-        narrow kernels: > 256 or not a multiple of 8)."""
+        """(general, out_gemm) of a plan, a description only -- every plan is bound and buffered the same way: ``general`` = some
+        hidden layer lies outside the tuned range (128 <= hidden <= 256, hidden % 16 == 0: no padded rows there) or the output layer
+        runs on the planes GEMMs; ``out_gemm`` = the latter (hidden width beyond the narrow kernels: > 256 or not a multiple of 8)."""
         layers = list(self.model.layers)
         dims = [f0] + [l.out_feats for l in layers]
         last = len(layers) - 1
         out_gemm = not (self._narrow(layers[last], dims[last]) and
                         (self._fused_head(last, layers[last], dims[last]) or self._narrow_padded(layers[last], dims[last])))
-        gen = out_gemm or any(k in (2, 3, 4) or (k == 0 and not self._planes_layer(i, layers[i], dims[i])) for i, k in enumerate(kinds))
+        gen = out_gemm or any(k in (LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT)
+                              or (k == LAYER_PLANES and not self._planes_layer(i, layers[i], dims[i])) for i, k in enumerate(kinds))
         return gen, out_gemm
 
     def _weight_images_gen(self, dims, kinds, out_gemm: bool):
-        """Weight images of a general plan (kept per (kinds, out_gemm)) and their conversion descriptors.  A planes layer's forward
+        """Weight images of a one-call plan (kept per _plan_key) and their conversion descriptors.  A planes layer's forward
         image holds [W_s rows ; zero rows up to ld ; W_n rows ; zero rows] (ld = fout rounded up to 16: the two halves of t start on
         16-column boundaries), its backward image [fin] x [W_s^T | W_n^T] with the second segment at column block ld / 16; an
         aggregate-first layer's image is [fout] x [W_s | W_n] with the second K segment at block ceil(fin / 16); the output
         layer's images are [32] x [H] (rows 0.. = W_s, 16.. = W_n) and [H] x [32].  Allocated zeroed: the padding is never written."""
-        key = ("gen", tuple(dims), tuple(kinds), bool(out_gemm))
+        key = self._plan_key(dims[0], kinds, out_gemm)
         hit = self._wimg.get(key)
         if hit is not None:
             return hit
@@ -665,7 +689,7 @@ class FusedGcnSageStep(TrainStep):
             fin, fout = dims[i], L.out_feats
             W = L.linear.weight
             wp, ldw = W.data_ptr(), W.stride(0)
-            if k == 0:
+            if k == LAYER_PLANES:
                 ld = _c16(fout)
                 fwd = img(2 * ld, fin)
                 descs.append(_lib.P3Desc(wp, ldw, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
@@ -676,13 +700,13 @@ class FusedGcnSageStep(TrainStep):
                     descs.append(_lib.P3Desc(wp, ldw, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
                     descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fin, fout, 1, bwd.at(0, ld // 16), bwd.ldp))
                 imgs[i] = (fwd, bwd)
-            elif k in (2, 3, 4):
+            elif k in (LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT):
                 kp = _c16(fin)
                 fwd = img(fout, 2 * kp)
                 descs.append(_lib.P3Desc(wp, ldw, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
                 descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fout, fin, 0, fwd.at(0, kp // 16), fwd.ldp))
                 bwd = None
-                if k == 4 and i > 0:
+                if k == LAYER_DROPOUT and i > 0:
                     # G = dz W: the image [2 kp][fout] = [W_s^T ; zero rows ; W_n^T from row kp ; zero rows] (B operand of an NT GEMM)
                     bwd = img(2 * kp, fout)
                     descs.append(_lib.P3Desc(wp, ldw, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
@@ -705,8 +729,10 @@ class FusedGcnSageStep(TrainStep):
         hit = self._wimg[key] = (imgs, arr, len(descs))
         return hit
 
-    def _bind_plan_gen(self, g, kinds, with_adam: bool, out_gemm: bool):
-        """_bind_plan for a general plan (padded buffer set, _alloc_gen)."""
+    def _bind_plan(self, g, kinds, with_adam: bool):
+        """The gte_step_plan of this layer plan (cached with the buffer set whose addresses it holds, _alloc_plan) with the
+        per-batch fields -- graph, features, node count -- set for ``g``.  Returns (plan, fused flag, {out3, logits rows, image-set
+        tag}, node count, tensors the plan points at)."""
         lib, P = self.lib, _lib.ptr
         xp = getattr(g, "feat_p3", None)
         if xp is not None:
@@ -715,7 +741,8 @@ class FusedGcnSageStep(TrainStep):
             x = ops._row_major(g.ndata['feat'])
             _lib.require_device(x, "FusedGcnSageStep")
             n, f0 = x.shape
-        b = self._buffers_gen(n, f0, kinds, out_gemm)
+        out_gemm = self._plan_mode(kinds, f0)[1]
+        b = self._buffers_plan(n, f0, kinds, out_gemm)
         layers = list(self.model.layers)
         dims = [f0] + [l.out_feats for l in layers]
         nh = len(layers) - 1
@@ -723,7 +750,7 @@ class FusedGcnSageStep(TrainStep):
         csr, rcsr = g.in_csr(), g.out_csr()
         w_in, w_out = g.in_weights(ew), g.out_weights(ew, True)
         plans = b.setdefault("_plans", {})
-        cached = plans.get(("gen", with_adam))
+        cached = plans.get(with_adam)
         if cached is None:
             imgs, arr, n_desc = self._weight_images_gen(dims, kinds, out_gemm)
             plan = _lib.StepPlan()
@@ -738,7 +765,7 @@ class FusedGcnSageStep(TrainStep):
                 sl.gW, sl.gbias = P(gs[id(L.linear.weight)]), P(gs[id(L.linear.bias)])
                 sl.ggamma, sl.gbeta = P(gs[id(L.lynorm.weight)]), P(gs[id(L.lynorm.bias)])
                 last_hidden = i == nh - 1
-                nxt_img = (not last_hidden and kinds[i + 1] == 0) or (last_hidden and out_gemm)
+                nxt_img = (not last_hidden and kinds[i + 1] == LAYER_PLANES) or (last_hidden and out_gemm)
                 # the layer's output: as an image for a planes consumer, as fp32 rows for the narrow output kernels
                 if nxt_img:
                     yp = b["hp_out"] if last_hidden else b["hp"][i + 1]
@@ -747,7 +774,7 @@ class FusedGcnSageStep(TrainStep):
                 sl.t, sl.stats, sl.dy = P(b["t"][i]), P(b["stats"][i]), P(b["dy"][i])
                 sl.ws_ln, sl.ws_ln_bytes = P(b["ws_ln"][i]), b["ws_ln"][i].numel()
                 sl.ws_dw, sl.ws_dw_bytes = P(b["ws_dw"][i]), b["ws_dw"][i].numel()
-                if kinds[i] == 1:
+                if kinds[i] == LAYER_SMALLK:
                     sl.ahn = P(b["ahn"][i])
                     continue
                 wf, wb = imgs[i]
@@ -755,17 +782,17 @@ class FusedGcnSageStep(TrainStep):
                 if wb is not None:
                     sl.wimg_bwd, sl.ldp_wbwd = P(wb.data), wb.ldp
                 sl.dzp, sl.ldp_o = P(b["dzp"][i].data), b["dzp"][i].ldp
-                if kinds[i] == 3:
+                if kinds[i] == LAYER_CACHED:
                     continue                                      # (both operand images are the batch's: bound per call)
                 sl.hp, sl.ldp_h = P(b["hp"][i].data), b["hp"][i].ldp
-                if kinds[i] == 4:
+                if kinds[i] == LAYER_DROPOUT:
                     # the masked operand images [D(x') | D(ahn')]; above layer 0 the input is y of the layer below, and G
                     sl.ahnp, sl.ldp_ahn = P(b["ahnp"][i].data), b["ahnp"][i].ldp
                     if i > 0:
                         sl.x, sl.ldx = P(b["y"][i - 1]), b["ld"][i - 1]
                         sl.g, sl.ldg = P(b["g"][i]), b["g"][i].shape[1]
                     continue
-                if kinds[i] == 0:
+                if kinds[i] == LAYER_PLANES:
                     sl.qp = P(b["qp"][i].data)
                 else:
                     sl.ahnp, sl.ldp_ahn = P(b["ahnp"][i].data), b["ahnp"][i].ldp
@@ -804,14 +831,14 @@ class FusedGcnSageStep(TrainStep):
                 self._tail_ws = torch.empty(int(lib.gte_gemm_tail_workspace_bytes()), dtype=torch.uint8, device=self.flat_param.device)
             if self.tail_split:
                 plan.tail_ws, plan.tail_ws_bytes = P(self._tail_ws), self._tail_ws.numel()
-            cached = plans[("gen", with_adam)] = (plan, arr, ctypes.c_int(0))
+            cached = plans[with_adam] = (plan, arr, ctypes.c_int(0))
         plan, _arr, fused = cached
         # per call: switches and class weights (public attributes), the graph, the features
         plan.class_weights = P(self.class_weights)
         plan.fuse_ln_dx = (int(self.fuse_ln_dx) | (2 if self.fuse_ln_narrow else 0) | (8 if self.fuse_smallk_dx else 0)
                            | (4 if self.fuse_head_gemm else 0) | (16 if self.fuse_ln_fwd else 0))
         L0 = plan.layer[0]
-        if kinds[0] == 4:
+        if kinds[0] == LAYER_DROPOUT:
             # dropout: the input as fp32 rows or as the (resident) image; the masks of this seed / rank at the device step counter
             if xp is not None:
                 L0.xp, L0.ldp_x, L0.x, L0.ldx = P(xp.data), xp.ldp, None, 0
@@ -822,14 +849,14 @@ class FusedGcnSageStep(TrainStep):
             self._adam_state()
             plan.dropout_p, plan.dropout_seed, plan.rank = float(self.dropout_p), self.dropout_seed, self.rank
             plan.step_counter = P(self._step_dev)
-        elif kinds[0] == 3:
+        elif kinds[0] == LAYER_CACHED:
             ap = getattr(g, "agg_p3", None)
             if xp is None or ap is None:
                 raise _lib.GteError("a cached-aggregate input layer needs feat_p3 and agg_p3 (resident images behind a row map, or the graph's own)")
             L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
             L0.ahnp, L0.ldp_ahn = P(ap.data), ap.ldp
             L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
-        elif kinds[0] == 0:
+        elif kinds[0] == LAYER_PLANES:
             if xp is not None:
                 L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
                 L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
@@ -849,115 +876,9 @@ class FusedGcnSageStep(TrainStep):
         plan.rindptr, plan.rindices, plan.w_out = P(rcsr.indptr), P(rcsr.indices), P(w_out)
         plan.n_nodes = n
         C = layers[-1].out_feats
-        view = {"out3": b["out3"], "_full": b, "_wkey": ("gen", tuple(dims), tuple(kinds), bool(out_gemm)),
+        view = {"out3": b["out3"], "_wkey": self._plan_key(f0, kinds, out_gemm),
                 "logits": b["t_out"][:n, :C] if out_gemm else b["logits"][:n]}
         return plan, fused, view, n, (csr, rcsr, w_in, w_out, self.class_weights)
-
-    def _bind_plan(self, g, kinds, with_adam: bool):
-        """The gte_step_plan of this layer plan (cached with the buffer set whose addresses it holds) with the per-batch fields --
-        graph, features, node count -- set for ``g``.  Returns (plan, fused flag, row views of the buffers, node count, tensors
-        the plan points at)."""
-        lib, P = self.lib, _lib.ptr
-        xp = getattr(g, "feat_p3", None)
-        if xp is not None:
-            x, n, f0 = None, xp.rows, xp.cols
-        else:
-            x = ops._row_major(g.ndata['feat'])
-            _lib.require_device(x, "FusedGcnSageStep")
-            n, f0 = x.shape
-        gen, out_gemm = self._plan_mode(kinds, f0)
-        if gen:
-            return self._bind_plan_gen(g, kinds, with_adam, out_gemm)
-        b = self._buffers(n, f0, self._private_key)
-        layers = list(self.model.layers)
-        dims = [f0] + [l.out_feats for l in layers]
-        ew = g.edata.get("feat")
-        csr, rcsr = g.in_csr(), g.out_csr()
-        w_in, w_out = g.in_weights(ew), g.out_weights(ew, True)
-        plans = b["_full"].setdefault("_plans", {})       # cached with the buffer set whose addresses they hold
-        key = (tuple(kinds), with_adam)
-        cached = plans.get(key)
-        if cached is None:
-            self._weight_images(dims, launch=False)
-            descs = self._wimg_descs
-            if len(descs) > 16:
-                raise _lib.GteError("gte_gcnsage_step: more than 16 weight images")
-            arr = (_lib.P3Desc * max(len(descs), 1))(*descs)
-            plan = _lib.StepPlan()
-            plan.n_hidden = len(layers) - 1
-            for i, L in enumerate(layers[:-1]):
-                sl = plan.layer[i]
-                fin, fout = dims[i], L.out_feats
-                sl.kind, sl.fin, sl.fout = kinds[i], fin, fout
-                sl.W, sl.bias, sl.gamma, sl.beta = P(L.linear.weight), P(L.linear.bias), P(L.lynorm.weight), P(L.lynorm.bias)
-                sl.eps, sl.relu = float(L.lynorm.eps), int(L.activation is not None)
-                gs = self._gslice
-                sl.gW, sl.gbias = P(gs[id(L.linear.weight)]), P(gs[id(L.linear.bias)])
-                sl.ggamma, sl.gbeta = P(gs[id(L.lynorm.weight)]), P(gs[id(L.lynorm.bias)])
-                nxt_planes = i + 1 < len(layers) - 1 and kinds[i + 1] == 0
-                if kinds[i] == 0:
-                    wf, wb = self._wimg[i]
-                    sl.wimg_fwd, sl.ldp_wfwd = P(wf.data), wf.ldp
-                    if wb is not None:
-                        sl.wimg_bwd, sl.ldp_wbwd = P(wb.data), wb.ldp
-                    sl.hp, sl.ldp_h = P(b["hp"][i].data), b["hp"][i].ldp
-                    sl.t = P(b["t"][i])
-                    sl.dzp, sl.qp, sl.ldp_o = P(b["dzp"][i].data), P(b["qp"][i].data), b["dzp"][i].ldp
-                    sl.ws_dw, sl.ws_dw_bytes = P(b["ws_p3"][i]), b["ws_p3"][i].numel()
-                    sl.y = None if nxt_planes else P(b["y"][i])
-                else:
-                    sl.ahn, sl.t = P(b["ahn"][i]), P(b["z"][i])
-                    sl.y = None if (nxt_planes and fout % 16 == 0) else P(b["y"][i])
-                    sl.ws_dw, sl.ws_dw_bytes = P(b["ws_dw"][i]), b["ws_dw"][i].numel()
-                if nxt_planes:
-                    sl.yp, sl.ldp_y = P(b["hp"][i + 1].data), b["hp"][i + 1].ldp
-                sl.stats, sl.dy = P(b["stats"][i]), P(b["dy"][i])
-                sl.ws_ln, sl.ws_ln_bytes = P(b["ws_ln"][i]), b["ws_ln"][i].numel()
-            Lo = layers[-1]
-            plan.out_fin, plan.n_classes = dims[-2], Lo.out_feats
-            plan.W_out, plan.b_out = P(Lo.linear.weight), P(Lo.linear.bias)
-            plan.gW_out, plan.gb_out = P(self._gslice[id(Lo.linear.weight)]), P(self._gslice[id(Lo.linear.bias)])
-            plan.h_out, plan.ld_h_out = P(b["y"][-2]), dims[-2]
-            plan.logits, plan.tn, plan.q_out = P(b["y"][-1]), P(b["tn"]), P(b["q"])
-            plan.dl, plan.dh_out = P(b["dy"][-1]), P(b["dy"][-2])
-            plan.ce_part, plan.ce_part_bytes = P(b["ce_part"]), b["ce_part"].numel()
-            plan.ws_nar, plan.ws_nar_bytes = P(b["ws_nar"]), b["ws_nar"].numel()
-            plan.out3 = P(b["out3"])
-            plan.wimg_descs, plan.n_wimg_descs = ctypes.addressof(arr), len(descs)
-            if with_adam:
-                plan.param, plan.grad, plan.exp_avg, plan.exp_avg_sq = (P(self.flat_param), P(self.flat_grad), P(self.exp_avg),
-                                                                        P(self.exp_avg_sq))
-                plan.n_param = self.flat_param.numel()
-                plan.hyper, plan.step_counter, plan.ticket = P(self._hyper), P(self._step_dev), P(self._ticket)
-            if self._tail_ws is None:
-                self._tail_ws = torch.empty(int(lib.gte_gemm_tail_workspace_bytes()), dtype=torch.uint8, device=self.flat_param.device)
-            if self.tail_split:
-                plan.tail_ws, plan.tail_ws_bytes = P(self._tail_ws), self._tail_ws.numel()
-            cached = plans[key] = (plan, arr, ctypes.c_int(0))
-        plan, _arr, fused = cached
-        # per call: the public switches and the class weights (re-read like the call-by-call path does) ...
-        plan.class_weights = P(self.class_weights)
-        plan.fuse_ln_dx = (int(self.fuse_ln_dx) | (2 if self.fuse_ln_narrow else 0)
-                           | (8 if self.fuse_smallk_dx else 0))
-        # ... and per batch: the graph, the features, the labels
-        b["logits"], b["_wkey"] = b["y"][-1], "tuned"
-        L0 = plan.layer[0]
-        if kinds[0] == 0:
-            if xp is not None:
-                L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
-                L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
-            else:
-                L0.hp, L0.ldp_h, L0.make_hp = P(b["hp"][0].data), b["hp"][0].ldp, 1
-                L0.h_rows, L0.n_res_rows = None, 0
-                L0.x, L0.ldx = P(x), ops._ld(x)
-        else:
-            if x is None:
-                raise _lib.GteError("the batch holds its features as a P3 image, but layer 0 reads fp32 rows")
-            L0.x, L0.ldx = P(x), ops._ld(x)
-        plan.indptr, plan.indices, plan.w_in = P(csr.indptr), P(csr.indices), P(w_in)
-        plan.rindptr, plan.rindices, plan.w_out = P(rcsr.indptr), P(rcsr.indices), P(w_out)
-        plan.n_nodes = n
-        return plan, fused, b, n, (csr, rcsr, w_in, w_out, self.class_weights)
 
     def _c_step(self, g, labels, grad_scale, kinds, with_adam: bool):
         """forward + loss + backward (+ Adam inside the fold launch) through gte_gcnsage_step: two host calls (the next batch's
@@ -1024,7 +945,7 @@ class FusedGcnSageStep(TrainStep):
         xp = getattr(g, "feat_p3", None)
         n, f0 = (xp.rows, xp.cols) if xp is not None else g.ndata['feat'].shape
         kinds = self._plan_kinds(f0, n, self._batch_cached(g), train=False) if n > 0 else None
-        if kinds is not None and xp is None and kinds[0] == 0 and n * f0 > self.FORWARD_IMAGE_MAX_ELEMS:
+        if kinds is not None and xp is None and kinds[0] == LAYER_PLANES and n * f0 > self.FORWARD_IMAGE_MAX_ELEMS:
             # fp32 features under a planes input layer: the one-call plan would first write their P3 image (65 us at 21.5 k x 831)
             # -- more than the call saves on a graph of this size; the module path multiplies the fp32 rows directly
             # (profiles/debug/val_forward_time.py: 0.241 against 0.275 ms at 21.5 k nodes, 1.24 against 1.43 ms at 124 k)
@@ -1097,7 +1018,7 @@ class FusedGcnSageStep(TrainStep):
             x = ops._row_major(g.ndata['feat'])
             _lib.require_device(x, "FusedGcnSageStep")
             n, f0 = x.shape
-        b = self._buffers(n, f0, self._private_key)
+        b = self._buffers(n, f0)
         b["xp"] = xp
         # (kept with the buffer set, not with this call's row views: backward_rest() of the data-parallel overlap reads what the
         # forward of forward_backward() left)
@@ -1591,8 +1512,7 @@ class FusedGcnSageStep(TrainStep):
         keys = list(self._graphs) if g is None else [id(g)]
         for k in keys:
             self._graphs.pop(k, None)
-            self._graph_bufs.pop(k, None)
-            for kk in [q for q in self._graph_bufs if isinstance(q, tuple) and q[0] == k]:     # (general plans: (batch, layout) keys)
+            for kk in [q for q in self._graph_bufs if q[0] == k]:          # (captured batch, buffer-set key)
                 self._graph_bufs.pop(kk, None)
             self._graph_owner.pop(k, None)
 

@@ -11,10 +11,10 @@ sign of the fma (the product of two fp32 values is exact in float64; rounding ke
 masks has no branch left to disagree on: every remaining difference is device rounding, so every case is checked tightly.
 
 Where ``z`` lives (``device_relu_masks``):
-  * one-call plan on the padded buffer set (engine._alloc_gen): ``t[i]``, columns [0, fout) -- a planes layer's [z | t_neigh]
-    (z accumulated into the left half), or the aggregate-first / cached input layer's z;
-  * the tuned one-call plan and the call-by-call schedule (engine._alloc): ``t[i]`` (left half) where the layer has one
-    (transform-first or planes layer), else ``z[i]``;
+  * one-call plan (engine._alloc_plan, found through engine.plan_buffers): ``t[i]``, columns [0, fout) -- a planes layer's
+    [z | t_neigh] (z accumulated into the left half), or the aggregate-first / cached input layer's z;
+  * the call-by-call schedule (engine._alloc): ``t[i]`` (left half) where the layer has one (transform-first or planes layer),
+    else ``z[i]``;
   * the one-pass short-input layer (BBOX features, gte_sage_smallk_bwd / gte_gemm_p3_nt_smallk_bwd) does NOT save z: its
     backward recomputes z with the forward kernel's instruction sequence (csrc/smallk_step.h: bit-identical z) and reads the
     forward's stats.  The forward wrote y = fmaxf(fmaf(xh, gamma, beta), 0) from that same z, so there the mask is ``y > 0``
@@ -43,22 +43,21 @@ def host_relu_mask(z, mean, rstd, gamma, beta) -> np.ndarray:
 
 
 def _layer_buffers(engine, batch):
-    """(buffer set, general plan?, plan kinds or None, out_gemm) of the step the engine just ran on ``batch``."""
+    """(buffer set, plan kinds or None for the call-by-call schedule, out_gemm) of the step the engine just ran on ``batch``."""
     xp = getattr(batch, "feat_p3", None)
     n, f0 = (xp.rows, xp.cols) if xp is not None else tuple(batch.ndata["feat"].shape)
-    kinds = engine._plan_kinds(f0, n, engine._batch_cached(batch))
-    if kinds is not None:
-        gen, out_gemm = engine._plan_mode(kinds, f0)
-        if gen:
-            return engine._bufs[("gen", f0, tuple(kinds), bool(out_gemm))], True, kinds, out_gemm, n, f0
-    return engine._bufs[(f0, engine._planes_on())], False, kinds, False, n, f0
+    on_plan = engine.plan_buffers(batch)
+    if on_plan is not None:
+        return on_plan + (n, f0)
+    return engine._bufs[(f0, engine._planes_on())], None, False, n, f0
 
 
 def device_relu_masks(engine, batch, state) -> list:
     """Per hidden layer: the ReLU mask (bool [n, fout]) the device's backward used in the step just run on ``batch`` (see the
     module docstring for where each path keeps z).  ``state``: the parameters BEFORE the step (name -> tensor)."""
     from gnn_tableextraction_amd import ops
-    b, gen, kinds, out_gemm, n, f0 = _layer_buffers(engine, batch)
+    from gnn_tableextraction_amd._lib import LAYER_PLANES, LAYER_SMALLK
+    b, kinds, out_gemm, n, f0 = _layer_buffers(engine, batch)
     lib = engine.lib
     layers = list(engine.model.layers)
     dims = [f0] + [l.out_feats for l in layers]
@@ -69,13 +68,13 @@ def device_relu_masks(engine, batch, state) -> list:
         assert L.activation is not None and isinstance(L.lynorm, torch.nn.LayerNorm), "hidden layers: LayerNorm + ReLU"
         st = b["stats"][i][:2 * n].cpu().numpy()
         if kinds is not None:
-            smallk = kinds[i] == 1 and bool(lib.gte_sage_smallk_bwd_supported(2 * fin, fout))
+            smallk = kinds[i] == LAYER_SMALLK and bool(lib.gte_sage_smallk_bwd_supported(2 * fin, fout))
         else:
             smallk = (b["t"][i] is None and bool(lib.gte_sage_linear_fwd_fuses_ln(2 * fin, fout)) and engine._smallk_bwd(i, L, fin))
         if smallk:
             # z is recomputed in the backward, bit-identical to the forward's: the forward's y carries the decision
-            if gen:
-                img = (b["hp_out"] if i == nh - 1 else b["hp"][i + 1]) if ((i < nh - 1 and kinds[i + 1] == 0) or (i == nh - 1 and out_gemm)) else None
+            if kinds is not None:
+                img = (b["hp_out"] if i == nh - 1 else b["hp"][i + 1]) if ((i < nh - 1 and kinds[i + 1] == LAYER_PLANES) or (i == nh - 1 and out_gemm)) else None
             else:
                 img = b["hp"][i + 1] if (b["pl"][i + 1] and fout % 16 == 0) else None
             y = (ops.p3_to_f32(img.view_rows(n)) if img is not None else b["y"][i][:n])[:, :fout].cpu().numpy()

@@ -35,6 +35,14 @@ def test_library_exports_every_declared_symbol():
     assert lib.gte_weighted_ce_workspace_bytes(1000) >= 4 * 3 * 4
 
 
+def test_layer_kind_names_mirror_the_header_enum():
+    text = open(os.path.join(ROOT, "include", "gte.h")).read()
+    enum = dict(re.findall(r"GTE_(LAYER_[A-Z]+) = (\d+)", re.search(r"enum gte_layer_kind \{(.*?)\}", text).group(1)))
+    assert len(enum) == 5
+    for name, value in enum.items():
+        assert getattr(_lib, name) == int(value)
+
+
 def test_which_products_take_the_block_major_weights_kernel():
     """gte_gemm_p3_nt_plan (host logic only, run here without a GPU): the dispatch rule of the NT planes GEMMs.  The headline step's
     layer-0 forward ([x | cached ahn] W^T, K = 2 x 831, LayerNorm epilogue) and dX + LayerNorm backward (K = 2 x 256) take the

@@ -250,12 +250,9 @@ def test_dropout_step_on_probe_pages_through_the_train_loop(f0, hid, m, p, mode,
 
 
 # ----------------------------------------------------------------------------------------------- captured graph, eval
-def _layer0_self_image(eng, f0, n, private_key=None):
-    kinds = eng._plan_kinds(f0, n)
-    gen, out_gemm = eng._plan_mode(kinds, f0)
-    key = ("gen", f0, tuple(kinds), bool(out_gemm))
-    b = eng._graph_bufs[(private_key, key)] if private_key is not None else eng._bufs[key]
-    return ops.p3_to_f32(b["hp"][0].view_rows(n)).cpu().numpy()
+def _layer0_self_image(eng, g, private_key=None):
+    b = eng.plan_buffers(g, private_key)[0]
+    return ops.p3_to_f32(b["hp"][0].view_rows(g.ndata["feat"].shape[0])).cpu().numpy()
 
 
 def test_captured_replays_draw_fresh_masks_and_equal_the_eager_step():
@@ -285,7 +282,7 @@ def test_captured_replays_draw_fresh_masks_and_equal_the_eager_step():
         replay()
         torch.cuda.synchronize()
         assert int(a._step_dev.item()) == c + 1
-        got.append(_layer0_self_image(a, f0, n, id(ga)))
+        got.append(_layer0_self_image(a, ga, id(ga)))
         if c == 0:
             params_after_1 = {k: v.detach().cpu().clone() for k, v in ma.state_dict().items()}
     np.testing.assert_array_equal(got[0], want[0])
@@ -293,9 +290,10 @@ def test_captured_replays_draw_fresh_masks_and_equal_the_eager_step():
     assert not np.array_equal(got[0], got[1])
     # the eager step at counter 0 computes what the first replay computed, bit for bit
     mb, b = engine()
-    b.step(_graph(src, dst, w, x), torch.from_numpy(y).to(DEV))
+    gb = _graph(src, dst, w, x)
+    b.step(gb, torch.from_numpy(y).to(DEV))
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(_layer0_self_image(b, f0, n), want[0])
+    np.testing.assert_array_equal(_layer0_self_image(b, gb), want[0])
     for k, v in mb.state_dict().items():
         assert torch.equal(v.detach().cpu(), params_after_1[k]), k
     a.release()

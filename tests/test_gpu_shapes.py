@@ -213,7 +213,8 @@ def test_run_shape_step_matches_reference_golden(name, both_gemm_modes):
     np.testing.assert_allclose(logits, z["logits"], rtol=1e-5, atol=1e-5)
     out3 = fused.step(g, dev(y).float())
     if on_plan:
-        assert any(k[0] == "gen" for k in fused._bufs), "the step ran on the general plan's buffer set"
+        ran = fused.plan_buffers(g)
+        assert ran is not None and ran[0].get("_plans") and (ran[1], ran[2]) == (kinds, out_gemm), "the step ran on the one-call plan"
     grads = {k: fused._gslice[id(p)].cpu().numpy() for k, p in model.named_parameters()}
     params = {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
     after = fused.forward_logits(g).cpu().numpy()

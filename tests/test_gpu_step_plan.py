@@ -6,7 +6,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _run(monkeypatch, c_step, f0, hid, weighted, n_pages=12, steps=3, resident=False):
+def _ran_on_plan(tr, g, private_key=None):
+    """The one-call plan's buffer set when a plan of the engine was bound for ``g`` (a step or a forward-only call), else None."""
+    on = tr.plan_buffers(g, private_key)
+    return on[0] if on is not None and on[0].get("_plans") else None
+
+
+def _run(monkeypatch, c_step, f0, hid, weighted, n_pages=12, steps=3, resident=False, layers=3, per_step=6, fixed=False, captured=False,
+         must_plan=False):
+    """``fixed``: the same batch, built once, every step; ``captured``: that batch captured once and replayed; ``must_plan``: a
+    one-call step that did not run on a plan fails the test instead of skipping it."""
     import gnn_tableextraction_amd as gte
     from gnn_tableextraction_amd import graph as G
     from gnn_tableextraction_amd.data import synthetic as S
@@ -15,7 +24,7 @@ def _run(monkeypatch, c_step, f0, hid, weighted, n_pages=12, steps=3, resident=F
     dev = "cuda:0"
     pages = S.make_pages(n_pages, in_feats=f0)
     torch.manual_seed(7)
-    model = gte.GcnSAGE(f0, hid, 9, 3, torch.nn.functional.relu, 0).to(dev)
+    model = gte.GcnSAGE(f0, hid, 9, layers, torch.nn.functional.relu, 0).to(dev)
     cw = torch.linspace(0.5, 2.0, 9, device=dev) if weighted else None
     tr = FusedGcnSageStep(model, lr=0.01, weight_decay=5e-4, class_weights=cw)
     assert tr.use_c_step == c_step
@@ -32,9 +41,13 @@ def _run(monkeypatch, c_step, f0, hid, weighted, n_pages=12, steps=3, resident=F
         res = G.ResidentPages(graphs, dev)
         if tr.wants_p3_features(f0):
             res.enable_p3()
+    fixed = fixed or captured
+    replay, g = None, None
     for s in range(steps):
-        ids = [(3 * s + j) % n_pages for j in range(6)]
-        if resident:
+        ids = list(range(per_step)) if fixed else [(3 * s + j) % n_pages for j in range(per_step)]
+        if fixed and g is not None:
+            pass                                                 # (the one batch of this run)
+        elif resident:
             g = res.batch(ids)
             y = g.ndata["label"]
         else:
@@ -42,12 +55,24 @@ def _run(monkeypatch, c_step, f0, hid, weighted, n_pages=12, steps=3, resident=F
             g = G.PageGraph(src, dst, int(off[-1]), device=dev)
             g.ndata["feat"], g.edata["feat"] = torch.from_numpy(feat).to(dev), torch.from_numpy(w).to(dev)
             y = torch.from_numpy(label).to(dev)
-        outs.append(tr.step(g, y).cpu().numpy().copy())
-    used = any(k for full in tr._bufs.values() for k in full.get("_plans", {}))
-    if c_step and not used:
+        if captured:
+            # the one batch (device tensors kept alive here), captured once and replayed: its private buffer set, Adam in the graph
+            if replay is None:
+                replay = tr.capture(g, y)
+            outs.append(replay().cpu().numpy().copy())
+        else:
+            outs.append(tr.step(g, y).cpu().numpy().copy())
+    used = _ran_on_plan(tr, g, id(g) if captured else None) is not None
+    if must_plan:
+        assert used, "no one-call plan ran (plan_buffers found no bound plan for the batch)"
+    elif c_step and not used:
         pytest.skip("the engine's switches rule the one-call step out for this configuration")
-    return (np.stack(outs), tr.flat_param.detach().cpu().numpy(), tr.flat_grad.detach().cpu().numpy(),
-            tr.exp_avg_sq.detach().cpu().numpy(), used, res.p3_mode if resident else None)
+    kinds = tr._plan_kinds(f0, g.num_nodes(), tr._batch_cached(g))
+    mode = tr._plan_mode(kinds, f0) if kinds is not None else None
+    out = (np.stack(outs), tr.flat_param.detach().cpu().numpy(), tr.flat_grad.detach().cpu().numpy(),
+           tr.exp_avg_sq.detach().cpu().numpy(), used, res.p3_mode if resident else None, mode)
+    tr.release()
+    return out
 
 
 @pytest.mark.parametrize("f0,hid,weighted,resident", [(831, 256, False, False), (831, 256, True, True), (13, 256, False, False),
@@ -59,6 +84,38 @@ def test_one_call_step_is_bitwise_the_call_by_call_step(monkeypatch, f0, hid, we
     a = _run(monkeypatch, True, f0, hid, weighted, resident=resident)
     b = _run(monkeypatch, False, f0, hid, weighted, resident=resident)
     assert a[4] and not b[4]                                     # the one-call path really ran / really did not
+    for x, y in zip(a[:4], b[:4]):
+        np.testing.assert_array_equal(x, y)
+    assert np.isfinite(a[0]).all()
+
+
+@pytest.mark.parametrize("f0,hid,layers", [(13, 128, 2), (13, 128, 4), (144, 128, 2), (144, 128, 4)])
+def test_one_call_step_is_bitwise_the_call_by_call_step_on_small_aligned_plans(monkeypatch, f0, hid, layers):
+    """The smallest plans on which a binder can mis-wire a layer, all in the 16-aligned range 128 .. 256 (no padded rows, narrow
+    output kernels: _plan_mode (False, False)), on a few pages of a few hundred nodes: (13, 2 layers) layer 0 is at once the input
+    layer, the one-pass short-input layer and the last hidden layer -- y as rows for the narrow kernels; (13, 4) the short-input
+    layer under two planes layers -- image chaining, layer 0's backward in layer 1's dX; (144, 2) a planes input layer that
+    makes its own input image and is the last hidden layer; (144, 4) an inner planes layer between two planes layers -- the
+    LayerNorm backward in the dX epilogue."""
+    kw = dict(n_pages=4, per_step=2, layers=layers)
+    a = _run(monkeypatch, True, f0, hid, True, must_plan=True, **kw)
+    b = _run(monkeypatch, False, f0, hid, True, **kw)
+    assert a[4] and not b[4]                                     # a plan ran (asserted in _run) / the call-by-call schedule ran
+    assert a[6] == (False, False)
+    for x, y in zip(a[:4], b[:4]):
+        np.testing.assert_array_equal(x, y)
+    assert np.isfinite(a[0]).all()
+
+
+def test_captured_replays_are_bitwise_the_eager_steps(monkeypatch):
+    """capture() of a (13, 128, 3 layers) batch -- its private exact-size buffer set, Adam inside the graph -- and three replays:
+    losses, gradients, parameters and optimiser state bit for bit those of three eager one-call steps on the same batch from the
+    same initial state."""
+    kw = dict(n_pages=4, per_step=2, layers=3)
+    a = _run(monkeypatch, True, 13, 128, True, captured=True, must_plan=True, **kw)
+    b = _run(monkeypatch, True, 13, 128, True, fixed=True, must_plan=True, **kw)
+    assert a[4] and b[4]                                         # a plan ran: on the private set / on the shared set
+    assert a[6] == (False, False) and b[6] == (False, False)
     for x, y in zip(a[:4], b[:4]):
         np.testing.assert_array_equal(x, y)
     assert np.isfinite(a[0]).all()
@@ -130,12 +187,12 @@ def test_forward_only_call_matches_the_module_forward_and_the_steps_forward(monk
     got = tr.forward_logits(g).clone()
     scale = float(want.abs().max())
     assert float((got - want).abs().max()) <= 2e-5 * max(scale, 1.0)
-    if not any(k for full in tr._bufs.values() for k in full.get("_plans", {})):
+    if _ran_on_plan(tr, g) is None:
         # (the module path answered, from the image's exact fp32 values for an image-mode batch)
         pytest.skip("the engine's switches rule the one-call plan out for this configuration")
     tr.step(g, y)
     n = want.shape[0]
-    step_logits = next(iter(tr._bufs.values()))["y"][-1][:n]
+    step_logits = _ran_on_plan(tr, g)["logits"][:n]
     torch.testing.assert_close(step_logits, got, rtol=0, atol=0)
     if resident:
         pipe = BatchPipeline(res)
@@ -155,8 +212,9 @@ def test_fold_launch_writes_the_weight_images_of_the_updated_parameters(monkeypa
     """gte_fold_defer_flush_adam_images: after a one-call step the weight images are, byte for byte, what the conversion launch
     makes of the updated parameters (so the next forward skips it); a parameter changed through torch is noticed (version
     counters) and the images are converted again; GTE_WIMG_IN_FOLD=0 gives the same bits."""
+    import ctypes
     import gnn_tableextraction_amd as gte
-    from gnn_tableextraction_amd import graph as G
+    from gnn_tableextraction_amd import graph as G, _lib
     from gnn_tableextraction_amd.data import synthetic as S
     from gnn_tableextraction_amd.models.engine import FusedGcnSageStep
     dev = "cuda:0"
@@ -175,17 +233,19 @@ def test_fold_launch_writes_the_weight_images_of_the_updated_parameters(monkeypa
             pytest.skip("the one-call step drives the planes path (default GEMM mode, GTE_PLANES=1)")
         for _ in range(3):
             tr.step(g, y)
-        if not any(k for full in tr._bufs.values() for k in full.get("_plans", {})):
+        if _ran_on_plan(tr, g) is None:
             pytest.skip("the engine's switches rule the one-call step out for this configuration")
         if not tr.fuse_adam:
             pytest.skip("GTE_FUSE_ADAM=0: the optimiser step is its own launch")
         if flag == "1":
             assert tr.adam_fused_steps == 3 and tr._wimg_sig is not None          # the fold launch wrote them
-            have = {i: (fw.data.clone(), None if bw is None else bw.data.clone()) for i, (fw, bw) in tr._wimg.items()}
-            assert have
-            dims = [f0] + [l.out_feats for l in model.layers]
-            tr._weight_images(dims, launch=True)                                    # the conversion launch on the same parameters
-            for i, (fw, bw) in tr._wimg.items():
+            # every forward and backward image of the plan that ran, against the conversion launch on the plan's own descriptors
+            _, kinds, out_gemm = tr.plan_buffers(g)
+            imgs, arr, n_desc = tr._weight_images_gen([f0] + [l.out_feats for l in model.layers], kinds, out_gemm)
+            have = {i: (fw.data.clone(), None if bw is None else bw.data.clone()) for i, (fw, bw) in imgs.items()}
+            assert have and 0 < n_desc <= 16
+            _lib.check(tr.lib.gte_p3_from_f32_batch(ctypes.addressof(arr), n_desc, _lib.current_stream()), "gte_p3_from_f32_batch")
+            for i, (fw, bw) in imgs.items():
                 assert torch.equal(have[i][0], fw.data)
                 if bw is not None:
                     assert torch.equal(have[i][1], bw.data)
