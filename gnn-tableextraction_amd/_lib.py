@@ -139,6 +139,7 @@ SIGNATURES = {
                                c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "gte_adam_ticket_bytes": (c_int64, []),
     "gte_gcnsage_step": (c_int, [c_void_p, c_int, POINTER(c_int), c_void_p]),
+    "gte_gcnsage_step_wide_layers": (c_int, [c_void_p]),
     "gte_gcnsage_forward": (c_int, [c_void_p, c_void_p]),
     "gte_fold_defer_begin": (c_int, [c_void_p]),
     "gte_fold_defer_flush": (c_int, []),
@@ -209,6 +210,8 @@ SIGNATURES = {
     "gte_adam_step_dev_images": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_int, c_void_p, c_void_p]),
     # dropout (csrc/dropout.hip)
+    "gte_dropout_set_wide": (c_int, [c_int]),
+    "gte_dropout_get_wide": (c_int, []),
     "gte_dropout_mask": (c_int, [c_float, c_uint64, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "gte_dropout_mask_host": (c_int, [c_float, c_uint64, c_int, c_int64, c_int, c_int64, c_int64, c_void_p, c_int64]),
     "gte_spmm_dropout_p3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,

@@ -235,7 +235,30 @@ DropArgs drop_args(float p, uint64_t seed, int rank, const int64_t* step_counter
 
 int grid_rows(int64_t n_rows) { return (int)gte::ceil_div(n_rows, 4); }      // one wave per row, four waves per block
 
+// Rows of a launch: row indices, the grid-stride sum r + waves (waves <= n_rows + 3) and the Philox row word are 32-bit, so
+// n_rows <= 2^30 keeps every one of them below 2^31.  Everything that is multiplied by a row stride is 64-bit per lane already
+// (the gathers reach arbitrary rows: no window to rebase), so no image or row buffer has a byte bound.
+int check_rows(int64_t n_rows, const char* what) {
+    if (n_rows > GTE_DROPOUT_MAX_ROWS)
+        return gte::fail(GTE_ERR_UNSUPPORTED, "%s: %lld rows; a dropout launch holds at most 2^30 rows (32-bit row indices)", what, (long long)n_rows);
+    return GTE_OK;
+}
+
+thread_local int g_wide_forced = 0;          // gte_dropout_set_wide
+thread_local int g_wide_scope = 0;           // open WideScope(true) objects of this thread
+
 }  // namespace
+
+bool gte::wide_forced() { return g_wide_forced != 0 || g_wide_scope > 0; }
+gte::WideScope::WideScope(bool on) : prev_(g_wide_scope) { if (on) ++g_wide_scope; }
+gte::WideScope::~WideScope() { g_wide_scope = prev_; }
+
+extern "C" int gte_dropout_set_wide(int mode) {
+    if (mode != 0 && mode != 1) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "dropout_set_wide: mode must be 0 (by size) or 1 (always)");
+    g_wide_forced = mode;
+    return GTE_OK;
+}
+extern "C" int gte_dropout_get_wide(void) { return g_wide_forced; }
 
 extern "C" int gte_dropout_mask(float p, uint64_t seed, int rank, int64_t step, int site, int64_t n_rows, int64_t n_cols, uint8_t* mask,
                                 int64_t ldm, void* stream) {
@@ -272,6 +295,7 @@ extern "C" int gte_spmm_dropout_p3(const int32_t* indptr, const int32_t* indices
     GTE_DROP_TRY(check_p(p, "spmm_dropout_p3"));
     if (n_rows < 0 || n_feat <= 0 || n_rows > INT32_MAX || n_feat > (1 << 24) || site < 1)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_p3: bad sizes or site");
+    GTE_DROP_TRY(check_rows(n_rows, "spmm_dropout_p3"));
     if (n_rows == 0) return GTE_OK;
     if (!indptr || !indices || !step_counter || !selfp3 || !aggp3 || (!x == !xp))
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_p3: null pointer (exactly one of x / xp is the input)");
@@ -301,6 +325,7 @@ extern "C" int gte_spmm_dropout_bwd(const int32_t* rindptr, const int32_t* rindi
     GTE_DROP_TRY(check_p(p, "spmm_dropout_bwd"));
     if (n_rows < 0 || n_feat <= 0 || n_rows > INT32_MAX || n_feat > (1 << 24) || site < 1)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_bwd: bad sizes or site");
+    GTE_DROP_TRY(check_rows(n_rows, "spmm_dropout_bwd"));
     if (n_rows == 0) return GTE_OK;
     if (!rindptr || !rindices || !w_out || !g || !step_counter || !dx) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_bwd: null pointer");
     const int64_t n4 = gte::round_up(n_feat, 4);

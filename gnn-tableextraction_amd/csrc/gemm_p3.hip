@@ -67,6 +67,9 @@ struct P3Gemm {
     // NT: BOTH K segments are resident images read through rowsA (A2 = the cached aggregated input next to the input itself,
     // gte_gemm_p3_nt_rows2); res_bytes2 = size of the second image
     int rows_both; long long res_bytes2;
+    // NT: the output is addressed through a window that starts at the first row of each wave's tile (64-bit base on the scalar
+    // unit, offsets inside the tile) instead of one window over all of C: outputs of 2 GB or more (store_tile)
+    int wide_c;
     // LayerNorm(+ReLU) backward as the epilogue of an NT product whose tile holds whole rows (N <= 256): the product is
     // dy = d(loss) / d(y of the layer below), never stored; the workgroup writes dz = LN'(z)(mask . dy) as fp32 and as a P3 image
     // and leaves the column partials {sum g xhat, sum g, sum dz} in ln_part[tile][3][N]  (gte_gemm_p3_nt_ln_bwd)
@@ -155,15 +158,20 @@ __device__ __forceinline__ void keep_frags(const Frags<TM, TN>& f) {
 
 // Store epilogue of a wave's TM x TN accumulator tiles through a buffer descriptor over the output: rows past M and columns
 // past `cols_valid` get an offset outside the window and are dropped by the range check (branch-free; sage_linear.hip).
+// wide == 0: ONE window over the whole output, 32-bit offsets from its first byte (outputs below 2 GB).  wide != 0: the window is
+// rebased to the wave's first row (row0 is wave-uniform: 64-bit base arithmetic on scalar registers) and covers the tile's rows
+// only, so the offsets stay below 32 TM ld 4 bytes whatever M is.  Same stores, same values, same order in both forms.
 // The stored value goes through a VGPR on purpose: with an accumulator element as the store's data operand hipcc 7.2 emitted
 // element 0 for all sixteen stores (gemm_bf16.hip).
 template <int TM, int TN>
 __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][TN], float* outp, long long ldo, int M, int cols_total,
                                            int row0, int col0, int cols_valid_end, const float* bias, int bias_cols, int relu,
-                                           int accumulate, int lane) {
+                                           int accumulate, int lane, int wide) {
     const int col_l = lane & 31, hrow = (lane >> 5) * 4;
-    const __amdgpu_buffer_rsrc_t c_srd =
-        __builtin_amdgcn_make_buffer_rsrc(outp, 0, (int)(((long long)(M - 1) * ldo + cols_total) * 4), SRD_FLAGS);
+    const int rb = wide ? row0 : 0;                                  // first row of the window
+    const int rows_w = wide ? min(M - rb, TM * 32) : M;              // rows it covers (<= 0: a tile past M, an empty window)
+    const __amdgpu_buffer_rsrc_t c_srd = __builtin_amdgcn_make_buffer_rsrc(
+        outp + (long long)rb * ldo, 0, rows_w > 0 ? (int)(((long long)(rows_w - 1) * ldo + cols_total) * 4) : 0, SRD_FLAGS);
     const int ld4 = (int)ldo * 4;
     const bool post = accumulate || relu;
 #pragma unroll
@@ -174,7 +182,7 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][TN], float* o
         const float bv = (bias && cok && (bias_cols <= 0 || col < bias_cols)) ? bias[col] : 0.f;
 #pragma unroll
         for (int a = 0; a < TM; ++a) {
-            const int roff0 = (row0 + a * 32 + hrow) * ld4 + coff;
+            const int roff0 = (row0 - rb + a * 32 + hrow) * ld4 + coff;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int off = roff0 + ((r & 3) + 8 * (r >> 2)) * ld4;
@@ -528,7 +536,7 @@ gemm_p3_nt_ring_kernel(const P3Gemm p) {
         smallk_bwd_epilogue<TM, TN, WM, WN, 160 * 1024>(acc, lds, p, m0, lb, wave, wm, wn, lane, tid);     // (launched with 160 KB of LDS)
     else
         store_tile<TM, TN>(acc, p.C, p.ldc, p.M, p.N, m0 + wm * TM * 32, n0 + wn * TN * 32, p.N, p.bias, p.bias_cols, p.relu,
-                           p.accumulate, lane);
+                           p.accumulate, lane, p.wide_c);
 }
 
 // (A variant of the ring kernel on v_mfma_f32_16x16x32_bf16 -- two plane products per instruction -- was measured in round 3 and
@@ -544,7 +552,7 @@ __device__ __forceinline__ void lw_epilogue(const f32x16 (&acc)[TM][TN], char* l
     const int wm = wave / WN, wn = wave % WN;
     if constexpr (LNB == 0) {
         store_tile<TM, TN>(acc, p.C, p.ldc, p.M, p.N, m0 + wm * TM * 32, n0 + wn * TN * 32, p.N, p.bias, p.bias_cols, p.relu,
-                           p.accumulate, lane);
+                           p.accumulate, lane, p.wide_c);
     } else if constexpr (LNB == 4) {
         // ---- LayerNorm(+ReLU) FORWARD of the tile's rows: z = product + bias goes to LDS row-major per slice of TM * 32 rows, then
         // every wave takes rows of the slice in the layout and with the arithmetic of ln_relu_fwd_gen_kernel<1, .> (lane l = columns
@@ -1444,7 +1452,7 @@ gemm_p3_tn_kernel(const P3Gemm p) {
     if (p.K == 12345)                                          // (measurement: no slab stores)
 #endif
     store_tile<TM, TN>(acc, outp, ldo, p.M, p.N, m0 + wm * TM * 32, cbase + n0 + wn * TN * 32, cbase + seg_cols, nullptr, 0,
-                       p.splits > 1 ? 0 : p.relu, p.splits > 1 ? 0 : p.accumulate, lane);
+                       p.splits > 1 ? 0 : p.relu, p.splits > 1 ? 0 : p.accumulate, lane, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1615,9 +1623,13 @@ static int gemm_p3_nt_impl(const void* a1, int64_t lda1, int64_t k1, const void*
     const P3Strides sb = p3_strides(ldb);
     if (lda1 < kb1 * 96 || (k2 > 0 && lda2 < kb2 * 96) || !p3_strides_ok(ldb, n, 16 * (kb1 + kb2)) || ldc < n)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt: leading dimension too small");
-    if (lda1 >= (1 << 22) || lda2 >= (1 << 22) || sb.ld >= (1 << 22) || (m + 256) * ldc * 4 >= ((int64_t)1 << 31))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt: row strides must be < 4 MB and the output < 2 GB");
+    // the output: one window over all of it while (m + 256) rows stay below 2 GB, else (or forced: gte_dropout_set_wide) a window
+    // per wave tile -- 256 rows of ldc floats must then fit 32-bit offsets with room to spare
+    const bool wide = gte::wide_forced() || (m + 256) * ldc * 4 >= ((int64_t)1 << 31);
+    if (lda1 >= (1 << 22) || lda2 >= (1 << 22) || sb.ld >= (1 << 22) || (wide && ldc >= (1 << 20)))
+        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt: row strides must be < 4 MB (the output's, when it holds 2 GB or more: < 4 MB too)");
     P3Gemm p = {};
+    p.wide_c = wide ? 1 : 0;
     p.A1 = (const char*)a1; p.lda1 = lda1; p.KB1 = (int)kb1;
     p.A2 = k2 > 0 ? (const char*)a2 : nullptr; p.lda2 = lda2; p.KB2 = (int)kb2;
     p.B = (const char*)b; p.ldb = sb.ld; p.C = c; p.ldc = ldc; p.bias = bias; p.bias_cols = (int)bias_cols;

@@ -44,6 +44,19 @@ TailWorkspace tail_workspace();
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Wide addressing (csrc/dropout.hip): true while this host thread's launches take their wide form whatever the sizes -- forced by
+// gte_dropout_set_wide(1), or inside a WideScope(true): gte_gcnsage_step opens one around the launches of a dropout layer whose
+// row buffers reach 2 GB.  Thread-local, as every forced configuration of the library.
+bool wide_forced();
+struct WideScope {
+    explicit WideScope(bool on);
+    ~WideScope();
+    WideScope(const WideScope&) = delete;
+    WideScope& operator=(const WideScope&) = delete;
+private:
+    int prev_;
+};
+
 // Measurement switches.  The shipped library reads ONE environment variable (GTE_GEMM_MODE, documented in include/gte.h); every
 // other switch -- forced tile / block counts, kernel paths turned off for A/B runs -- exists only in the measurement build
 // (-DGTE_MEASURE: libgte_hip_measure.so of the Makefile, which tests/test_gpu_variants.py and the scripts under profiles/ load

@@ -34,6 +34,18 @@ bool narrow_padded(const gte_step_plan& p) {
     return !p.out_gemm && p.out_fin % 8 != 0 && p.ld_h_out > p.out_fin && gte_sage_narrow_pad_supported(p.out_fin, p.ld_h_out, p.n_classes);
 }
 
+// A dropout layer runs its launches in their WIDE form (csrc/gemm_p3.hip store_tile: the output window rebased per wave tile)
+// when its fp32 row buffers can reach 2 GB: (n + 256) x 2 x max(ceil16(fout), ceil16(fin)) fp32 values (t / y / dy are ceil16(fout)
+// wide, G = dz W is 2 ceil16(fin)), the bound the 32-bit form was held to.  Below it the launches are the 32-bit ones, bit for bit.
+inline int64_t c16(int64_t v) { return (v + 15) / 16 * 16; }
+bool layer_wide(const gte_step_plan& p, int i) {
+    const gte_step_layer& L = p.layer[i];
+    if (L.kind != GTE_LAYER_DROPOUT) return false;
+    if (gte::wide_forced()) return true;
+    const int64_t ld = c16(L.fout) > c16(L.fin) ? c16(L.fout) : c16(L.fin);
+    return (p.n_nodes + 256) * 2 * ld * 4 >= ((int64_t)1 << 31);
+}
+
 // weight images + the hidden layers (the output layer's input is p.h_out / p.hp_out afterwards).  fwd_only: nothing is kept for a
 // backward -- a planes layer whose output is consumed as an image (by the next planes layer, or by the output layer's GEMM) does
 // not write its fp32 rows (a sixth of the aggregation + LayerNorm kernel's bytes)
@@ -57,6 +69,7 @@ int forward_hidden(const gte_step_plan& p, void* st, bool fwd_only = false) {
     for (int i = 0; i < p.n_hidden; ++i) {
         const gte_step_layer& L = p.layer[i];
         const int64_t ld = ldf(L);
+        const gte::WideScope wide(layer_wide(p, i));
         if (L.kind == GTE_LAYER_SMALLK) {
             GTE_TRY(gte_spmm_csr(p.indptr, p.indices, p.w_in, L.x, L.ldx, L.ahn, L.fin, n, L.fin, GTE_F32, GTE_REDUCE_MEAN, st));
             // (the one-pass backward recomputes z from the 2 fin inputs per row: nothing to save)
@@ -188,6 +201,7 @@ int backward_a(const gte_step_plan& p, void* st) {
     const int64_t n = p.n_nodes, C = p.n_classes, lg = ld_lg(p);
     bool ln_done = false, smallk_done = false;
     const gte_step_layer& T = p.layer[p.n_hidden - 1];
+    const gte::WideScope wide_out(layer_wide(p, p.n_hidden - 1));      // (the output layer's dh lands in the last hidden layer's dy)
     if (p.out_gemm) {
         // q = A_w^T (norm dl); dl and q as ONE image [n][32] (dl in block 0, q in block 1); dW_out = [dl^T h | q^T h] (two column
         // segments of one TN launch, M = n_classes), dbias = colsum(dl), dh = [dl | q] [W_s^T | W_n^T] (K = 32)
@@ -204,6 +218,7 @@ int backward_a(const gte_step_plan& p, void* st) {
         GTE_TRY(gte_gemm_p3_tn(p.dlqp, p.ldp_dlq, static_cast<const char*>(p.dlqp) + 96, p.ldp_dlq, p.hp_out, p.ldp_hout, nullptr, 0,
                                p.out_fin, p.gW_out, 2 * p.out_fin, C, 2 * p.out_fin, n, p.ws_out, p.ws_out_bytes, st));
         if ((p.fuse_ln_dx & 1) && T.kind != GTE_LAYER_SMALLK && gte_gemm_p3_nt_ln_bwd_supported(p.out_fin) && T.dy == p.dh_out &&
+            (n + 256) * p.ldp_dlq < ((int64_t)1 << 31) &&          // (that launch's own bound on its operand image: else the two launches)
             (p.out_fin % 16 == 0 || ldf(T) >= ((p.out_fin + 3) & ~(int64_t)3))) {
             // ... with the LayerNorm(+ReLU) backward of the last hidden layer as its epilogue (hidden widths up to 256)
             GTE_TRY(gte_gemm_p3_nt_ln_bwd(p.dlqp, p.ldp_dlq, 32, nullptr, 0, 0, p.wimg_out_bwd, p.ldp_wout_bwd, z_of(T), ldz_of(T), T.stats,
@@ -239,6 +254,7 @@ int backward_a(const gte_step_plan& p, void* st) {
     for (int i = p.n_hidden - 1; i >= 0; --i) {
         const gte_step_layer& L = p.layer[i];
         const int64_t ld = ldf(L);
+        const gte::WideScope wide(layer_wide(p, i));
         if (L.kind == GTE_LAYER_SMALLK) {
             if (smallk_done) continue;
             if (!gte_sage_smallk_bwd_supported(2 * L.fin, L.fout))
@@ -290,6 +306,7 @@ int backward_a(const gte_step_plan& p, void* st) {
 int backward_b(const gte_step_plan& p, void* st) {
     const int64_t n = p.n_nodes;
     const gte_step_layer& L = p.layer[0];
+    const gte::WideScope wide(layer_wide(p, 0));
     if (smallk_in_dx(p)) {                             // layer 1's dX with layer 0's whole backward as its epilogue
         const gte_step_layer& U = p.layer[1];
         return gte_gemm_p3_nt_smallk_bwd(U.dzp, U.ldp_o, U.fout, U.qp, U.ldp_o, U.fout, U.wimg_bwd, U.ldp_wbwd, L.x, L.ldx, L.fin, L.ahn,
@@ -363,10 +380,23 @@ int check_plan(const gte_step_plan& p) {
                        p.q_out != p.dl + 16))
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: the GEMM output layer needs n_classes <= 16, [n][32] logits / dl buffers and its images");
     if (p.n_nodes == 0) return gte::fail(GTE_ERR_UNSUPPORTED, "gcnsage_step: empty batch");
+    if (p.dropout_p != 0.f && p.n_nodes > GTE_DROPOUT_MAX_ROWS)
+        return gte::fail(GTE_ERR_UNSUPPORTED, "gcnsage_step: %lld nodes; a dropout plan holds at most 2^30 rows (32-bit row indices and "
+                                              "mask row words; no byte bound on its buffers)", (long long)p.n_nodes);
     return GTE_OK;
 }
 
 }  // namespace
+
+extern "C" int gte_gcnsage_step_wide_layers(const gte_step_plan* plan) {
+    if (!plan) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step_wide_layers: null plan");
+    const gte_step_plan& p = *plan;
+    if (p.n_hidden < 1 || p.n_hidden > 7 || p.n_nodes < 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step_wide_layers: bad plan");
+    int mask = 0;
+    for (int i = 0; i < p.n_hidden; ++i)
+        if (layer_wide(p, i)) mask |= 1 << i;
+    return mask;
+}
 
 extern "C" int gte_gcnsage_step(const gte_step_plan* plan, int phase, int* adam_fused, void* stream) {
     if (!plan) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gcnsage_step: null plan");

@@ -107,6 +107,9 @@ from ..components.graphs.models import GcnSAGE, _is_relu               # noqa: E
 import torch.nn as nn                                                  # noqa: E402
 
 
+DROPOUT_MAX_ROWS = 1 << 30          # GTE_DROPOUT_MAX_ROWS of include/gte.h: nodes of a dropout plan
+
+
 def _c16(x: int) -> int:
     return -(-int(x) // 16) * 16
 
@@ -486,11 +489,11 @@ class FusedGcnSageStep(TrainStep):
                 and bool(self.lib.gte_spmm_csr_accumulate_ln_supported(fout))
                 and not (n and ops.use_tiled(n, fout, None, fused_ln=True)))
 
-    def wants_p3_features(self, f0: int) -> bool:
+    def wants_p3_features(self, f0: int, train: bool = True) -> bool:
         """True when layer 0 takes its input as a P3 image: the train loop then keeps the resident features as images and
         assembles batches of image rows (graph.ResidentPages.enable_p3)."""
         L = self.model.layers[0]
-        return self._layer_kind(0, L, f0) == LAYER_PLANES
+        return self._layer_kind(0, L, f0, train=train) == LAYER_PLANES
 
     def _param_sig(self):
         return (self.flat_param._version,) + tuple(p._version for p in self.model.parameters())
@@ -553,23 +556,23 @@ class FusedGcnSageStep(TrainStep):
                 and L.linear.bias is not None and (L.activation is None or _is_relu(L.activation))
                 and 128 <= L.out_feats <= 1024)
 
-    def wants_agg_image(self, f0: int) -> bool:
-        """True when the train loop should keep the image of the input's mean aggregate next to the feature image
-        (graph.ResidentPages.enable_p3(agg=True))."""
+    def wants_agg_image(self, f0: int, train: bool = True) -> bool:
+        """True when the train loop (``train`` False: an evaluation loop, which applies no dropout) should keep the image of the
+        input's mean aggregate next to the feature image (graph.ResidentPages.enable_p3(agg=True))."""
         L = self.model.layers[0]
-        if self.dropout_p > 0:
+        if train and self.dropout_p > 0:
             return False                  # (layer 0 aggregates the DROPPED input: a cached aggregate of x is of no use)
         return (len(self.model.layers) >= 2 and self._cached_layer0(L, f0)
-                and self._layer_kind(0, L, f0) in (LAYER_PLANES, LAYER_AGGFIRST))
+                and self._layer_kind(0, L, f0, train=train) in (LAYER_PLANES, LAYER_AGGFIRST))
 
-    def wants_resident_images(self, f0: int) -> bool:
+    def wants_resident_images(self, f0: int, train: bool = True) -> bool:
         """True when the train loop should keep the resident features as images (and hand out row-map batches): layer 0 takes its
         input as an image (wants_p3_features), or it is a widening aggregate-first layer that can run on the cached aggregate --
         63 / 313 / 363 -> 1000, 63 -> 206 of the reference's runs: without the cache such a layer copies its fp32 rows per batch and
         makes both images per step."""
-        if self.dropout_p > 0:            # a dropout layer 0 reads the resident feature image through the batch's row map
+        if train and self.dropout_p > 0:  # a dropout layer 0 reads the resident feature image through the batch's row map
             return self._layer_kind(0, self.model.layers[0], f0) == LAYER_DROPOUT
-        return self.wants_p3_features(f0) or self.wants_agg_image(f0)
+        return self.wants_p3_features(f0, train) or self.wants_agg_image(f0, train)
 
     def _layer_kind(self, i: int, L, fin: int, n: int = 0, cached: bool = False, train: bool = True):
         """How hidden layer i runs on the one-call plan (gte_step_layer.kind): 0 planes layer in transform-first order, 1 the
@@ -622,13 +625,30 @@ class FusedGcnSageStep(TrainStep):
             k = self._layer_kind(i, L, dims[i], n, cached, train)
             if k is None:
                 return None
-            # (the planes GEMMs address their output through 32-bit buffer offsets: [n][2 ld] fp32 must stay below 2 GB; a dropout
-            # layer's G is [n][2 ceil16(fin)])
-            ld_max = max(_c16(L.out_feats), _c16(dims[i]) if k == LAYER_DROPOUT else 0)
-            if k != LAYER_SMALLK and (n + 256) * 2 * ld_max * 4 >= (1 << 31):
+            # (the p = 0 planes layers address their output through 32-bit buffer offsets: [n][2 ld] fp32 must stay below 2 GB.  A
+            # dropout layer has no byte bound -- past this size gte_gcnsage_step runs its launches in their wide form, wide_layers()
+            # -- only a row bound, DROPOUT_MAX_ROWS, which forward_backward reports)
+            if k not in (LAYER_SMALLK, LAYER_DROPOUT) and (n + 256) * 2 * _c16(L.out_feats) * 4 >= (1 << 31):
                 return None
             kinds.append(k)
+        if drop and n > DROPOUT_MAX_ROWS:
+            return None
         return kinds
+
+    def wide_layers(self, g) -> int:
+        """Bit mask of the hidden layers a training step on ``g`` runs in the wide addressing form (gte_gcnsage_step_wide_layers on
+        the step's own plan: a dropout layer whose row buffers reach 2 GB, or every dropout layer under gte_dropout_set_wide(1) on
+        this thread); 0 for a model without dropout or a step that is not on a plan."""
+        xp = getattr(g, "feat_p3", None)
+        n, f0 = (xp.rows, xp.cols) if xp is not None else g.ndata['feat'].shape
+        kinds = self._plan_kinds(f0, n, self._batch_cached(g))
+        if kinds is None or self.dropout_p == 0:
+            return 0
+        plan = self._bind_plan(g, kinds, with_adam=bool(self._fuse_adam_req))[0]
+        rc = int(self.lib.gte_gcnsage_step_wide_layers(ctypes.addressof(plan)))
+        if rc < 0:
+            _lib.check(rc, "gte_gcnsage_step_wide_layers")
+        return rc
 
     def attach_feature_image(self, g) -> bool:
         """Give a graph that is evaluated again and again (the validation graph of train(): the same graph every epoch,
@@ -989,9 +1009,8 @@ class FusedGcnSageStep(TrainStep):
         if self.dropout_p > 0:
             raise RuntimeError(f"FusedGcnSageStep: dropout {self.dropout_p} runs on the one-call plan only (gte_gcnsage_step with "
                                "GTE_LAYER_DROPOUT layers); this step would take the call-by-call schedule, which applies no masks: "
-                               "a switch changed after construction (use_c_step, op timers) or a batch past the plan's size limit "
-                               "((nodes + 256) x 2 x max(ceil16(hidden), ceil16(fin)) fp32 values must stay below 2 GB). "
-                               "Use TrainStep for it.")
+                               f"a switch changed after construction (use_c_step, op timers) or a batch of more than {DROPOUT_MAX_ROWS} "
+                               "nodes (2^30: 32-bit row indices; the plan has no byte bound). Use TrainStep for it.")
 
     def backward_rest(self, g, from_layer: int) -> None:
         """Backward of layers from_layer-1 .. 0 after ``forward_backward(..., upto_layer=from_layer)`` on the same batch."""

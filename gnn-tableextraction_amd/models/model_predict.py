@@ -130,10 +130,11 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None) -> torch.Ten
     ids = np.arange(len(res.page_sizes()), dtype=np.int64) if page_ids is None else np.asarray(page_ids, dtype=np.int64)
     steps = [ids[i:i + batch_pages] for i in range(0, ids.size, batch_pages)]
     f0 = res.feat.shape[1]
-    want_p3 = bool(engine.wants_resident_images(f0))
+    # (train=False: the evaluation forward applies no dropout -- a dropout model runs the p = 0 plan and wants ITS images)
+    want_p3 = bool(engine.wants_resident_images(f0, train=False))
     if want_p3 != bool(res.p3_mode):                       # as loop.run_steps: layer 0 reads the resident feature image
         torch.cuda.synchronize(pipe.device)
-        res.enable_p3(agg=bool(engine.wants_agg_image(f0))) if want_p3 else res.disable_p3()
+        res.enable_p3(agg=bool(engine.wants_agg_image(f0, train=False))) if want_p3 else res.disable_p3()
         pipe._sets, pipe._free_ev = [], [None] * pipe.depth
     pipe.load(steps)
     total = sum(pipe.nodes(s) for s in range(len(steps)))
@@ -173,12 +174,20 @@ def test(data, config, weights_path=None, save_predictions=True):
     bs = max(1, int(config.TRAINING.batch_size))
     all_pred, all_true = [], []
     mean_test_acc = 0.0
-    if not config.TRAINING.dropout and len(data.graphs) > 0:
+    engine = None
+    if len(data.graphs) > 0:
+        # evaluation applies no dropout: a model trained with --dropout takes the same path (forward_logits binds the p = 0 plan);
+        # only a model the engine refuses to build for (a dropout model outside the one-call plan) keeps the module loop below
+        from .engine import FusedGcnSageStep
+        try:
+            engine = FusedGcnSageStep(model)
+        except ValueError:
+            if not config.TRAINING.dropout:
+                raise
+    if engine is not None:
         # the shipped configuration: pages resident in HBM, batches assembled on the device one forward ahead, one host call per
         # forward (predict_resident); one device -> host copy of all predictions at the end
-        from .engine import FusedGcnSageStep
         from .loop import BatchPipeline
-        engine = FusedGcnSageStep(model)
         pipe = BatchPipeline(G.ResidentPages(data.graphs, device))
         flat_pred = predict_resident(engine, pipe, bs).cpu().numpy()
         off = 0

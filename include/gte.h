@@ -471,6 +471,19 @@ int gte_dropout_mask(float p, uint64_t seed, int rank, int64_t step, int site, i
                      int64_t ldm, void* stream);
 int gte_dropout_mask_host(float p, uint64_t seed, int rank, int64_t step, int site, int64_t n_rows, int64_t n_cols, uint8_t* mask,
                           int64_t ldm);
+/* Rows of a dropout launch / nodes of a dropout plan: row indices, the kernels' grid-stride sums and the Philox row word are 32-bit,
+ * and 2^30 keeps all of them below 2^31.  There is NO byte bound: gte_spmm_dropout_p3 / _bwd address every image and row buffer
+ * through 64-bit per-lane addresses (their gathers reach arbitrary rows), the planes GEMMs rebase their operand windows per tile
+ * and stage, and the NT product's output window is rebased per wave tile in its WIDE form -- taken by gte_gemm_p3_nt when
+ * (m + 256) ldc 4 >= 2^31 and, inside gte_gcnsage_step, for every launch of a dropout layer with
+ * (n + 256) x 2 x max(ceil16(fout), ceil16(fin)) x 4 >= 2^31 (gte_gcnsage_step_wide_layers).  Below that the 32-bit form runs. */
+#define GTE_DROPOUT_MAX_ROWS ((int64_t)1 << 30)
+/* TEST HOOK, THREAD-LOCAL like the three gte_gemm_p3_set_* setters above: 1 = the calling host thread's later launches take the
+ * wide form at any size (every layer of a dropout plan, and any gte_gemm_p3_nt output), 0 = by size (default).  It does not
+ * reach launches another host thread issues (e.g. PyTorch's autograd thread): force it on the thread that calls
+ * gte_gcnsage_step, and assert the form taken with gte_gcnsage_step_wide_layers.  gte_dropout_get_wide: this thread's mode. */
+int gte_dropout_set_wide(int mode);
+int gte_dropout_get_wide(void);
 /* Producer of a dropout layer's operands (models.py:53-61 in training mode): with x' = D_0(x) when in_dropout (layer 0: the
  * model's input dropout applied to every gathered row and to the row's own features) else x,
  *     selfp3 = D_site(x'[v]),   aggp3 = D_site(scale_v sum_{u -> v} w_e x'[u])     (scale_v = 1 / in-degree, 0 without in-edges)
@@ -592,6 +605,9 @@ typedef struct gte_step_plan {
     float dropout_p; uint64_t dropout_seed; int rank;
 } gte_step_plan;
 /* *adam_fused: bit 0 = the optimiser step ran inside the fold launch, bit 1 = ... and it wrote the weight images */
+/* Which hidden layers of `plan` gte_gcnsage_step would run in the wide form on the calling thread: bit i = layer i (always 0 for a
+ * plan without dropout); a negative error code for a null / malformed plan.  Host logic only. */
+int gte_gcnsage_step_wide_layers(const gte_step_plan* plan);
 int gte_gcnsage_step(const gte_step_plan* plan, int phase, int* adam_fused, void* stream);
 /* The forward pass alone from the same plan (replaces `logits = model(g)` under no_grad: src/models/model_predict.py:141-147 and
  * the validation forward src/models/model_train.py:349-353): weight images, hidden layers, the output layer; logits [n, C] in
