@@ -22,6 +22,7 @@
 //   [16 k][8 blocks x 96 bytes] in memory order, the block position rotated by 2 (k mod 4) (again on the source side) so the
 //   four k rows a transposing read (ds_read_b64_tr_b16) touches fall on disjoint banks.
 #include "gte_common.h"
+#include "gemm_p3_host.h"
 #include "p3.h"
 #include "smallk_step.h"
 
@@ -1529,12 +1530,15 @@ TnPlan tn_plan(int64_t M, int64_t N, int64_t Nseg, int64_t K) {
     return pl;
 }
 
-#define GTE_SET_LDS(kernel, bytes) \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (bytes))
+// a kernel's dynamic-LDS limit, raised the first time its launcher runs (`done`: the launcher's own static flag)
+template <typename K>
+inline void set_lds_once(bool& done, K* kernel, int bytes) {
+    if (done) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = true;
+}
 
 }  // namespace
-
-namespace { int launch_nt(const P3Gemm& p, hipStream_t s); }
 
 extern "C" int64_t gte_p3_row_bytes(int64_t cols) { return cols > 0 ? p3::row_bytes(cols) : 0; }
 
@@ -1610,109 +1614,85 @@ extern "C" int gte_gemm_p3_set_rows64(int mode) {
     return GTE_OK;
 }
 
-// C[m, n] (+)= [a1 | a2] b^T (+ bias): a1 = P3 [m][k1], a2 = P3 [m][k2] (nullable, k2 = 0), b = P3 [n][ceil16(k1) + k2]
-// (the K blocks of the second segment follow the ceil(k1 / 16) blocks of the first in every row of b)
-static int gemm_p3_nt_impl(const void* a1, int64_t lda1, int64_t k1, const void* a2, int64_t lda2, int64_t k2, const void* b,
-                           int64_t ldb, const float* bias, int64_t bias_cols, float* c, int64_t ldc, int64_t m, int64_t n,
-                           int relu, int accumulate, void* stream, const int32_t* a_rows, int64_t n_res_rows, bool rows_both = false) {
-    if (m < 0 || n < 0 || k1 <= 0 || k2 < 0 || m > INT32_MAX || n > INT32_MAX || k1 + k2 > INT32_MAX)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt: bad sizes");
-    if (m == 0 || n == 0) return GTE_OK;
-    if (!a1 || !b || !c || (k2 > 0 && !a2)) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt: null pointer");
-    const int64_t kb1 = p3::blocks(k1), kb2 = p3::blocks(k2);
-    const P3Strides sb = p3_strides(ldb);
-    if (lda1 < kb1 * 96 || (k2 > 0 && lda2 < kb2 * 96) || !p3_strides_ok(ldb, n, 16 * (kb1 + kb2)) || ldc < n)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt: leading dimension too small");
-    // the output: one window over all of it while (m + 256) rows stay below 2 GB, else (or forced: gte_dropout_set_wide) a window
-    // per wave tile -- 256 rows of ldc floats must then fit 32-bit offsets with room to spare
-    const bool wide = gte::wide_forced() || (m + 256) * ldc * 4 >= ((int64_t)1 << 31);
-    if (lda1 >= (1 << 22) || lda2 >= (1 << 22) || sb.ld >= (1 << 22) || (wide && ldc >= (1 << 20)))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt: row strides must be < 4 MB (the output's, when it holds 2 GB or more: < 4 MB too)");
-    P3Gemm p = {};
-    p.wide_c = wide ? 1 : 0;
-    p.A1 = (const char*)a1; p.lda1 = lda1; p.KB1 = (int)kb1;
-    p.A2 = k2 > 0 ? (const char*)a2 : nullptr; p.lda2 = lda2; p.KB2 = (int)kb2;
-    p.B = (const char*)b; p.ldb = sb.ld; p.C = c; p.ldc = ldc; p.bias = bias; p.bias_cols = (int)bias_cols;
-    p.bsa1 = p.bsa2 = 96; p.bsb = sb.bs;
-    p.M = (int)m; p.N = (int)n; p.relu = relu; p.accumulate = accumulate; p.splits = 1;
-    if (a_rows) {
-        if (k2 > 0 && !rows_both) return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_rows: one K segment only (two: gte_gemm_p3_nt_rows2)");
-        if (n_res_rows <= 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_rows: empty resident image");
-        p.rowsA = a_rows; p.res_bytes = n_res_rows * lda1;
-        p.rows64 = rows64_needed(p.res_bytes);
-        if (rows_both) {
-            p.rows_both = 1; p.res_bytes2 = n_res_rows * lda2;
-            if (rows64_needed(p.res_bytes2)) p.rows64 = 1;     // (64-bit per-lane addresses for both images)
-        }
-    }
-    return launch_nt(p, gte::as_stream(stream));
-}
-
-extern "C" int gte_gemm_p3_nt(const void* a1, int64_t lda1, int64_t k1, const void* a2, int64_t lda2, int64_t k2, const void* b,
-                              int64_t ldb, const float* bias, int64_t bias_cols, float* c, int64_t ldc, int64_t m, int64_t n,
-                              int relu, int accumulate, void* stream) {
-    return gemm_p3_nt_impl(a1, lda1, k1, a2, lda2, k2, b, ldb, bias, bias_cols, c, ldc, m, n, relu, accumulate, stream, nullptr, 0);
-}
-
-// c[m, n] (+)= A b^T with A = the rows a_rows[0 .. m) of a RESIDENT P3 image a_res [n_res_rows][k]: the input layer's forward
-// transform straight from the resident features (no per-batch copy of the rows).  One K segment.  Images of 4 GB or more are
-// read through 64-bit per-lane addresses (the loader-wave kernels, 128 / 192 x 256 tiles).
-extern "C" int gte_gemm_p3_nt_rows(const void* a_res, int64_t ldpa, int64_t k, const int32_t* a_rows, int64_t n_res_rows, const void* b,
-                                   int64_t ldpb, const float* bias, int64_t bias_cols, float* c, int64_t ldc, int64_t m, int64_t n,
-                                   int relu, int accumulate, void* stream) {
-    if (!a_rows) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_rows: null row map");
-    return gemm_p3_nt_impl(a_res, ldpa, k, nullptr, 0, 0, b, ldpb, bias, bias_cols, c, ldc, m, n, relu, accumulate, stream, a_rows, n_res_rows);
-}
-
-// c[m, n] (+)= [A | A2] b^T with A / A2 = the rows a_rows[0 .. m) of TWO resident P3 images of n_res_rows rows and k columns each
-// (the input features and their cached mean aggregate: an aggregate-first input layer without any per-batch operand preparation);
-// b = P3 [n][2 ceil16(k)], the second K segment at block ceil(k / 16).  Images below 4 GB.
-extern "C" int gte_gemm_p3_nt_rows2(const void* a_res, int64_t ldpa, const void* a2_res, int64_t ldpa2, int64_t k, const int32_t* a_rows,
-                                    int64_t n_res_rows, const void* b, int64_t ldpb, const float* bias, int64_t bias_cols, float* c,
-                                    int64_t ldc, int64_t m, int64_t n, int relu, int accumulate, void* stream) {
-    if (!a_rows || !a2_res) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_rows2: null row map / second image");
-    return gemm_p3_nt_impl(a_res, ldpa, k, a2_res, ldpa2, k, b, ldpb, bias, bias_cols, c, ldc, m, n, relu, accumulate, stream, a_rows,
-                           n_res_rows, true);
-}
-
+// ---- NT, host side: ONE check of the operands (nt_prepare), ONE dispatch rule (nt_pick), the row-tile ladder once (launch_one_column);
+// the entry points below add their own outputs and epilogue operands ----
 namespace {
+// What an NT entry point allows, and what it found wrong with its OWN arguments (outputs, epilogue operands): the own_* findings are
+// reported from inside the one sequence of checks, so that a call that is wrong in two ways returns the code it always has:  sizes
+// (invalid) -- shape (unsupported) -- m or n == 0 (nothing to do) -- null pointers, leading dimensions (invalid) -- stride limits
+// (unsupported) -- row map (invalid).
+struct NtLimits {
+    int64_t max_ld;                 // every row stride (bytes) stays below this
+    bool below_2gb;                 // (m + 256) rows of each A segment stay below 2 GB
+    bool rows_ok;                   // the entry point takes a row map
+    bool own_sizes;                 // its sizes are bad (those of n, and the bound on k1 / k2, differ between the entry points)
+    const char* unsupported;        // nullptr, or why it does not take this shape
+    bool own_null, own_ld, own_stride;
+};
+
+// Validates the operands of [a1 | a2] b^T, m x n, and fills what every NT launch reads: A1 / A2 / B, the strides, KB1 / KB2, M, N,
+// splits and the row map.  Returns GTE_OK with p.M == 0 when there is nothing to do (p untouched).
+int nt_prepare(const char* name, const gte::P3NtOperands& o, int64_t m, int64_t n, const NtLimits& lim, P3Gemm& p) {
+    if (lim.own_sizes || m < 0 || o.k1 <= 0 || o.k2 < 0 || m > INT32_MAX) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: bad sizes", name);
+    if (lim.unsupported) return gte::fail(GTE_ERR_UNSUPPORTED, "%s: %s", name, lim.unsupported);
+    if (m == 0 || n == 0) return GTE_OK;
+    if (lim.own_null || !o.a1 || !o.b || (o.k2 > 0 && !o.a2)) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
+    const int64_t kb1 = p3::blocks(o.k1), kb2 = p3::blocks(o.k2);
+    const P3Strides sb = p3_strides(o.ldb);
+    if (lim.own_ld || o.lda1 < kb1 * 96 || (o.k2 > 0 && o.lda2 < kb2 * 96) || !p3_strides_ok(o.ldb, n, 16 * (kb1 + kb2)))
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: leading dimension too small", name);
+    const int64_t gb2 = (int64_t)1 << 31;
+    if (lim.own_stride || o.lda1 >= lim.max_ld || o.lda2 >= lim.max_ld || sb.ld >= lim.max_ld ||
+        (lim.below_2gb && ((m + 256) * o.lda1 >= gb2 || (o.k2 > 0 && (m + 256) * o.lda2 >= gb2))))
+        return gte::fail(GTE_ERR_UNSUPPORTED, "%s: row strides must be < %lld MB%s", name, (long long)(lim.max_ld >> 20),
+                         lim.below_2gb ? ", operand images < 2 GB" : " (an output of 2 GB or more: < 4 MB)");
+    if (o.rows && !lim.rows_ok) return gte::fail(GTE_ERR_UNSUPPORTED, "%s: takes no row map", name);
+    if (o.rows && o.n_res_rows <= 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: empty resident image", name);
+    p.A1 = (const char*)o.a1; p.lda1 = o.lda1; p.KB1 = (int)kb1;
+    p.A2 = o.k2 > 0 ? (const char*)o.a2 : nullptr; p.lda2 = o.lda2; p.KB2 = (int)kb2;
+    p.B = (const char*)o.b; p.ldb = sb.ld;
+    p.bsa1 = p.bsa2 = 96; p.bsb = sb.bs;
+    p.M = (int)m; p.N = (int)n; p.splits = 1;
+    if (o.rows) {                   // both segments behind the map; 64-bit per-lane addresses as soon as ONE image needs them
+        p.rowsA = o.rows; p.res_bytes = o.n_res_rows * o.lda1;
+        if (o.k2 > 0) { p.rows_both = 1; p.res_bytes2 = o.n_res_rows * o.lda2; }
+        p.rows64 = (rows64_needed(p.res_bytes) || (o.k2 > 0 && rows64_needed(p.res_bytes2))) ? 1 : 0;
+    }
+    return GTE_OK;
+}
+
 template <int WM, int WN, int TM, int TN, int NBUF, int WGS>
 void launch_ring(const P3Gemm& p, hipStream_t s) {
     constexpr int NW = WM * WN, BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int NI = ((BM + BN) * 96 / 1024 + NW - 1) / NW, shm = NBUF * NI * NW * 1024;
     static bool configured = false;
-    if (!configured) {
-        GTE_SET_LDS((gemm_p3_nt_ring_kernel<WM, WN, TM, TN, NBUF, WGS>), shm);
-        configured = true;
-    }
+    set_lds_once(configured, &gemm_p3_nt_ring_kernel<WM, WN, TM, TN, NBUF, WGS>, shm);
     const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, BN)));
     hipLaunchKernelGGL((gemm_p3_nt_ring_kernel<WM, WN, TM, TN, NBUF, WGS>), grid, dim3(NW * 64), shm, s, p);
 }
-template <int WM, int WN, int TM, int TN, int NL, bool BIG = false>
+// (LNB != 0: an epilogue on whole rows -- n <= 256 = BN, one column of tiles)
+template <int WM, int WN, int TM, int TN, int NL, int LNB = 0, bool BIG = false>
 void launch_lw(const P3Gemm& p, hipStream_t s) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int NI = ((BM + BN) * 96 / 1024 + NL - 1) / NL, shm = 3 * NI * NL * 1024;
+    static_assert(LNB == 0 || (BN == 256 && shm >= TM * 32 * 256 * 4 && shm >= WM * WN * 3 * 256 * 4),
+                  "the epilogue's row slice lives in the stage images");
     static bool configured = false;
-    if (!configured) {
-        GTE_SET_LDS((gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, 0, BIG>), shm);
-        configured = true;
-    }
+    set_lds_once(configured, &gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, LNB, BIG>, shm);
     const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, BN)));
-    hipLaunchKernelGGL((gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, 0, BIG>), grid, dim3((WM * WN + NL) * 64), shm, s, p);
-}
-template <int WM, int WN, int TM, int TN, int NL, int LNB = 1, bool BIG = false>
-void launch_lw_lnb(const P3Gemm& p, hipStream_t s) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    constexpr int NI = ((BM + BN) * 96 / 1024 + NL - 1) / NL, shm = 3 * NI * NL * 1024;
-    static_assert(shm >= TM * 32 * 256 * 4 && shm >= WM * WN * 3 * 256 * 4, "the epilogue's row slice lives in the stage images");
-    static bool configured = false;
-    if (!configured) {
-        GTE_SET_LDS((gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, LNB, BIG>), shm);
-        configured = true;
-    }
-    const dim3 grid((unsigned)gte::ceil_div(p.M, BM));
     hipLaunchKernelGGL((gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, LNB, BIG>), grid, dim3((WM * WN + NL) * 64), shm, s, p);
 }
+// the block-major-weights kernel (gemm_p3_nt_sq_kernel): (32 TM) x 256 tiles
+template <int TM, int NL, int LNB>
+void launch_sq(const P3Gemm& p, hipStream_t s) {
+    constexpr int BM = TM * 32, shm = 3 * 4 * BM * 96 + 1024;
+    static_assert(LNB == 0 || (shm >= BM * 256 * 4 && shm >= 8 * 3 * 256 * 4), "the epilogue's row slice lives in the slots");
+    static bool configured = false;
+    set_lds_once(configured, &gemm_p3_nt_sq_kernel<TM, NL, LNB>, shm);
+    const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, 256)));
+    hipLaunchKernelGGL((gemm_p3_nt_sq_kernel<TM, NL, LNB>), grid, dim3((8 + NL) * 64), shm, s, p);
+}
+
 // The block-major-weights kernel takes a product when the weights ARE block-major, the rows are reached through 32-bit offsets, one
 // column of tiles covers the output, and cutting the K blocks into slots of four pads the K loop by at most 1 / 12 ...
 inline bool sq_applies(const P3Gemm& p) {
@@ -1725,19 +1705,6 @@ inline bool sq_applies(const P3Gemm& p) {
 }
 // ... a PLAIN product (no LayerNorm epilogue) additionally wants its one column of tiles more than half full
 inline bool sq_plain_wanted(const P3Gemm& p) { return p.N > 128; }
-// the block-major-weights kernel (gemm_p3_nt_sq_kernel): (32 TM) x 256 tiles
-template <int TM, int NL, int LNB>
-void launch_sq(const P3Gemm& p, hipStream_t s) {
-    constexpr int BM = TM * 32, shm = 3 * 4 * BM * 96 + 1024;
-    static_assert(LNB == 0 || (shm >= BM * 256 * 4 && shm >= 8 * 3 * 256 * 4), "the epilogue's row slice lives in the slots");
-    static bool configured = false;
-    if (!configured) {
-        GTE_SET_LDS((gemm_p3_nt_sq_kernel<TM, NL, LNB>), shm);
-        configured = true;
-    }
-    const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, 256)));
-    hipLaunchKernelGGL((gemm_p3_nt_sq_kernel<TM, NL, LNB>), grid, dim3((8 + NL) * 64), shm, s, p);
-}
 // Configurations (measured on the step's shapes, profiles/r03/gemm_p3.md): the kernel runs at the chip's power limit
 // (~1.3 PF bf16 whatever the tile), so what matters is ONE balanced round of tiles: the row tile is the smallest of
 // 128 / 160 / 192 / 224 / 256 that covers M with at most one tile per CU; N is cut in 256-column tiles.
@@ -1752,11 +1719,9 @@ constexpr NtCfg kNtCfg[] = {{0, 64, 128, 3}, {1, 128, 128, 2}, {2, 128, 256, 1},
 // this was a static getenv read once -- the per-configuration tests that set the variable after the first GEMM of the process ran
 // the chooser's pick every time) or GTE_P3_NT_CFG at the first call
 thread_local int g_nt_cfg = -2;
-int nt_choose(const P3Gemm& p) {
-    if (g_nt_cfg == -2) g_nt_cfg = GTE_MEASURE_INT("GTE_P3_NT_CFG", -1);
+int nt_choose(const P3Gemm& p, int cus) {
     const int forced = g_nt_cfg;
     if (forced >= 0 && forced <= 7) return forced;
-    const int cus = gte::device_props().cus;
     double best = 1e30;
     int bi = 0;
     for (const NtCfg& c : kNtCfg) {
@@ -1776,45 +1741,164 @@ inline int one_round_row_tile(int64_t m, int64_t cus, int min_tile = 32) {
         if (t >= min_tile && gte::ceil_div(m, t) <= cus) return t;
     return 128;
 }
-int lnb_row_tile(int64_t m);
-int launch_nt(const P3Gemm& p, hipStream_t s) {
+// Row tile of the fused dX + LayerNorm-backward launch: 128.  (A 192-row instantiation served m > 128 x #CUs until round 3: its
+// epilogue's row slice + 96 accumulator registers did not fit the 170-register budget of three waves per SIMD -- 140 bytes of
+// scratch per lane.  Batches beyond one round of 128-row tiles run several rounds of the same kernel.)
+// Round 5: 96 rows (1 x 8 waves of 96 x 32) while that covers m in ONE round of tiles -- 24 317 rows of the headline batch are 190
+// tiles of 128 rows on 256 CUs, a quarter of the chip idle for the whole launch; 254 tiles of 96 rows fill it.
+// ... and 64 / 32 rows (1 x 8 waves of 64 x 32 / 32 x 32) for batches that leave CUs idle even then: the launch lasts as long
+// as ONE tile's K loop whatever the number of tiles in the round (L0 forward, K = 1 662: 106 us on 50 tiles of 128 rows, 109 us
+// on 95, 124 us on 202 -- profiles/r05/sequence_pages*.txt), so a small batch wants the smallest tile that still is one round.
+thread_local int g_ln_rows = -1;        // forced row tile of the one-column launches: 0 = the chooser (gte_gemm_p3_set_ln_rows)
+int lnb_row_tile(int64_t m, int cus) {
+    if (g_ln_rows < 0) g_ln_rows = GTE_MEASURE_INT("GTE_P3_LN_ROWS", 0);        // (32 / 64 / 96 / 128)
+    const int forced = g_ln_rows;
+    if (forced == 32 || forced == 64 || forced == 96 || forced == 128) return forced;
+    static const int min_tile = GTE_MEASURE_INT("GTE_P3_LN_MIN_ROWS", 32);
+    return one_round_row_tile(m, cus, min_tile);
+}
+
+// THE dispatch rule of the NT products: which kernel family a prepared product takes, and on which row tile.  epilogue: 0 plain,
+// 1 / 3 LayerNorm backward (3: a width that is no multiple of 16), 4 LayerNorm forward.  cus <= 0: the device's (given: pure host logic).
+//   rows64  a row map into an image of 4 GB or more: the loader-wave kernels on 64-bit per-lane addresses (128 / 192 rows)
+//   sq      the block-major-weights kernel on ONE column of tiles, the row tile by the one-round rule
+//   lw      the loader-wave kernel: an epilogue's one column of tiles (one-round rule), or a plain 128 / 192 x 256 (cfg: its id)
+//   ring    the ring kernels of a plain product (cfg: the configuration's id)
+enum class NtFamily { rows64, sq, lw, ring };
+struct NtPick { NtFamily family; int bm, cfg; };
+NtPick nt_pick(const P3Gemm& p, int epilogue, int cus = 0) {
+    if (cus <= 0) cus = gte::device_props().cus;
     if (p.rowsA && p.rows64) {
-        // a row map into an image of 4 GB or more: the two loader-wave tiles, whichever makes the shorter schedule
-        const int cus = gte::device_props().cus;
+        if (epilogue != 0) return {NtFamily::rows64, 128, -1};
+        // a plain product: the two loader-wave tiles, whichever makes the shorter schedule
         const int64_t r128 = gte::ceil_div(gte::ceil_div(p.M, 128) * gte::ceil_div(p.N, 256), cus) * 128;
         const int64_t r192 = gte::ceil_div(gte::ceil_div(p.M, 192) * gte::ceil_div(p.N, 256), cus) * 192;
-        if (r192 < r128) launch_lw<2, 4, 3, 2, 4, true>(p, s); else launch_lw<2, 4, 2, 2, 4, true>(p, s);
-        return gte::check_launch("gemm_p3_nt_rows");
+        return {NtFamily::rows64, r192 < r128 ? 192 : 128, -1};
     }
+    // (column tiles of 128 / 192 for hidden widths up to 128 / 192 were measured in round 5 and removed: 27 -> 30 us at 96 columns)
+    if (epilogue != 0) return {sq_applies(p) ? NtFamily::sq : NtFamily::lw, lnb_row_tile(p.M, cus), -1};
     if (g_nt_cfg == -2) g_nt_cfg = GTE_MEASURE_INT("GTE_P3_NT_CFG", -1);
-    if (g_nt_cfg < 0 && sq_applies(p) && sq_plain_wanted(p)) {
-        // block-major weights and one column of tiles more than half full: the block-major-weights kernel, on the smallest row tile
-        // that covers M in one round (the narrow-width input GEMMs of the scaled runs: 2 x 96 ... 2 x 128 columns over K = 781 / 831)
-        const int bm = lnb_row_tile(p.M);
-        if (bm == 32) launch_sq<1, 4, 0>(p, s);
-        else if (bm == 64) launch_sq<2, 4, 0>(p, s);
-        else if (bm == 96) launch_sq<3, 4, 0>(p, s);
-        else launch_sq<4, 4, 0>(p, s);
-        return gte::check_launch("gemm_p3_nt");
+    // block-major weights and one column of tiles more than half full: the block-major-weights kernel, on the smallest row tile
+    // that covers M in one round (the narrow-width input GEMMs of the scaled runs: 2 x 96 ... 2 x 128 columns over K = 781 / 831)
+    if (g_nt_cfg < 0 && sq_applies(p) && sq_plain_wanted(p)) return {NtFamily::sq, lnb_row_tile(p.M, cus), -1};
+    const int cfg = nt_choose(p, cus);
+    return {cfg == 2 || cfg == 4 ? NtFamily::lw : NtFamily::ring, cfg == 7 ? 192 : kNtCfg[cfg].bm, cfg};
+}
+
+// The launches on ONE column of tiles (n <= 256): the 32 / 64 / 96 / 128-row ladder of the block-major-weights kernel and of the
+// loader-wave kernel with an epilogue.  LNB 0 (plain) exists on the block-major-weights kernel only.
+template <int LNB>
+void launch_one_column(const P3Gemm& p, const NtPick& k, hipStream_t s) {
+    const int bm = k.bm;
+    if (k.family == NtFamily::sq) {                       // fragments straight to registers, 64-deep A slots
+        if (bm == 32) launch_sq<1, 4, LNB>(p, s);
+        else if (bm == 64) launch_sq<2, 4, LNB>(p, s);
+        else if (bm == 96) launch_sq<3, 4, LNB>(p, s);
+        else launch_sq<4, 4, LNB>(p, s);
+    } else if constexpr (LNB != 0) {
+        if constexpr (LNB == 4)                           // (rows64: no range check, the rows past the tile re-read its first row)
+            if (k.family == NtFamily::rows64) return launch_lw<2, 4, 2, 2, 4, 4, true>(p, s);
+        if (bm == 32) launch_lw<1, 8, 1, 1, 4, LNB>(p, s);
+        else if (bm == 64) launch_lw<1, 8, 2, 1, 4, LNB>(p, s);
+        else if (bm == 96) launch_lw<1, 8, 3, 1, 4, LNB>(p, s);
+        else launch_lw<2, 4, 2, 2, 4, LNB>(p, s);
     }
-    int cfg = nt_choose(p);
-    switch (cfg) {
-        case 7: launch_ring<2, 4, 3, 2, 3, 1>(p, s); break;     // measurement: 192 x 256 ring (no loader waves)
-        case 0: launch_ring<2, 2, 1, 2, 2, 3>(p, s); break;    //  64 x 128, three workgroups per CU
-        case 1: launch_ring<2, 2, 2, 2, 3, 2>(p, s); break;    // 128 x 128, two
-        case 2: launch_lw<2, 4, 2, 2, 4>(p, s); break;         // 128 x 256: 8 compute + 4 loader waves
-        case 3: launch_ring<1, 8, 5, 1, 3, 1>(p, s); break;    // 160 x 256: 1 x 8 waves of 160 x 32
-        case 4: launch_lw<2, 4, 3, 2, 4>(p, s); break;         // 192 x 256: 8 compute + 4 loader waves
-        case 5: launch_ring<1, 8, 7, 1, 3, 1>(p, s); break;    // 224 x 256
-        default: launch_ring<2, 4, 4, 2, 3, 1>(p, s); break;   // 256 x 256
+}
+
+int launch_nt(const P3Gemm& p, hipStream_t s) {
+    const NtPick k = nt_pick(p, 0);
+    if (k.family == NtFamily::rows64) {
+        if (k.bm == 192) launch_lw<2, 4, 3, 2, 4, 0, true>(p, s); else launch_lw<2, 4, 2, 2, 4, 0, true>(p, s);
+    } else if (k.family == NtFamily::sq) {
+        launch_one_column<0>(p, k, s);
+    } else {
+        switch (k.cfg) {
+            case 7: launch_ring<2, 4, 3, 2, 3, 1>(p, s); break;     // measurement: 192 x 256 ring (no loader waves)
+            case 0: launch_ring<2, 2, 1, 2, 2, 3>(p, s); break;    //  64 x 128, three workgroups per CU
+            case 1: launch_ring<2, 2, 2, 2, 3, 2>(p, s); break;    // 128 x 128, two
+            case 2: launch_lw<2, 4, 2, 2, 4>(p, s); break;         // 128 x 256: 8 compute + 4 loader waves
+            case 3: launch_ring<1, 8, 5, 1, 3, 1>(p, s); break;    // 160 x 256: 1 x 8 waves of 160 x 32
+            case 4: launch_lw<2, 4, 3, 2, 4>(p, s); break;         // 192 x 256: 8 compute + 4 loader waves
+            case 5: launch_ring<1, 8, 7, 1, 3, 1>(p, s); break;    // 224 x 256
+            default: launch_ring<2, 4, 4, 2, 3, 1>(p, s); break;   // 256 x 256
+        }
     }
-    return gte::check_launch("gemm_p3_nt");
+    return gte::check_launch(k.family == NtFamily::rows64 ? "gemm_p3_nt_rows" : "gemm_p3_nt");
+}
+
+// out[j] = sum_k part[k * stride + j]   (only when no fold deferral is open)
+__global__ void __launch_bounds__(256)
+p3_colsum_fold_kernel(const float* __restrict__ part, long long stride, int count, int n, float* __restrict__ out) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    float s = 0.f;
+    for (int k = 0; k < count; ++k) s += part[k * stride + j];
+    out[j] = s;
+}
+// the LayerNorm column partials part[nb][3][n] = {sum g xhat, sum g, sum dz} of nb row tiles into dgamma / dbeta / dbias (each
+// nullable): they join an open fold deferral, else three launches
+int fold_ln_partials(const char* what, float* part, int64_t n, int nb, float* dgamma, float* dbeta, float* dbias, hipStream_t s) {
+    float* outs[3] = {dgamma, dbeta, dbias};
+    if (gte::defer_fold(part, 3 * n, nb, 1, (int)n, outs[0], n)) {
+        gte::defer_fold(part + n, 3 * n, nb, 1, (int)n, outs[1], n);
+        gte::defer_fold(part + 2 * n, 3 * n, nb, 1, (int)n, outs[2], n);
+        return GTE_OK;
+    }
+    for (int i = 0; i < 3; ++i)
+        if (outs[i])
+            hipLaunchKernelGGL(p3_colsum_fold_kernel, dim3((unsigned)gte::ceil_div(n, 256)), dim3(256), 0, s, part + i * n, (long long)3 * n, nb,
+                               (int)n, outs[i]);
+    return gte::check_launch(what);
 }
 }  // namespace
 
-// Which kernel family an NT product with ONE column of tiles takes (pure host logic: no device call when `cus` > 0).  Returns 1 for
-// the block-major-weights kernel (gemm_p3_nt_sq_kernel), 0 for the loader-wave / ring kernels; *row_tile = rows of its tile where
-// the launch picks one by the one-round rule (the LayerNorm-epilogue launches and the narrow plain products), else 0.
+// C[m, n] (+)= [a1 | a2] b^T (+ bias): a1 = P3 [m][k1], a2 = P3 [m][k2] (nullable, k2 = 0), b = P3 [n][ceil16(k1) + k2]
+// (the K blocks of the second segment follow the ceil(k1 / 16) blocks of the first in every row of b)
+int gte::gemm_p3_nt(const P3NtOperands& op, const float* bias, int64_t bias_cols, float* c, int64_t ldc, int64_t m, int64_t n, int relu,
+                    int accumulate, void* stream, const char* name) {
+    // the output: one window over all of it while (m + 256) rows stay below 2 GB, else (or forced: gte_dropout_set_wide) a window
+    // per wave tile -- 256 rows of ldc floats must then fit 32-bit offsets with room to spare
+    const bool wide = gte::wide_forced() || (m + 256) * ldc * 4 >= ((int64_t)1 << 31);
+    NtLimits lim = {};
+    lim.max_ld = 1 << 22; lim.rows_ok = true;
+    lim.own_sizes = n < 0 || n > INT32_MAX || op.k1 + op.k2 > INT32_MAX;
+    lim.own_null = !c; lim.own_ld = ldc < n; lim.own_stride = wide && ldc >= (1 << 20);
+    P3Gemm p = {};
+    const int rc = nt_prepare(name, op, m, n, lim, p);
+    if (rc != GTE_OK || p.M == 0) return rc;
+    p.wide_c = wide ? 1 : 0;
+    p.C = c; p.ldc = ldc; p.bias = bias; p.bias_cols = (int)bias_cols; p.relu = relu; p.accumulate = accumulate;
+    return launch_nt(p, gte::as_stream(stream));
+}
+
+extern "C" int gte_gemm_p3_nt(const void* a1, int64_t lda1, int64_t k1, const void* a2, int64_t lda2, int64_t k2, const void* b,
+                              int64_t ldb, const float* bias, int64_t bias_cols, float* c, int64_t ldc, int64_t m, int64_t n,
+                              int relu, int accumulate, void* stream) {
+    return gte::gemm_p3_nt({a1, lda1, k1, a2, lda2, k2, b, ldb, nullptr, 0}, bias, bias_cols, c, ldc, m, n, relu, accumulate, stream);
+}
+
+// ... with a row map: ONE resident image (the input layer's forward transform straight from the resident features) ...
+extern "C" int gte_gemm_p3_nt_rows(const void* a_res, int64_t ldpa, int64_t k, const int32_t* a_rows, int64_t n_res_rows, const void* b,
+                                   int64_t ldpb, const float* bias, int64_t bias_cols, float* c, int64_t ldc, int64_t m, int64_t n,
+                                   int relu, int accumulate, void* stream) {
+    if (!a_rows) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_rows: null row map");
+    return gte::gemm_p3_nt({a_res, ldpa, k, nullptr, 0, 0, b, ldpb, a_rows, n_res_rows}, bias, bias_cols, c, ldc, m, n, relu, accumulate,
+                           stream, "gemm_p3_nt_rows");
+}
+
+// ... or TWO of k columns each (the input features and their cached mean aggregate), the second K segment at block ceil(k / 16) of b
+extern "C" int gte_gemm_p3_nt_rows2(const void* a_res, int64_t ldpa, const void* a2_res, int64_t ldpa2, int64_t k, const int32_t* a_rows,
+                                    int64_t n_res_rows, const void* b, int64_t ldpb, const float* bias, int64_t bias_cols, float* c,
+                                    int64_t ldc, int64_t m, int64_t n, int relu, int accumulate, void* stream) {
+    if (!a_rows || !a2_res) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_rows2: null row map / second image");
+    return gte::gemm_p3_nt({a_res, ldpa, k, a2_res, ldpa2, k, b, ldpb, a_rows, n_res_rows}, bias, bias_cols, c, ldc, m, n, relu, accumulate,
+                           stream, "gemm_p3_nt_rows2");
+}
+
+// Which kernel family an NT product with ONE column of tiles takes (pure host logic: no device call when `cus` > 0): what nt_pick
+// says of the product.  Returns 1 for the block-major-weights kernel (gemm_p3_nt_sq_kernel), 0 for the loader-wave / ring kernels;
+// *row_tile = rows of its tile where the launch picks one by the one-round rule (the LayerNorm-epilogue launches and the narrow
+// plain products), else 0.
 extern "C" int gte_gemm_p3_nt_plan(int64_t m, int64_t n, int64_t k1, int64_t k2, int weights_block_major, int epilogue, int cus,
                                    int* row_tile) {
     if (row_tile) *row_tile = 0;
@@ -1824,9 +1908,9 @@ extern "C" int gte_gemm_p3_nt_plan(int64_t m, int64_t n, int64_t k1, int64_t k2,
     p.M = (int)m; p.N = (int)n; p.KB1 = (int)p3::blocks(k1); p.KB2 = (int)p3::blocks(k2);
     p.bsa1 = p.bsa2 = 96;
     p.ldb = weights_block_major ? 96 : (p.KB1 + p.KB2) * 96; p.bsb = weights_block_major ? gte::round_up(n, 16) * 96 : 96;
-    const int bm = one_round_row_tile(m, cus > 0 ? cus : gte::device_props().cus);
-    const bool sq = sq_applies(p) && (epilogue != 0 || sq_plain_wanted(p));
-    if (row_tile && n <= 256 && (epilogue != 0 || sq)) *row_tile = bm;
+    const NtPick k = nt_pick(p, epilogue, cus);
+    const bool sq = k.family == NtFamily::sq;
+    if (row_tile && n <= 256 && (epilogue != 0 || sq)) *row_tile = k.bm;
     return sq ? 1 : 0;
 }
 
@@ -1837,33 +1921,6 @@ extern "C" int gte_gemm_p3_set_nt_cfg(int cfg) {
 }
 
 // ---- the NT product with the LayerNorm(+ReLU) backward of the layer below as its epilogue ------------------------------
-namespace {
-// Row tile of the fused dX + LayerNorm-backward launch: 128.  (A 192-row instantiation served m > 128 x #CUs until round 3: its
-// epilogue's row slice + 96 accumulator registers did not fit the 170-register budget of three waves per SIMD -- 140 bytes of
-// scratch per lane.  Batches beyond one round of 128-row tiles run several rounds of the same kernel.)
-// Round 5: 96 rows (1 x 8 waves of 96 x 32) while that covers m in ONE round of tiles -- 24 317 rows of the headline batch are 190
-// tiles of 128 rows on 256 CUs, a quarter of the chip idle for the whole launch; 254 tiles of 96 rows fill it.
-// ... and 64 / 32 rows (1 x 8 waves of 64 x 32 / 32 x 32) for batches that leave CUs idle even then: the launch lasts as long
-// as ONE tile's K loop whatever the number of tiles in the round (L0 forward, K = 1 662: 106 us on 50 tiles of 128 rows, 109 us
-// on 95, 124 us on 202 -- profiles/r05/sequence_pages*.txt), so a small batch wants the smallest tile that still is one round.
-thread_local int g_ln_rows = -1;        // forced row tile of the LayerNorm-epilogue launches: 0 = the chooser (gte_gemm_p3_set_ln_rows)
-int lnb_row_tile(int64_t m) {
-    if (g_ln_rows < 0) g_ln_rows = GTE_MEASURE_INT("GTE_P3_LN_ROWS", 0);        // (32 / 64 / 96 / 128)
-    const int forced = g_ln_rows;
-    if (forced == 32 || forced == 64 || forced == 96 || forced == 128) return forced;
-    static const int min_tile = GTE_MEASURE_INT("GTE_P3_LN_MIN_ROWS", 32);
-    return one_round_row_tile(m, gte::device_props().cus, min_tile);
-}
-// out[j] = sum_k part[k * stride + j]   (only when no fold deferral is open)
-__global__ void __launch_bounds__(256)
-p3_colsum_fold_kernel(const float* __restrict__ part, long long stride, int count, int n, float* __restrict__ out) {
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= n) return;
-    float s = 0.f;
-    for (int k = 0; k < count; ++k) s += part[k * stride + j];
-    out[j] = s;
-}
-}
 extern "C" int gte_gemm_p3_set_ln_rows(int rows) {
     if (rows != 0 && rows != 32 && rows != 64 && rows != 96 && rows != 128)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_set_ln_rows: 0 (chooser), 32, 64, 96 or 128");
@@ -1882,128 +1939,65 @@ extern "C" int64_t gte_gemm_p3_nt_ln_bwd_workspace_bytes(int64_t m, int64_t n) {
 // (each nullable) join the fold deferral.  Same arithmetic as gte_gemm_p3_nt + gte_ln_relu_bwd_p3: dz is bit-identical.  dz itself is
 // nullable when dzp3 is given (the layer below reads the image only: an input layer on the cached aggregate has no transpose
 // aggregation, its dW = dz^T [x | ahn] takes the image -- 25 MB per step less at 24 k x 256).
+int gte::gemm_p3_nt_ln_bwd(const P3NtOperands& op, const float* z, int64_t ldz, const float* stats, const float* gamma, const float* beta,
+                           int relu, float* dz, int64_t lddz, void* dzp3, int64_t ldp3, float* dgamma, float* dbeta, float* dbias,
+                           int64_t m, int64_t n, void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* name = "gemm_p3_nt_ln_bwd";
+    const int64_t n4 = gte::round_up(n, 4);
+    NtLimits lim = {};
+    lim.max_ld = 1 << 23; lim.below_2gb = true;
+    lim.own_sizes = n <= 0 || op.k1 > INT32_MAX || op.k2 > INT32_MAX;
+    lim.unsupported = gte_gemm_p3_nt_ln_bwd_supported(n) ? nullptr : "needs n <= 256";
+    lim.own_null = !z || !stats || !gamma || !beta || (!dz && !dzp3) || !workspace;
+    lim.own_ld = ldz < n4 || (dz && lddz < n4) || (dzp3 && (ldp3 < p3::row_bytes(n) || ldp3 % 16 != 0));
+    P3Gemm p = {};
+    int rc = nt_prepare(name, op, m, n, lim, p);
+    if (rc != GTE_OK || p.M == 0) return rc;
+    const int64_t need = gte_gemm_p3_nt_ln_bwd_workspace_bytes(m, n);
+    if (workspace_bytes < need)
+        return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "%s: needs %lld workspace bytes, got %lld", name, (long long)need, (long long)workspace_bytes);
+    p.ln_z = z; p.ln_ldz = ldz; p.ln_stats = stats; p.ln_gamma = gamma; p.ln_beta = beta; p.ln_relu = relu;
+    p.ln_dz = dz; p.ln_lddz = lddz; p.ln_dzp3 = reinterpret_cast<char*>(dzp3); p.ln_ldp3 = ldp3;
+    p.ln_part = reinterpret_cast<float*>(workspace);
+    hipStream_t s = gte::as_stream(stream);
+    // (a width that is no multiple of 16: per-element validity, zero image columns up to the next multiple of 16)
+    const NtPick k = nt_pick(p, n % 16 == 0 ? 1 : 3);
+    if (n % 16 == 0) launch_one_column<1>(p, k, s); else launch_one_column<3>(p, k, s);
+    rc = gte::check_launch(name);
+    if (rc != GTE_OK) return rc;
+    return fold_ln_partials("gemm_p3_nt_ln_bwd fold", p.ln_part, n, (int)gte::ceil_div(m, k.bm), dgamma, dbeta, dbias, s);
+}
 extern "C" int gte_gemm_p3_nt_ln_bwd(const void* a1, int64_t lda1, int64_t k1, const void* a2, int64_t lda2, int64_t k2, const void* b,
                                      int64_t ldb, const float* z, int64_t ldz, const float* stats, const float* gamma,
                                      const float* beta, int relu, float* dz, int64_t lddz, void* dzp3, int64_t ldp3, float* dgamma,
                                      float* dbeta, float* dbias, int64_t m, int64_t n, void* workspace, int64_t workspace_bytes,
                                      void* stream) {
-    if (m < 0 || n <= 0 || k1 <= 0 || k2 < 0 || m > INT32_MAX || k1 > INT32_MAX || k2 > INT32_MAX)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_bwd: bad sizes");
-    if (!gte_gemm_p3_nt_ln_bwd_supported(n)) return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_ln_bwd: needs n <= 256");
-    if (m == 0) return GTE_OK;
-    if (!a1 || !b || !z || !stats || !gamma || !beta || (!dz && !dzp3) || !workspace || (k2 > 0 && !a2))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_bwd: null pointer");
-    const int64_t kb1 = p3::blocks(k1), kb2 = k2 > 0 ? p3::blocks(k2) : 0;
-    const int64_t n4 = gte::round_up(n, 4);
-    const P3Strides sb = p3_strides(ldb);
-    if (lda1 < p3::row_bytes(k1) || (k2 > 0 && lda2 < p3::row_bytes(k2)) || !p3_strides_ok(ldb, n, 16 * (kb1 + kb2)) || ldz < n4 ||
-        (dz && lddz < n4) || (dzp3 && (ldp3 < p3::row_bytes(n) || ldp3 % 16 != 0)))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_bwd: leading dimension too small");
-    if (lda1 >= (1 << 23) || lda2 >= (1 << 23) || sb.ld >= (1 << 23) || (m + 256) * lda1 >= ((int64_t)1 << 31) ||
-        (k2 > 0 && (m + 256) * lda2 >= ((int64_t)1 << 31)))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_ln_bwd: operand images must be < 2 GB with row strides < 8 MB");
-    const int64_t need = gte_gemm_p3_nt_ln_bwd_workspace_bytes(m, n);
-    if (workspace_bytes < need)
-        return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "gemm_p3_nt_ln_bwd: needs %lld workspace bytes, got %lld", (long long)need,
-                         (long long)workspace_bytes);
-    P3Gemm p = {};
-    p.A1 = reinterpret_cast<const char*>(a1); p.lda1 = lda1; p.KB1 = (int)kb1;
-    p.A2 = k2 > 0 ? reinterpret_cast<const char*>(a2) : nullptr; p.lda2 = lda2; p.KB2 = (int)kb2;
-    p.B = reinterpret_cast<const char*>(b); p.ldb = sb.ld;
-    p.bsa1 = p.bsa2 = 96; p.bsb = sb.bs;
-    p.M = (int)m; p.N = (int)n; p.splits = 1;
-    p.ln_z = z; p.ln_ldz = ldz; p.ln_stats = stats; p.ln_gamma = gamma; p.ln_beta = beta; p.ln_relu = relu;
-    p.ln_dz = dz; p.ln_lddz = lddz; p.ln_dzp3 = reinterpret_cast<char*>(dzp3); p.ln_ldp3 = ldp3;
-    p.ln_part = reinterpret_cast<float*>(workspace);
-    hipStream_t s = gte::as_stream(stream);
-    const int bm = lnb_row_tile(m);
-    // (column tiles of 128 / 192 for hidden widths up to 128 / 192 were measured in round 5 and removed: 27 -> 30 us at 96 columns)
-    if (sq_applies(p)) {                                  // block-major weights: fragments straight to registers, 64-deep A slots
-        if (n % 16 == 0) {
-            if (bm == 32) launch_sq<1, 4, 1>(p, s);
-            else if (bm == 64) launch_sq<2, 4, 1>(p, s);
-            else if (bm == 96) launch_sq<3, 4, 1>(p, s);
-            else launch_sq<4, 4, 1>(p, s);
-        } else {
-            if (bm == 32) launch_sq<1, 4, 3>(p, s);
-            else if (bm == 64) launch_sq<2, 4, 3>(p, s);
-            else if (bm == 96) launch_sq<3, 4, 3>(p, s);
-            else launch_sq<4, 4, 3>(p, s);
-        }
-    } else if (n % 16 == 0) {
-        if (bm == 32) launch_lw_lnb<1, 8, 1, 1, 4>(p, s);
-        else if (bm == 64) launch_lw_lnb<1, 8, 2, 1, 4>(p, s);
-        else if (bm == 96) launch_lw_lnb<1, 8, 3, 1, 4>(p, s);
-        else launch_lw_lnb<2, 4, 2, 2, 4>(p, s);
-    } else {                                              // per-element validity, zero image columns up to the next multiple of 16
-        if (bm == 32) launch_lw_lnb<1, 8, 1, 1, 4, 3>(p, s);
-        else if (bm == 64) launch_lw_lnb<1, 8, 2, 1, 4, 3>(p, s);
-        else if (bm == 96) launch_lw_lnb<1, 8, 3, 1, 4, 3>(p, s);
-        else launch_lw_lnb<2, 4, 2, 2, 4, 3>(p, s);
-    }
-    int rc = gte::check_launch("gemm_p3_nt_ln_bwd");
-    if (rc != GTE_OK) return rc;
-    const int nb = (int)gte::ceil_div(m, bm);
-    if (gte::defer_fold(p.ln_part, 3 * n, nb, 1, (int)n, dgamma, n)) {
-        gte::defer_fold(p.ln_part + n, 3 * n, nb, 1, (int)n, dbeta, n);
-        gte::defer_fold(p.ln_part + 2 * n, 3 * n, nb, 1, (int)n, dbias, n);
-        return GTE_OK;
-    }
-    float* outs[3] = {dgamma, dbeta, dbias};
-    for (int i = 0; i < 3; ++i)
-        if (outs[i])
-            hipLaunchKernelGGL(p3_colsum_fold_kernel, dim3((unsigned)gte::ceil_div(n, 256)), dim3(256), 0, s, p.ln_part + i * n,
-                               (long long)3 * n, nb, (int)n, outs[i]);
-    return gte::check_launch("gemm_p3_nt_ln_bwd fold");
+    return gte::gemm_p3_nt_ln_bwd({a1, lda1, k1, a2, lda2, k2, b, ldb, nullptr, 0}, z, ldz, stats, gamma, beta, relu, dz, lddz, dzp3, ldp3,
+                                  dgamma, dbeta, dbias, m, n, workspace, workspace_bytes, stream);
 }
 
 // ---- the NT product with LayerNorm(+ReLU) FORWARD as its epilogue ------------------------------------------------------------
 // z = [a1 | a2] b^T + bias (m x n, n <= 256: a workgroup's tile holds whole rows) is written as fp32 (the operand of the layer's
 // LayerNorm backward), and the workgroup that computed a row block normalises it: stats (mean, rstd), y = relu?(LN(z)) as fp32
 // (nullable) and as a P3 image (nullable).  Bit-identical to gte_gemm_p3_nt + gte_ln_relu_fwd_p3 (one launch, the z read-back and
-// the LayerNorm launch gone).  Rows of z / y padded to a multiple of 4 floats.
-static int gemm_p3_nt_ln_fwd_impl(const void* a1, int64_t lda1, int64_t k1, const void* a2, int64_t lda2, int64_t k2, const int32_t* a_rows,
-                                  int64_t n_res_rows, const void* b, int64_t ldb, const float* bias, const float* gamma,
-                                  const float* beta, float eps, int relu, float* z, int64_t ldz, float* y, int64_t ldy, void* yp3,
-                                  int64_t ldyp3, float* stats, int64_t m, int64_t n, void* stream) {
-    if (m < 0 || n <= 0 || n > 256 || k1 <= 0 || k2 < 0 || m > INT32_MAX || k1 > INT32_MAX || k2 > INT32_MAX)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_fwd: bad sizes (n <= 256)");
-    if (m == 0) return GTE_OK;
-    if (!a1 || !b || !z || !gamma || !beta || (!y && !yp3) || (k2 > 0 && !a2))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_fwd: null pointer");
-    const int64_t kb1 = p3::blocks(k1), kb2 = k2 > 0 ? p3::blocks(k2) : 0, n4 = gte::round_up(n, 4);
-    const P3Strides sb = p3_strides(ldb);
-    if (lda1 < kb1 * 96 || (k2 > 0 && lda2 < kb2 * 96) || !p3_strides_ok(ldb, n, 16 * (kb1 + kb2)) || ldz < n4 || (y && ldy < n4) ||
-        (yp3 && (ldyp3 < p3::row_bytes(n) || ldyp3 % 16 != 0)))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_fwd: leading dimension too small (rows of z / y padded to 4 floats)");
-    if (lda1 >= (1 << 22) || lda2 >= (1 << 22) || sb.ld >= (1 << 22))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_ln_fwd: row strides must be < 4 MB");
+// the LayerNorm launch gone).  Rows of z / y padded to a multiple of 4 floats.  Resident images of 4 GB or more: 64-bit per-lane
+// addresses.
+int gte::gemm_p3_nt_ln_fwd(const P3NtOperands& op, const float* bias, const float* gamma, const float* beta, float eps, int relu, float* z,
+                           int64_t ldz, float* y, int64_t ldy, void* yp3, int64_t ldyp3, float* stats, int64_t m, int64_t n, void* stream,
+                           const char* name) {
+    const int64_t n4 = gte::round_up(n, 4);
+    NtLimits lim = {};
+    lim.max_ld = 1 << 22; lim.rows_ok = true;
+    lim.own_sizes = n <= 0 || n > 256 || op.k1 > INT32_MAX || op.k2 > INT32_MAX;
+    lim.own_null = !z || !gamma || !beta || (!y && !yp3);
+    lim.own_ld = ldz < n4 || (y && ldy < n4) || (yp3 && (ldyp3 < p3::row_bytes(n) || ldyp3 % 16 != 0));      // (rows of z / y padded to 4 floats)
     P3Gemm p = {};
-    p.A1 = (const char*)a1; p.lda1 = lda1; p.KB1 = (int)kb1;
-    p.A2 = k2 > 0 ? (const char*)a2 : nullptr; p.lda2 = lda2; p.KB2 = (int)kb2;
-    p.B = (const char*)b; p.ldb = sb.ld; p.C = z; p.ldc = ldz; p.bias = bias;
-    p.bsa1 = p.bsa2 = 96; p.bsb = sb.bs;
-    p.M = (int)m; p.N = (int)n; p.splits = 1;
+    const int rc = nt_prepare(name, op, m, n, lim, p);
+    if (rc != GTE_OK || p.M == 0) return rc;
+    p.C = z; p.ldc = ldz; p.bias = bias;
     p.ln_gamma = gamma; p.ln_beta = beta; p.ln_relu = relu;
     p.lnf_y = y; p.lnf_ldy = ldy; p.lnf_yp3 = reinterpret_cast<char*>(yp3); p.lnf_ldp = ldyp3; p.lnf_stats = stats; p.lnf_eps = eps;
-    if (a_rows) {
-        if (n_res_rows <= 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_ln_fwd: empty resident image");
-        p.rowsA = a_rows; p.res_bytes = n_res_rows * lda1;
-        if (k2 > 0) { p.rows_both = 1; p.res_bytes2 = n_res_rows * lda2; }
-        p.rows64 = (rows64_needed(p.res_bytes) || (k2 > 0 && rows64_needed(p.res_bytes2))) ? 1 : 0;
-    }
-    if (p.rows64)                                          // images of 4 GB or more: 64-bit per-lane addresses (no range check: the
-        launch_lw_lnb<2, 4, 2, 2, 4, 4, true>(p, gte::as_stream(stream));                    // rows past the tile re-read its first row)
-    else if (sq_applies(p)) {                              // block-major weights: fragments straight to registers, 64-deep A slots
-        const int bm = lnb_row_tile(m);
-        if (bm == 32) launch_sq<1, 4, 4>(p, gte::as_stream(stream));
-        else if (bm == 64) launch_sq<2, 4, 4>(p, gte::as_stream(stream));
-        else if (bm == 96) launch_sq<3, 4, 4>(p, gte::as_stream(stream));
-        else launch_sq<4, 4, 4>(p, gte::as_stream(stream));
-    } else if (lnb_row_tile(m) == 32) launch_lw_lnb<1, 8, 1, 1, 4, 4>(p, gte::as_stream(stream));
-    else if (lnb_row_tile(m) == 64) launch_lw_lnb<1, 8, 2, 1, 4, 4>(p, gte::as_stream(stream));
-    else if (lnb_row_tile(m) == 96) launch_lw_lnb<1, 8, 3, 1, 4, 4>(p, gte::as_stream(stream));
-    else launch_lw_lnb<2, 4, 2, 2, 4, 4>(p, gte::as_stream(stream));
+    launch_one_column<4>(p, nt_pick(p, 4), gte::as_stream(stream));
     return gte::check_launch("gemm_p3_nt_ln_fwd");
 }
 extern "C" int gte_gemm_p3_nt_ln_fwd_supported(int64_t n) { return (n >= 1 && n <= 256) ? 1 : 0; }
@@ -2011,7 +2005,7 @@ extern "C" int gte_gemm_p3_nt_ln_fwd(const void* a1, int64_t lda1, int64_t k1, c
                                      int64_t ldb, const float* bias, const float* gamma, const float* beta, float eps, int relu, float* z,
                                      int64_t ldz, float* y, int64_t ldy, void* yp3, int64_t ldyp3, float* stats, int64_t m, int64_t n,
                                      void* stream) {
-    return gemm_p3_nt_ln_fwd_impl(a1, lda1, k1, a2, lda2, k2, nullptr, 0, b, ldb, bias, gamma, beta, eps, relu, z, ldz, y, ldy, yp3, ldyp3,
+    return gte::gemm_p3_nt_ln_fwd({a1, lda1, k1, a2, lda2, k2, b, ldb, nullptr, 0}, bias, gamma, beta, eps, relu, z, ldz, y, ldy, yp3, ldyp3,
                                   stats, m, n, stream);
 }
 // ... with [A | A2] = the rows a_rows[0 .. m) of two resident images of k columns each (gte_gemm_p3_nt_rows2): the whole forward of
@@ -2021,8 +2015,8 @@ extern "C" int gte_gemm_p3_nt_rows2_ln_fwd(const void* a_res, int64_t ldpa, cons
                                            const float* gamma, const float* beta, float eps, int relu, float* z, int64_t ldz, float* y,
                                            int64_t ldy, void* yp3, int64_t ldyp3, float* stats, int64_t m, int64_t n, void* stream) {
     if (!a_rows || !a2_res) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_rows2_ln_fwd: null row map / second image");
-    return gemm_p3_nt_ln_fwd_impl(a_res, ldpa, k, a2_res, ldpa2, k, a_rows, n_res_rows, b, ldb, bias, gamma, beta, eps, relu, z, ldz, y, ldy,
-                                  yp3, ldyp3, stats, m, n, stream);
+    return gte::gemm_p3_nt_ln_fwd({a_res, ldpa, k, a2_res, ldpa2, k, b, ldb, a_rows, n_res_rows}, bias, gamma, beta, eps, relu, z, ldz, y, ldy,
+                                  yp3, ldyp3, stats, m, n, stream, "gemm_p3_nt_rows2_ln_fwd");
 }
 
 // ---- ... with the WHOLE backward of a short-input layer below (gte_sage_smallk_bwd) as its epilogue --------------------------
@@ -2037,73 +2031,54 @@ extern "C" int64_t gte_gemm_p3_nt_smallk_bwd_workspace_bytes(int64_t m, int64_t 
 // bias)); it is not stored: the workgroup that computed a row block recomputes z from the k1 + k2 <= 28 inputs per row, runs the
 // LayerNorm(+ReLU) backward and accumulates dW = dz^T [x | ahn]; dW / dbias / dgamma / dbeta join the fold deferral.  Replaces
 // gte_gemm_p3_nt + gte_sage_smallk_bwd (one launch, the 2 m n 4 bytes of the dy round trip).
-extern "C" int gte_gemm_p3_nt_smallk_bwd(const void* a1, int64_t lda1, int64_t kg1, const void* a2, int64_t lda2, int64_t kg2,
-                                         const void* b, int64_t ldb, const float* x, int64_t ldx, int64_t k1, const float* ahn,
-                                         int64_t ldahn, int64_t k2, const float* W, int64_t ldw, const float* bias, const float* gamma,
-                                         const float* beta, const float* stats, int relu, float* dW, int64_t lddw, float* dbias,
-                                         float* dgamma, float* dbeta, int64_t m, int64_t n, void* workspace, int64_t workspace_bytes,
-                                         void* stream) {
-    if (m < 0 || n <= 0 || kg1 <= 0 || kg2 < 0 || k1 <= 0 || k2 < 0 || m > INT32_MAX || kg1 > INT32_MAX || kg2 > INT32_MAX)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_smallk_bwd: bad sizes");
+int gte::gemm_p3_nt_smallk_bwd(const P3NtOperands& op, const float* x, int64_t ldx, int64_t k1, const float* ahn, int64_t ldahn, int64_t k2,
+                               const float* W, int64_t ldw, const float* bias, const float* gamma, const float* beta, const float* stats,
+                               int relu, float* dW, int64_t lddw, float* dbias, float* dgamma, float* dbeta, int64_t m, int64_t n,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    const char* name = "gemm_p3_nt_smallk_bwd";
     const int64_t K = k1 + k2;
-    if (!gte_gemm_p3_nt_smallk_bwd_supported(K, n))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_smallk_bwd: needs n <= 256, n %% 4 == 0, k1 + k2 <= 28");
-    if (m == 0) return GTE_OK;
-    if (!a1 || !b || !x || (k2 > 0 && !ahn) || !W || !bias || !gamma || !beta || !stats || !dW || !workspace || (kg2 > 0 && !a2))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_smallk_bwd: null pointer");
-    const int64_t kb1 = p3::blocks(kg1), kb2 = kg2 > 0 ? p3::blocks(kg2) : 0;
-    const P3Strides sb = p3_strides(ldb);
-    if (lda1 < p3::row_bytes(kg1) || (kg2 > 0 && lda2 < p3::row_bytes(kg2)) || !p3_strides_ok(ldb, n, 16 * (kb1 + kb2)) || ldx < k1 || (k2 > 0 && ldahn < k2) ||
-        ldw < K || lddw < K)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_nt_smallk_bwd: leading dimension too small");
-    if (lda1 >= (1 << 23) || lda2 >= (1 << 23) || sb.ld >= (1 << 23) || (m + 256) * lda1 >= ((int64_t)1 << 31) ||
-        (kg2 > 0 && (m + 256) * lda2 >= ((int64_t)1 << 31)))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_smallk_bwd: operand images must be < 2 GB with row strides < 8 MB");
+    NtLimits lim = {};
+    lim.max_ld = 1 << 23; lim.below_2gb = true;
+    lim.own_sizes = n <= 0 || k1 <= 0 || k2 < 0 || op.k1 > INT32_MAX || op.k2 > INT32_MAX;
+    lim.unsupported = gte_gemm_p3_nt_smallk_bwd_supported(K, n) ? nullptr : "needs n <= 256, n % 4 == 0, k1 + k2 <= 28";
+    lim.own_null = !x || (k2 > 0 && !ahn) || !W || !bias || !gamma || !beta || !stats || !dW || !workspace;
+    lim.own_ld = ldx < k1 || (k2 > 0 && ldahn < k2) || ldw < K || lddw < K;
+    P3Gemm p = {};
+    int rc = nt_prepare(name, op, m, n, lim, p);
+    if (rc != GTE_OK || p.M == 0) return rc;
     const int64_t need = gte_gemm_p3_nt_smallk_bwd_workspace_bytes(m, K, n);
     if (workspace_bytes < need)
-        return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "gemm_p3_nt_smallk_bwd: needs %lld workspace bytes, got %lld", (long long)need,
-                         (long long)workspace_bytes);
+        return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "%s: needs %lld workspace bytes, got %lld", name, (long long)need, (long long)workspace_bytes);
     const int bm = 128;       // (the 192-row tile's stage images are 2.5 KB short of the row slice + W^T + inputs)
     const int nb = (int)gte::ceil_div(m, bm);
-    P3Gemm p = {};
-    p.A1 = reinterpret_cast<const char*>(a1); p.lda1 = lda1; p.KB1 = (int)kb1;
-    p.A2 = kg2 > 0 ? reinterpret_cast<const char*>(a2) : nullptr; p.lda2 = lda2; p.KB2 = (int)kb2;
-    p.B = reinterpret_cast<const char*>(b); p.ldb = sb.ld;
-    p.bsa1 = p.bsa2 = 96; p.bsb = sb.bs;
-    p.M = (int)m; p.N = (int)n; p.splits = 1;
     p.ln_stats = stats; p.ln_gamma = gamma; p.ln_beta = beta; p.ln_relu = relu;
     p.sk_x = x; p.sk_ldx = ldx; p.sk_k1 = (int)k1; p.sk_ahn = k2 > 0 ? ahn : nullptr; p.sk_ldahn = ldahn; p.sk_k2 = (int)k2;
     p.sk_W = W; p.sk_ldw = ldw; p.sk_bias = bias;
     p.sk_part_dw = reinterpret_cast<float*>(workspace);
     p.ln_part = p.sk_part_dw + (int64_t)nb * n * K;
     hipStream_t s = gte::as_stream(stream);
-    {
-        constexpr int shm = 160 * 1024;                             // the 128 x 256 ring tile (3 x 40 KB) + room for the whole fp32 tile
-        static bool configured = false;
-        if (!configured) {
-            GTE_SET_LDS((gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>), shm);
-            configured = true;
-        }
-        hipLaunchKernelGGL((gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>), dim3((unsigned)nb), dim3(512), shm, s, p);
-    }
-    int rc = gte::check_launch("gemm_p3_nt_smallk_bwd");
+    constexpr int shm = 160 * 1024;                             // the 128 x 256 ring tile (3 x 40 KB) + room for the whole fp32 tile
+    static bool configured = false;
+    set_lds_once(configured, &gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>, shm);
+    hipLaunchKernelGGL((gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>), dim3((unsigned)nb), dim3(512), shm, s, p);
+    rc = gte::check_launch(name);
     if (rc != GTE_OK) return rc;
-    if (gte::defer_fold(p.sk_part_dw, n * K, nb, (int)n, (int)K, dW, lddw)) {
-        gte::defer_fold(p.ln_part, 3 * n, nb, 1, (int)n, dgamma, n);
-        gte::defer_fold(p.ln_part + n, 3 * n, nb, 1, (int)n, dbeta, n);
-        gte::defer_fold(p.ln_part + 2 * n, 3 * n, nb, 1, (int)n, dbias, n);
-        return GTE_OK;
+    if (!gte::defer_fold(p.sk_part_dw, n * K, nb, (int)n, (int)K, dW, lddw)) {
+        // (no deferral open: fold here; dW is written packed, lddw == K)
+        if (lddw != K) return gte::fail(GTE_ERR_UNSUPPORTED, "%s: outside a fold deferral dW must be packed (lddw == k1 + k2)", name);
+        hipLaunchKernelGGL(p3_colsum_fold_kernel, dim3((unsigned)gte::ceil_div(n * K, 256)), dim3(256), 0, s, p.sk_part_dw, (long long)n * K,
+                           nb, (int)(n * K), dW);
     }
-    // (no deferral open: fold here; dW is written packed, lddw == K)
-    if (lddw != K) return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_nt_smallk_bwd: outside a fold deferral dW must be packed (lddw == k1 + k2)");
-    hipLaunchKernelGGL(p3_colsum_fold_kernel, dim3((unsigned)gte::ceil_div(n * K, 256)), dim3(256), 0, s, p.sk_part_dw, (long long)n * K, nb,
-                       (int)(n * K), dW);
-    float* outs[3] = {dgamma, dbeta, dbias};
-    for (int i = 0; i < 3; ++i)
-        if (outs[i])
-            hipLaunchKernelGGL(p3_colsum_fold_kernel, dim3((unsigned)gte::ceil_div(n, 256)), dim3(256), 0, s, p.ln_part + i * n,
-                               (long long)3 * n, nb, (int)n, outs[i]);
-    return gte::check_launch("gemm_p3_nt_smallk_bwd fold");
+    return fold_ln_partials("gemm_p3_nt_smallk_bwd fold", p.ln_part, n, nb, dgamma, dbeta, dbias, s);
+}
+extern "C" int gte_gemm_p3_nt_smallk_bwd(const void* a1, int64_t lda1, int64_t kg1, const void* a2, int64_t lda2, int64_t kg2,
+                                         const void* b, int64_t ldb, const float* x, int64_t ldx, int64_t k1, const float* ahn,
+                                         int64_t ldahn, int64_t k2, const float* W, int64_t ldw, const float* bias, const float* gamma,
+                                         const float* beta, const float* stats, int relu, float* dW, int64_t lddw, float* dbias,
+                                         float* dgamma, float* dbeta, int64_t m, int64_t n, void* workspace, int64_t workspace_bytes,
+                                         void* stream) {
+    return gte::gemm_p3_nt_smallk_bwd({a1, lda1, kg1, a2, lda2, kg2, b, ldb, nullptr, 0}, x, ldx, k1, ahn, ldahn, k2, W, ldw, bias, gamma, beta,
+                                      stats, relu, dW, lddw, dbias, dgamma, dbeta, m, n, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t gte_gemm_p3_tn_workspace_bytes(int64_t m, int64_t n, int64_t nseg, int64_t k) {
@@ -2111,13 +2086,6 @@ extern "C" int64_t gte_gemm_p3_tn_workspace_bytes(int64_t m, int64_t n, int64_t 
     const TnPlan pl = tn_plan(m, n, nseg, k);
     return pl.splits_bound > 1 ? gte::round_up((int64_t)pl.splits_bound * m * n * 4, 256) : 256;
 }
-
-// C[m, n] = a^T b over k rows: a = P3 [k][m], b = P3 [k][n].  nseg > 0: two column segments of nseg columns (n == 2 nseg),
-// C[:, 0:nseg] = a^T b, C[:, nseg:] = a2^T b2 (a2 / b2 nullable: the operand of segment 0).  The split-K fold joins an open
-// fold deferral (gte_fold_defer_begin), else it runs as its own launch.
-extern "C" int gte_gemm_p3_tn(const void* a, int64_t lda, const void* a2, int64_t lda2, const void* b, int64_t ldb, const void* b2,
-                              int64_t ldb2, int64_t nseg, float* c, int64_t ldc, int64_t m, int64_t n, int64_t k, void* workspace,
-                              int64_t workspace_bytes, void* stream);
 
 namespace {
 __global__ void __launch_bounds__(256)
@@ -2131,53 +2099,53 @@ p3_fold_kernel(const float* __restrict__ slab, int splits, long long mn, int N, 
 }
 }  // namespace
 
-static int gemm_p3_tn_impl(const void* a, int64_t lda, const void* a2, int64_t lda2, const void* b, int64_t ldb, const void* b2,
-                           int64_t ldb2, int64_t nseg, float* c, int64_t ldc, int64_t m, int64_t n, int64_t k, void* workspace,
-                           int64_t workspace_bytes, void* stream, const int32_t* b_rows, int64_t n_res_rows) {
+// C[m, n] = a^T b over k rows: a = P3 [k][m], b = P3 [k][n].  nseg > 0: two column segments of nseg columns (n == 2 nseg),
+// C[:, 0:nseg] = a^T b, C[:, nseg:] = a2^T b2 (a2 / b2 nullable: the operand of segment 0).  The split-K fold joins an open
+// fold deferral (gte_fold_defer_begin), else it runs as its own launch.
+int gte::gemm_p3_tn(const P3TnOperands& o, float* c, int64_t ldc, int64_t m, int64_t n, int64_t k, void* workspace, int64_t workspace_bytes,
+                    void* stream, const char* name) {
+    const int64_t nseg = o.nseg;
     if (m <= 0 || n <= 0 || k < 0 || nseg < 0 || m > INT32_MAX || n > INT32_MAX || k > INT32_MAX || (nseg > 0 && n != 2 * nseg))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_tn: bad sizes");
-    if (!a || !b || !c) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_tn: null pointer");
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: bad sizes", name);
+    if (!o.a || !o.b || !c) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: null pointer", name);
     const int64_t bcols = nseg > 0 ? nseg : n;
-    if (lda < p3::row_bytes(m) || ldb < p3::row_bytes(bcols) || (a2 && lda2 < p3::row_bytes(m)) || (b2 && ldb2 < p3::row_bytes(bcols)) ||
-        ldc < n)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_tn: leading dimension too small");
-    if (lda >= (1 << 23) || ldb >= (1 << 23) || lda2 >= (1 << 23) || ldb2 >= (1 << 23) || (m + 128) * n * 4 >= ((int64_t)1 << 31) ||
+    if (o.lda < p3::row_bytes(m) || o.ldb < p3::row_bytes(bcols) || (o.a2 && o.lda2 < p3::row_bytes(m)) ||
+        (o.b2 && o.ldb2 < p3::row_bytes(bcols)) || ldc < n)
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: leading dimension too small", name);
+    if (o.lda >= (1 << 23) || o.ldb >= (1 << 23) || o.lda2 >= (1 << 23) || o.ldb2 >= (1 << 23) || (m + 128) * n * 4 >= ((int64_t)1 << 31) ||
         (m + 128) * ldc * 4 >= ((int64_t)1 << 31))
-        return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_tn: row strides must be < 8 MB and the output < 2 GB");
+        return gte::fail(GTE_ERR_UNSUPPORTED, "%s: row strides must be < 8 MB and the output < 2 GB", name);
     hipStream_t s = gte::as_stream(stream);
     if (k == 0) {
         for (int64_t r = 0; r < m; ++r)
-            if (hipMemsetAsync(c + r * ldc, 0, (size_t)n * 4, s) != hipSuccess) return gte::fail(GTE_ERR_LAUNCH, "gemm_p3_tn: memset failed");
+            if (hipMemsetAsync(c + r * ldc, 0, (size_t)n * 4, s) != hipSuccess) return gte::fail(GTE_ERR_LAUNCH, "%s: memset failed", name);
         return GTE_OK;
     }
     const TnPlan pl = tn_plan(m, n, nseg, k);
     P3Gemm p = {};
-    p.A1 = (const char*)a; p.lda1 = lda; p.An2 = (const char*)a2; p.ldan2 = lda2;
-    p.B = (const char*)b; p.ldb = ldb; p.Bn2 = (const char*)b2; p.ldbn2 = ldb2;
+    p.A1 = (const char*)o.a; p.lda1 = o.lda; p.An2 = (const char*)o.a2; p.ldan2 = o.lda2;
+    p.B = (const char*)o.b; p.ldb = o.ldb; p.Bn2 = (const char*)o.b2; p.ldbn2 = o.ldb2;
     p.Nseg = (int)nseg; p.M = (int)m; p.N = (int)n; p.K = (int)k; p.C = c; p.ldc = ldc;
     p.splits = pl.splits; p.stages_per_split = pl.stages_per_split;
-    if (b_rows) {
-        if (b2 && ldb2 != ldb) return gte::fail(GTE_ERR_UNSUPPORTED, "gemm_p3_tn_rows: both resident images need the same row stride");
-        if (n_res_rows <= 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_tn_rows: empty resident image");
-        p.rowsB = b_rows; p.res_bytes = n_res_rows * ldb;
-        p.rows64 = rows64_needed((n_res_rows + 1) * ldb);
+    if (o.rows) {
+        if (o.b2 && o.ldb2 != o.ldb) return gte::fail(GTE_ERR_UNSUPPORTED, "%s: both resident images need the same row stride", name);
+        if (o.n_res_rows <= 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: empty resident image", name);
+        p.rowsB = o.rows; p.res_bytes = o.n_res_rows * o.ldb;
+        p.rows64 = rows64_needed((o.n_res_rows + 1) * o.ldb);
     }
     if (pl.splits > 1) {
         const int64_t need = (int64_t)pl.splits * m * n * 4;
         if (!workspace || workspace_bytes < need)
-            return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "gemm_p3_tn: split-K needs %lld workspace bytes, got %lld", (long long)need,
+            return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "%s: split-K needs %lld workspace bytes, got %lld", name, (long long)need,
                              (long long)workspace_bytes);
         p.slab = reinterpret_cast<float*>(workspace);
     }
     const int64_t tiles = gte::ceil_div(m, 128) * (nseg > 0 ? 2 * gte::ceil_div(nseg, 128) : gte::ceil_div(n, 128));
     constexpr int shm_small = 3 * 6 * 4 * 1024;
-    static bool configured = false;
-    if (!configured) {
-        GTE_SET_LDS((gemm_p3_tn_kernel<2, 2, 2>), shm_small);
-        GTE_SET_LDS((gemm_p3_tn_kernel<2, 2, 2, true>), shm_small);
-        GTE_SET_LDS((gemm_p3_tn_kernel<2, 2, 2, true, true>), shm_small);
-        configured = true;
-    }
+    static bool configured[3] = {};
+    set_lds_once(configured[0], &gemm_p3_tn_kernel<2, 2, 2>, shm_small);
+    set_lds_once(configured[1], &gemm_p3_tn_kernel<2, 2, 2, true>, shm_small);
+    set_lds_once(configured[2], &gemm_p3_tn_kernel<2, 2, 2, true, true>, shm_small);
     const dim3 grid((unsigned)(tiles * pl.splits));
     if (p.rowsB && p.rows64) hipLaunchKernelGGL((gemm_p3_tn_kernel<2, 2, 2, true, true>), grid, dim3(256), shm_small, s, p);
     else if (p.rowsB) hipLaunchKernelGGL((gemm_p3_tn_kernel<2, 2, 2, true>), grid, dim3(256), shm_small, s, p);
@@ -2194,19 +2162,18 @@ static int gemm_p3_tn_impl(const void* a, int64_t lda, const void* a2, int64_t l
 extern "C" int gte_gemm_p3_tn(const void* a, int64_t lda, const void* a2, int64_t lda2, const void* b, int64_t ldb, const void* b2,
                               int64_t ldb2, int64_t nseg, float* c, int64_t ldc, int64_t m, int64_t n, int64_t k, void* workspace,
                               int64_t workspace_bytes, void* stream) {
-    return gemm_p3_tn_impl(a, lda, a2, lda2, b, ldb, b2, ldb2, nseg, c, ldc, m, n, k, workspace, workspace_bytes, stream, nullptr, 0);
+    return gte::gemm_p3_tn({a, lda, a2, lda2, b, ldb, b2, ldb2, nseg, nullptr, 0}, c, ldc, m, n, k, workspace, workspace_bytes, stream);
 }
 
-// ... with b = the rows b_rows[0 .. k) of a RESIDENT P3 image b_res [n_res_rows][.] (the input layer's dW straight from the
-// resident features).  b_rows must hold k rounded up to 16, plus 1, entries; the entries past k = n_res_rows (a row past the
-// image: zeros).  Both column segments read the same image.  An image of 4 GB or more is read through 64-bit addresses without a
-// range check: row n_res_rows must then exist in the allocation and hold zeros.
+// ... with b = the rows b_rows[0 .. k) of a RESIDENT image (the input layer's dW straight from the resident features).  b_rows holds
+// k rounded up to 16, plus 1, entries; those past k = n_res_rows (a row past the image: zeros; an image of 4 GB or more is read
+// through 64-bit addresses without a range check: that row must then exist and hold zeros).  Both column segments read the image.
 extern "C" int gte_gemm_p3_tn_rows(const void* a, int64_t ldpa, const void* a2, int64_t ldpa2, const void* b_res, int64_t ldpb,
                                    const int32_t* b_rows, int64_t n_res_rows, int64_t nseg, float* c, int64_t ldc, int64_t m, int64_t n,
                                    int64_t k, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!b_rows) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_tn_rows: null row map");
-    return gemm_p3_tn_impl(a, ldpa, a2, ldpa2, b_res, ldpb, nullptr, 0, nseg, c, ldc, m, n, k, workspace, workspace_bytes, stream, b_rows,
-                           n_res_rows);
+    return gte::gemm_p3_tn({a, ldpa, a2, ldpa2, b_res, ldpb, nullptr, 0, nseg, b_rows, n_res_rows}, c, ldc, m, n, k, workspace, workspace_bytes,
+                           stream, "gemm_p3_tn_rows");
 }
 
 // ... with TWO resident images behind the map: C[:, 0:nseg] = a^T b_res[rows], C[:, nseg:] = a^T b2_res[rows] (the input features
@@ -2215,6 +2182,6 @@ extern "C" int gte_gemm_p3_tn_rows2(const void* a, int64_t ldpa, const void* b_r
                                     const int32_t* b_rows, int64_t n_res_rows, int64_t nseg, float* c, int64_t ldc, int64_t m, int64_t n,
                                     int64_t k, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!b_rows || !b2_res || nseg <= 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "gemm_p3_tn_rows2: null row map / second image, or nseg <= 0");
-    return gemm_p3_tn_impl(a, ldpa, nullptr, 0, b_res, ldpb, b2_res, ldpb2, nseg, c, ldc, m, n, k, workspace, workspace_bytes, stream, b_rows,
-                           n_res_rows);
+    return gte::gemm_p3_tn({a, ldpa, nullptr, 0, b_res, ldpb, b2_res, ldpb2, nseg, b_rows, n_res_rows}, c, ldc, m, n, k, workspace,
+                           workspace_bytes, stream, "gemm_p3_tn_rows2");
 }

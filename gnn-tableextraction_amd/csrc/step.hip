@@ -6,6 +6,7 @@
 // Python through ctypes each costs ~10 us of interpreter + marshalling, which bounded the BBOX-only configurations (F0 = 13:
 // ~0.25 ms of host time per 0.37 ms step).
 #include "gte_common.h"
+#include "gemm_p3_host.h"
 
 #include <stdlib.h>
 
@@ -46,6 +47,26 @@ bool layer_wide(const gte_step_plan& p, int i) {
     return (p.n_nodes + 256) * 2 * ld * 4 >= ((int64_t)1 << 31);
 }
 
+// What a hidden layer multiplies, stated ONCE for its forward and its weight gradient: the image of its input h -- and, unless the
+// layer aggregates AFTER the transform (GTE_LAYER_PLANES), of h's mean aggregate next to it -- made per batch, or RESIDENT and read
+// through the batch's row map h_rows (a dropout layer's producer has followed the map already: its images are the batch's own)
+inline bool two_images(const gte_step_layer& L) { return L.kind != GTE_LAYER_PLANES; }
+inline const int32_t* rows_of(const gte_step_layer& L) { return (L.kind == GTE_LAYER_PLANES || L.kind == GTE_LAYER_CACHED) ? L.h_rows : nullptr; }
+// forward: [h | ahn] W^T (PLANES: h [W_s ; W_n]^T)
+inline gte::P3NtOperands fwd_operands(const gte_step_layer& L) {
+    const bool two = two_images(L);
+    return {L.hp, L.ldp_h, L.fin, two ? L.ahnp : nullptr, two ? L.ldp_ahn : 0, two ? L.fin : 0, L.wimg_fwd, L.ldp_wfwd, rows_of(L), L.n_res_rows};
+}
+// weight gradient: dW = [dz^T h | dz^T ahn] (PLANES: [dz^T h | q^T h]), two column segments of one TN product
+inline gte::P3TnOperands dw_operands(const gte_step_layer& L) {
+    const bool two = two_images(L);
+    return {L.dzp, L.ldp_o, two ? nullptr : L.qp, two ? 0 : L.ldp_o, L.hp, L.ldp_h, two ? L.ahnp : nullptr, two ? L.ldp_ahn : 0, L.fin,
+            rows_of(L), L.n_res_rows};
+}
+inline int layer_dw(const gte_step_layer& L, int64_t n, void* st) {
+    return gte::gemm_p3_tn(dw_operands(L), L.gW, 2 * L.fin, L.fout, 2 * L.fin, n, L.ws_dw, L.ws_dw_bytes, st);
+}
+
 // weight images + the hidden layers (the output layer's input is p.h_out / p.hp_out afterwards).  fwd_only: nothing is kept for a
 // backward -- a planes layer whose output is consumed as an image (by the next planes layer, or by the output layer's GEMM) does
 // not write its fp32 rows (a sixth of the aggregation + LayerNorm kernel's bytes)
@@ -82,68 +103,38 @@ int forward_hidden(const gte_step_plan& p, void* st, bool fwd_only = false) {
                                             L.fout, L.stats, L.y, L.fout, n, L.fout, st));
             continue;
         }
-        if (L.kind == GTE_LAYER_AGGFIRST || L.kind == GTE_LAYER_DROPOUT) {
+        if (two_images(L)) {
             // z = [x | mean-aggregate(x)] W^T + b on the planes GEMM (two K segments), then LayerNorm + ReLU: the input layer of a
             // model whose hidden width exceeds its input width (aggregating fin columns is the cheaper order, models.py:53-72).
-            // A dropout layer: both operand images with the layer's mask (and, layer 0, the input dropout) from ONE producer
+            // A dropout layer: both operand images with the layer's mask (and, layer 0, the input dropout) from ONE producer.
+            // A cached layer: x AND its aggregate are RESIDENT images behind the batch's row map (the aggregate of the input is
+            // page-local and constant: cached when the pages were loaded; h_rows == NULL: the images hold the graph's own rows -- a
+            // graph that is evaluated again and again, e.g. the validation graph of train(), with its images made once)
             if (L.kind == GTE_LAYER_DROPOUT) {
                 GTE_TRY(gte_spmm_dropout_p3(p.indptr, p.indices, p.w_in, L.x, L.ldx, L.xp, L.ldp_x, L.h_rows, L.n_res_rows, i == 0,
                                             p.dropout_p, p.dropout_seed, p.rank, p.step_counter, i + 1, L.hp, L.ldp_h, L.ahnp,
                                             L.ldp_ahn, n, L.fin, st));
-            } else {
+            } else if (L.kind == GTE_LAYER_AGGFIRST) {
                 GTE_TRY(gte_p3_from_f32(L.x, L.ldx, n, L.fin, 0, L.hp, L.ldp_h, st));
                 GTE_TRY(gte_spmm_csr_p3(p.indptr, p.indices, p.w_in, L.x, L.ldx, L.ahnp, L.ldp_ahn, n, L.fin, GTE_REDUCE_MEAN, st));
             }
             mark(2 * i);
-            if ((p.fuse_ln_dx & 16) && gte_gemm_p3_nt_ln_fwd_supported(L.fout)) {      // LayerNorm + ReLU as the GEMM's epilogue
-                GTE_TRY(gte_gemm_p3_nt_ln_fwd(L.hp, L.ldp_h, L.fin, L.ahnp, L.ldp_ahn, L.fin, L.wimg_fwd, L.ldp_wfwd, L.bias, L.gamma, L.beta,
-                                              L.eps, L.relu, L.t, ld, L.y, ld, L.yp, L.ldp_y, L.stats, n, L.fout, st));
+            float* const y = (L.kind == GTE_LAYER_CACHED && L.yp && (fwd_only || y_unread(i))) ? nullptr : L.y;
+            if ((p.fuse_ln_dx & 16) && gte_gemm_p3_nt_ln_fwd_supported(L.fout)) {      // LayerNorm + ReLU as the GEMM's epilogue: ONE launch
+                GTE_TRY(gte::gemm_p3_nt_ln_fwd(fwd_operands(L), L.bias, L.gamma, L.beta, L.eps, L.relu, L.t, ld, y, ld, L.yp, L.ldp_y, L.stats, n,
+                                               L.fout, st));
                 mark(2 * i + 1);
                 continue;
             }
-            GTE_TRY(gte_gemm_p3_nt(L.hp, L.ldp_h, L.fin, L.ahnp, L.ldp_ahn, L.fin, L.wimg_fwd, L.ldp_wfwd, L.bias, L.fout, L.t, ld, n, L.fout,
-                                   0, 0, st));
+            GTE_TRY(gte::gemm_p3_nt(fwd_operands(L), L.bias, L.fout, L.t, ld, n, L.fout, 0, 0, st));
             mark(2 * i + 1);
-            GTE_TRY(gte_ln_relu_fwd_p3(L.t, ld, L.gamma, L.beta, L.eps, L.relu, L.y, ld, L.yp, L.ldp_y, L.stats, n, L.fout, st));
-            continue;
-        }
-        if (L.kind == GTE_LAYER_CACHED) {
-            // z = [x | ahn] W^T + b with x AND its mean aggregate read from their RESIDENT images through the batch's row map (the
-            // aggregate of the input is page-local and constant: cached when the pages were loaded), then LayerNorm + ReLU
-            mark(2 * i);
-            float* const y3 = (L.yp && (fwd_only || y_unread(i))) ? nullptr : L.y;
-            // (h_rows == NULL: the two images hold the graph's own rows -- a graph that is evaluated again and again, e.g. the
-            // validation graph of train(), with its images made once)
-            if ((p.fuse_ln_dx & 16) && gte_gemm_p3_nt_ln_fwd_supported(L.fout)) {      // the layer's whole forward in ONE launch
-                if (L.h_rows)
-                    GTE_TRY(gte_gemm_p3_nt_rows2_ln_fwd(L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.h_rows, L.n_res_rows, L.wimg_fwd,
-                                                        L.ldp_wfwd, L.bias, L.gamma, L.beta, L.eps, L.relu, L.t, ld, y3, ld, L.yp, L.ldp_y,
-                                                        L.stats, n, L.fout, st));
-                else
-                    GTE_TRY(gte_gemm_p3_nt_ln_fwd(L.hp, L.ldp_h, L.fin, L.ahnp, L.ldp_ahn, L.fin, L.wimg_fwd, L.ldp_wfwd, L.bias, L.gamma,
-                                                  L.beta, L.eps, L.relu, L.t, ld, y3, ld, L.yp, L.ldp_y, L.stats, n, L.fout, st));
-                mark(2 * i + 1);
-                continue;
-            }
-            if (L.h_rows)
-                GTE_TRY(gte_gemm_p3_nt_rows2(L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.h_rows, L.n_res_rows, L.wimg_fwd, L.ldp_wfwd, L.bias,
-                                             L.fout, L.t, ld, n, L.fout, 0, 0, st));
-            else
-                GTE_TRY(gte_gemm_p3_nt(L.hp, L.ldp_h, L.fin, L.ahnp, L.ldp_ahn, L.fin, L.wimg_fwd, L.ldp_wfwd, L.bias, L.fout, L.t, ld, n,
-                                       L.fout, 0, 0, st));
-            mark(2 * i + 1);
-            GTE_TRY(gte_ln_relu_fwd_p3(L.t, ld, L.gamma, L.beta, L.eps, L.relu, y3, ld, L.yp, L.ldp_y, L.stats, n, L.fout, st));
+            GTE_TRY(gte_ln_relu_fwd_p3(L.t, ld, L.gamma, L.beta, L.eps, L.relu, y, ld, L.yp, L.ldp_y, L.stats, n, L.fout, st));
             continue;
         }
         if (L.make_hp) GTE_TRY(gte_p3_from_f32(L.x, L.ldx, n, L.fin, 0, L.hp, L.ldp_h, st));
         // t = [t_self | t_neigh], each half ld columns wide (the weight image holds zero rows behind the fout rows of a half)
         mark(2 * i);
-        if (L.h_rows)
-            GTE_TRY(gte_gemm_p3_nt_rows(L.hp, L.ldp_h, L.fin, L.h_rows, L.n_res_rows, L.wimg_fwd, L.ldp_wfwd, L.bias, L.fout, L.t, 2 * ld,
-                                        n, 2 * ld, 0, 0, st));
-        else
-            GTE_TRY(gte_gemm_p3_nt(L.hp, L.ldp_h, L.fin, nullptr, 0, 0, L.wimg_fwd, L.ldp_wfwd, L.bias, L.fout, L.t, 2 * ld, n,
-                                   2 * ld, 0, 0, st));
+        GTE_TRY(gte::gemm_p3_nt(fwd_operands(L), L.bias, L.fout, L.t, 2 * ld, n, 2 * ld, 0, 0, st));
         mark(2 * i + 1);
         float* const y = (L.yp && y_unread(i)) ? nullptr : L.y;
         GTE_TRY(gte_spmm_csr_accumulate_ln_p3(p.indptr, p.indices, p.w_in, L.t + ld, 2 * ld, L.t, 2 * ld, n, L.fout,
@@ -271,8 +262,7 @@ int backward_a(const gte_step_plan& p, void* st) {
             if (i == 0) break;                         // (dW = dz^T [D(x') | D(ahn')]: phase 2, as an aggregate-first layer 0)
             // dW = dz^T [self | agg] on the forward's images; G = dz W (both halves); dy of the layer below = the mask's backward of
             // G's self half + the transpose aggregation of its masked agg half (then the LayerNorm backward of that layer)
-            GTE_TRY(gte_gemm_p3_tn(L.dzp, L.ldp_o, nullptr, 0, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n,
-                                   L.ws_dw, L.ws_dw_bytes, st));
+            GTE_TRY(layer_dw(L, n, st));
             GTE_TRY(gte_gemm_p3_nt(L.dzp, L.ldp_o, L.fout, nullptr, 0, 0, L.wimg_bwd, L.ldp_wbwd, nullptr, 0, L.g, L.ldg, n, L.ldg, 0, 0, st));
             const gte_step_layer& B = p.layer[i - 1];
             GTE_TRY(gte_spmm_dropout_bwd(p.rindptr, p.rindices, p.w_out, L.g, L.ldg, L.ldg / 2, p.dropout_p, p.dropout_seed, p.rank,
@@ -318,20 +308,9 @@ int backward_b(const gte_step_plan& p, void* st) {
                                    L.relu, L.gW, 2 * L.fin, L.gbias, L.ggamma, L.gbeta, n, L.fout, L.ws_dw, L.ws_dw_bytes, st);
     if (L.kind == GTE_LAYER_SMALLK)
         return gte_sage_linear_dw(L.dy, L.fout, L.x, L.ldx, L.fin, L.ahn, L.fin, L.fin, L.gW, 2 * L.fin, L.fout, n, L.ws_dw, L.ws_dw_bytes, st);
-    if (L.kind == GTE_LAYER_CACHED && !L.h_rows)       // (the graph's own images: as the aggregate-first layer below)
-        return gte_gemm_p3_tn(L.dzp, L.ldp_o, nullptr, 0, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n,
-                              L.ws_dw, L.ws_dw_bytes, st);
-    if (L.kind == GTE_LAYER_CACHED)                    // dW = [dz^T x | dz^T ahn], both operands resident behind the row map
-        return gte_gemm_p3_tn_rows2(L.dzp, L.ldp_o, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.h_rows, L.n_res_rows, L.fin, L.gW, 2 * L.fin,
-                                    L.fout, 2 * L.fin, n, L.ws_dw, L.ws_dw_bytes, st);
-    if (L.kind == GTE_LAYER_AGGFIRST || L.kind == GTE_LAYER_DROPOUT)      // dW = [dz^T x | dz^T ahn] (dropout: the masked images)
-        return gte_gemm_p3_tn(L.dzp, L.ldp_o, nullptr, 0, L.hp, L.ldp_h, L.ahnp, L.ldp_ahn, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n,
-                              L.ws_dw, L.ws_dw_bytes, st);
-    if (L.h_rows)
-        return gte_gemm_p3_tn_rows(L.dzp, L.ldp_o, L.qp, L.ldp_o, L.hp, L.ldp_h, L.h_rows, L.n_res_rows, L.fin, L.gW, 2 * L.fin, L.fout,
-                                   2 * L.fin, n, L.ws_dw, L.ws_dw_bytes, st);
-    return gte_gemm_p3_tn(L.dzp, L.ldp_o, L.qp, L.ldp_o, L.hp, L.ldp_h, nullptr, 0, L.fin, L.gW, 2 * L.fin, L.fout, 2 * L.fin, n, L.ws_dw,
-                          L.ws_dw_bytes, st);
+    // dW on the forward's operands: [dz^T x | dz^T ahn] (cached: resident behind the row map; dropout: the masked images), a planes
+    // layer's [dz^T h | q^T h]
+    return layer_dw(L, n, st);
 }
 
 int flush(const gte_step_plan& p, int* adam_fused) {

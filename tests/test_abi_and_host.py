@@ -327,3 +327,174 @@ def test_no_kernel_of_the_library_spills():
     names = ru.demangle(list(table))
     p3 = [k for k in table if "gemm_p3_" in names[k]]
     assert p3 and all(table[k]["vgprs"] + table[k].get("agprs", 0) <= 512 for k in p3)
+
+
+# ---------------------------------------------------------------- the planes GEMMs' argument checks (no GPU)
+_P = 0x10000          # a dummy address: every call of the table returns before anything dereferences it or launches a kernel
+_L22, _L23 = 1 << 22, 1 << 23
+_P3_PARAMS = {
+    "gte_gemm_p3_nt": "a1 lda1 k1 a2 lda2 k2 b ldb bias bias_cols c ldc m n relu accumulate stream",
+    "gte_gemm_p3_nt_rows": "a_res ldpa k a_rows n_res_rows b ldpb bias bias_cols c ldc m n relu accumulate stream",
+    "gte_gemm_p3_nt_rows2": "a_res ldpa a2_res ldpa2 k a_rows n_res_rows b ldpb bias bias_cols c ldc m n relu accumulate stream",
+    "gte_gemm_p3_nt_ln_fwd": "a1 lda1 k1 a2 lda2 k2 b ldb bias gamma beta eps relu z ldz y ldy yp3 ldyp3 stats m n stream",
+    "gte_gemm_p3_nt_rows2_ln_fwd": "a_res ldpa a2_res ldpa2 k a_rows n_res_rows b ldb bias gamma beta eps relu z ldz y ldy yp3 ldyp3 "
+                                   "stats m n stream",
+    "gte_gemm_p3_nt_ln_bwd": "a1 lda1 k1 a2 lda2 k2 b ldb z ldz stats gamma beta relu dz lddz dzp3 ldp3 dgamma dbeta dbias m n "
+                             "workspace workspace_bytes stream",
+    "gte_gemm_p3_nt_smallk_bwd": "a1 lda1 kg1 a2 lda2 kg2 b ldb x ldx k1 ahn ldahn k2 W ldw bias gamma beta stats relu dW lddw dbias "
+                                 "dgamma dbeta m n workspace workspace_bytes stream",
+    "gte_gemm_p3_tn": "a lda a2 lda2 b ldb b2 ldb2 nseg c ldc m n k workspace workspace_bytes stream",
+    "gte_gemm_p3_tn_rows": "a ldpa a2 ldpa2 b_res ldpb b_rows n_res_rows nseg c ldc m n k workspace workspace_bytes stream",
+    "gte_gemm_p3_tn_rows2": "a ldpa b_res ldpb b2_res ldpb2 b_rows n_res_rows nseg c ldc m n k workspace workspace_bytes stream",
+}
+
+
+def _p3_valid_calls(lib):
+    """A VALID argument set per entry point (never issued as it stands: it would launch).  NT: m = 100, n = 64, K = 32 (two blocks:
+    192-byte rows; 384 with two segments); TN: m = n = 128 over k = 512 rows: four K splits on any device with two CUs or more."""
+    out = dict(bias=None, bias_cols=0, c=_P, ldc=64, m=100, n=64, relu=0, accumulate=0, stream=None)
+    ln_f = dict(bias=None, gamma=_P, beta=_P, eps=1e-5, relu=1, z=_P, ldz=64, y=_P, ldy=64, yp3=_P, ldyp3=384, stats=_P, m=100, n=64, stream=None)
+    seg1 = dict(a1=_P, lda1=192, k1=32, a2=None, lda2=0, k2=0, b=_P, ldb=192)
+    res2 = dict(a_res=_P, ldpa=192, a2_res=_P, ldpa2=192, k=32, a_rows=_P, n_res_rows=1000, b=_P)
+    tn_ws = 4 * 128 * 128 * 4
+    tn_out = dict(c=_P, ldc=128, m=128, n=128, k=512, workspace=_P, workspace_bytes=tn_ws, stream=None)
+    return {
+        "gte_gemm_p3_nt": dict(seg1, **out),
+        "gte_gemm_p3_nt_rows": dict(a_res=_P, ldpa=192, k=32, a_rows=_P, n_res_rows=1000, b=_P, ldpb=192, **out),
+        "gte_gemm_p3_nt_rows2": dict(res2, ldpb=384, **out),
+        "gte_gemm_p3_nt_ln_fwd": dict(seg1, **ln_f),
+        "gte_gemm_p3_nt_rows2_ln_fwd": dict(res2, ldb=384, **ln_f),
+        "gte_gemm_p3_nt_ln_bwd": dict(seg1, z=_P, ldz=64, stats=_P, gamma=_P, beta=_P, relu=1, dz=_P, lddz=64, dzp3=_P, ldp3=384, dgamma=_P,
+                                      dbeta=_P, dbias=_P, m=100, n=64, workspace=_P,
+                                      workspace_bytes=lib.gte_gemm_p3_nt_ln_bwd_workspace_bytes(100, 64), stream=None),
+        "gte_gemm_p3_nt_smallk_bwd": dict(a1=_P, lda1=192, kg1=32, a2=None, lda2=0, kg2=0, b=_P, ldb=192, x=_P, ldx=13, k1=13, ahn=_P, ldahn=13,
+                                          k2=13, W=_P, ldw=26, bias=_P, gamma=_P, beta=_P, stats=_P, relu=1, dW=_P, lddw=26, dbias=_P,
+                                          dgamma=_P, dbeta=_P, m=100, n=64, workspace=_P,
+                                          workspace_bytes=lib.gte_gemm_p3_nt_smallk_bwd_workspace_bytes(100, 26, 64), stream=None),
+        "gte_gemm_p3_tn": dict(a=_P, lda=768, a2=None, lda2=0, b=_P, ldb=768, b2=None, ldb2=0, nseg=0, **tn_out),
+        "gte_gemm_p3_tn_rows": dict(a=_P, ldpa=768, a2=None, ldpa2=0, b_res=_P, ldpb=768, b_rows=_P, n_res_rows=1000, nseg=0, **tn_out),
+        "gte_gemm_p3_tn_rows2": dict(a=_P, ldpa=768, b_res=_P, ldpb=384, b2_res=_P, ldpb2=384, b_rows=_P, n_res_rows=1000, nseg=64, **tn_out),
+    }
+
+
+def _p3_invalid_calls(lib):
+    """(entry point, what is wrong with the valid call, return code).  -1 invalid argument, -3 workspace too small, -4 unsupported,
+    0 nothing to do.  A call that passes a check it is meant to PASS (a stride one below the limit, the last row count below
+    2 GB) is wrong in a way that is only looked at later -- an empty resident image, a workspace one byte short -- so that it
+    still returns before a launch; the plain gte_gemm_p3_nt / _nt_ln_fwd have no later check, their limits are those of the
+    row-map forms, which run the same code."""
+    ln_ws, sk_ws = lib.gte_gemm_p3_nt_ln_bwd_workspace_bytes, lambda m: lib.gte_gemm_p3_nt_smallk_bwd_workspace_bytes(m, 26, 64)
+    tn_ws = 4 * 128 * 128 * 4
+    two = dict(k2=16, a2=_P, lda2=96, ldb=288)             # a second K segment of one block
+    nt, rows, rows2 = "gte_gemm_p3_nt", "gte_gemm_p3_nt_rows", "gte_gemm_p3_nt_rows2"
+    lnf, lnf2, lnb, sk = "gte_gemm_p3_nt_ln_fwd", "gte_gemm_p3_nt_rows2_ln_fwd", "gte_gemm_p3_nt_ln_bwd", "gte_gemm_p3_nt_smallk_bwd"
+    tn, tnr, tnr2 = "gte_gemm_p3_tn", "gte_gemm_p3_tn_rows", "gte_gemm_p3_tn_rows2"
+    t = []
+    # ---- gte_gemm_p3_nt
+    t += [(nt, dict(m=-1), -1), (nt, dict(n=-1), -1), (nt, dict(k1=0), -1), (nt, dict(k2=-1), -1), (nt, dict(m=1 << 31), -1),
+          (nt, dict(m=0, a1=None), 0), (nt, dict(n=0, c=None), 0),
+          (nt, dict(a1=None), -1), (nt, dict(b=None), -1), (nt, dict(c=None), -1), (nt, dict(two, a2=None), -1),
+          (nt, dict(lda1=191), -1), (nt, dict(two, lda2=95), -1), (nt, dict(ldb=176), -1), (nt, dict(ldb=-(64 * 96 - 16)), -1),
+          (nt, dict(ldc=63), -1),
+          (nt, dict(lda1=_L22), -4), (nt, dict(lda2=_L22), -4), (nt, dict(ldb=_L22), -4), (nt, dict(m=256, ldc=1 << 20), -4),
+          (nt, dict(lda1=191, ldb=_L22), -1), (nt, dict(c=None, lda1=_L22), -1), (nt, dict(m=-1, lda1=_L22), -1),
+          (nt, dict(m=0, lda1=_L22), 0)]
+    # ---- gte_gemm_p3_nt_rows / _rows2
+    t += [(rows, dict(a_rows=None), -1), (rows, dict(a_rows=None, ldpa=_L22), -1), (rows, dict(k=0), -1), (rows, dict(a_res=None), -1),
+          (rows, dict(ldpa=191), -1), (rows, dict(ldpb=176), -1), (rows, dict(ldpa=_L22), -4), (rows, dict(ldpa=_L22 - 1, n_res_rows=0), -1),
+          (rows, dict(ldpb=_L22), -4), (rows, dict(ldpb=_L22 - 16, n_res_rows=0), -1),
+          (rows, dict(m=256, ldc=1 << 20, n_res_rows=0), -4), (rows, dict(m=256, ldc=(1 << 20) - 1, n_res_rows=0), -1),
+          (rows, dict(n_res_rows=0), -1), (rows, dict(n_res_rows=-5), -1), (rows, dict(ldpa=_L22, n_res_rows=0), -4),
+          (rows, dict(m=0, n_res_rows=0), 0),
+          (rows2, dict(a_rows=None), -1), (rows2, dict(a2_res=None), -1), (rows2, dict(a2_res=None, ldpa=_L22), -1),
+          (rows2, dict(ldpa2=191), -1), (rows2, dict(ldpb=368), -1), (rows2, dict(ldpa2=_L22), -4),
+          (rows2, dict(ldpa2=_L22 - 1, n_res_rows=0), -1), (rows2, dict(n_res_rows=0), -1), (rows2, dict(ldpa=_L22, n_res_rows=0), -4)]
+    # ---- gte_gemm_p3_nt_ln_fwd / _rows2_ln_fwd
+    t += [(lnf, dict(m=-1), -1), (lnf, dict(n=0), -1), (lnf, dict(n=257, ldz=260, ldy=260, ldyp3=1632), -1), (lnf, dict(k1=0), -1),
+          (lnf, dict(k2=-1), -1), (lnf, dict(m=0, a1=None), 0),
+          (lnf, dict(a1=None), -1), (lnf, dict(b=None), -1), (lnf, dict(z=None), -1), (lnf, dict(gamma=None), -1), (lnf, dict(beta=None), -1),
+          (lnf, dict(y=None, yp3=None), -1), (lnf, dict(two, a2=None), -1),
+          (lnf, dict(lda1=191), -1), (lnf, dict(two, lda2=95), -1), (lnf, dict(ldb=176), -1), (lnf, dict(ldz=63), -1), (lnf, dict(ldy=63), -1),
+          (lnf, dict(n=62, ldz=63), -1), (lnf, dict(ldyp3=368), -1), (lnf, dict(ldyp3=392), -1),
+          (lnf, dict(lda1=_L22), -4), (lnf, dict(lda2=_L22), -4), (lnf, dict(ldb=_L22), -4),
+          (lnf, dict(n=257, lda1=_L22), -1), (lnf, dict(z=None, lda1=_L22), -1), (lnf, dict(ldz=63, ldb=_L22), -1),
+          (lnf2, dict(a_rows=None), -1), (lnf2, dict(a2_res=None), -1), (lnf2, dict(a_rows=None, ldpa=_L22), -1),
+          (lnf2, dict(n_res_rows=0), -1), (lnf2, dict(ldpa=_L22, n_res_rows=0), -4), (lnf2, dict(ldpa=_L22 - 1, n_res_rows=0), -1),
+          (lnf2, dict(ldpa2=_L22, n_res_rows=0), -4), (lnf2, dict(ldpa2=_L22 - 1, n_res_rows=0), -1),
+          (lnf2, dict(ldb=_L22 - 16, n_res_rows=0), -1), (lnf2, dict(z=None, n_res_rows=0), -1)]
+    # ---- gte_gemm_p3_nt_ln_bwd (its lda1 limit lies behind the 2 GB bound: 257 rows of 8 MB are more)
+    t += [(lnb, dict(m=-1), -1), (lnb, dict(n=0), -1), (lnb, dict(k1=0), -1), (lnb, dict(k2=-1), -1), (lnb, dict(n=257), -4),
+          (lnb, dict(n=257, m=0), -4), (lnb, dict(n=257, m=-1), -1), (lnb, dict(n=257, a1=None), -4), (lnb, dict(m=0, a1=None), 0),
+          (lnb, dict(a1=None), -1), (lnb, dict(b=None), -1), (lnb, dict(z=None), -1), (lnb, dict(stats=None), -1), (lnb, dict(gamma=None), -1),
+          (lnb, dict(beta=None), -1), (lnb, dict(dz=None, dzp3=None), -1), (lnb, dict(workspace=None), -1), (lnb, dict(two, a2=None), -1),
+          (lnb, dict(lda1=191), -1), (lnb, dict(two, lda2=95), -1), (lnb, dict(ldb=176), -1), (lnb, dict(ldz=63), -1), (lnb, dict(lddz=63), -1),
+          (lnb, dict(ldp3=368), -1), (lnb, dict(ldp3=392), -1),
+          (lnb, dict(lda1=_L23), -4), (lnb, dict(lda2=_L23), -4), (lnb, dict(lda2=_L23 - 1, workspace_bytes=ln_ws(100, 64) - 1), -3),
+          (lnb, dict(ldb=_L23), -4), (lnb, dict(ldb=_L23 - 16, workspace_bytes=ln_ws(100, 64) - 1), -3),
+          (lnb, dict(lda1=1 << 20, m=1792, workspace_bytes=ln_ws(1792, 64)), -4),
+          (lnb, dict(lda1=1 << 20, m=1791, workspace_bytes=ln_ws(1791, 64) - 1), -3),
+          (lnb, dict(two, lda2=1 << 20, m=1792, workspace_bytes=ln_ws(1792, 64)), -4),
+          (lnb, dict(two, lda2=1 << 20, m=1791, workspace_bytes=ln_ws(1791, 64) - 1), -3),
+          (lnb, dict(workspace_bytes=ln_ws(100, 64) - 1), -3), (lnb, dict(workspace_bytes=ln_ws(100, 64) - 1, ldb=_L23), -4),
+          (lnb, dict(workspace_bytes=ln_ws(100, 64) - 1, z=None), -1), (lnb, dict(ldz=63, ldb=_L23), -1)]
+    # ---- gte_gemm_p3_nt_smallk_bwd
+    t += [(sk, dict(m=-1), -1), (sk, dict(n=0), -1), (sk, dict(kg1=0), -1), (sk, dict(kg2=-1), -1), (sk, dict(k1=0), -1), (sk, dict(k2=-1), -1),
+          (sk, dict(k1=15, k2=14, ldx=15, ldahn=14, ldw=29, lddw=29), -4), (sk, dict(n=62), -4), (sk, dict(n=260), -4),
+          (sk, dict(n=62, a1=None), -4), (sk, dict(n=62, m=-1), -1), (sk, dict(n=62, m=0), -4), (sk, dict(m=0, a1=None), 0),
+          (sk, dict(a1=None), -1), (sk, dict(b=None), -1), (sk, dict(x=None), -1), (sk, dict(ahn=None), -1), (sk, dict(W=None), -1),
+          (sk, dict(bias=None), -1), (sk, dict(gamma=None), -1), (sk, dict(beta=None), -1), (sk, dict(stats=None), -1), (sk, dict(dW=None), -1),
+          (sk, dict(workspace=None), -1), (sk, dict(kg2=16, a2=None, lda2=96, ldb=288), -1),
+          (sk, dict(lda1=191), -1), (sk, dict(kg2=16, a2=_P, lda2=95, ldb=288), -1), (sk, dict(ldb=176), -1), (sk, dict(ldx=12), -1),
+          (sk, dict(ldahn=12), -1), (sk, dict(ldw=25), -1), (sk, dict(lddw=25), -1),
+          (sk, dict(lda1=_L23), -4), (sk, dict(lda2=_L23), -4), (sk, dict(lda2=_L23 - 1, workspace_bytes=sk_ws(100) - 1), -3),
+          (sk, dict(ldb=_L23), -4), (sk, dict(ldb=_L23 - 16, workspace_bytes=sk_ws(100) - 1), -3),
+          (sk, dict(lda1=1 << 20, m=1792, workspace_bytes=sk_ws(1792)), -4),
+          (sk, dict(lda1=1 << 20, m=1791, workspace_bytes=sk_ws(1791) - 1), -3),
+          (sk, dict(kg2=16, a2=_P, lda2=1 << 20, ldb=288, m=1792, workspace_bytes=sk_ws(1792)), -4),
+          (sk, dict(kg2=16, a2=_P, lda2=1 << 20, ldb=288, m=1791, workspace_bytes=sk_ws(1791) - 1), -3),
+          (sk, dict(workspace_bytes=sk_ws(100) - 1), -3), (sk, dict(workspace_bytes=sk_ws(100) - 1, ldb=_L23), -4),
+          (sk, dict(workspace_bytes=sk_ws(100) - 1, ldw=25), -1), (sk, dict(x=None, ldb=_L23), -1)]
+    # ---- gte_gemm_p3_tn / _tn_rows / _tn_rows2 (the split plan in front of the row-map and workspace checks asks for the device's
+    # CU count: a query, no launch; 256 without a device)
+    short = dict(workspace_bytes=tn_ws - 1)
+    t += [(tn, dict(m=0), -1), (tn, dict(n=0), -1), (tn, dict(k=-1), -1), (tn, dict(nseg=-1), -1), (tn, dict(nseg=60), -1),
+          (tn, dict(a=None), -1), (tn, dict(b=None), -1), (tn, dict(c=None), -1),
+          (tn, dict(lda=752), -1), (tn, dict(ldb=752), -1), (tn, dict(a2=_P, lda2=752), -1), (tn, dict(nseg=64, b2=_P, ldb2=368), -1),
+          (tn, dict(ldc=127), -1),
+          (tn, dict(lda=_L23), -4), (tn, dict(ldb=_L23), -4), (tn, dict(lda2=_L23), -4), (tn, dict(ldb2=_L23), -4),
+          (tn, dict(short, lda=_L23 - 16), -3), (tn, dict(short, ldb=_L23 - 16), -3), (tn, dict(ldc=1 << 21), -4),
+          (tn, dict(short, ldc=(1 << 21) - 1), -3),
+          (tn, short, -3), (tn, dict(workspace=None), -3), (tn, dict(c=None, lda=_L23), -1), (tn, dict(short, ldc=1 << 21), -4),
+          (tn, dict(short, ldc=127), -1),
+          (tnr, dict(b_rows=None), -1), (tnr, dict(b_rows=None, ldpb=_L23), -1), (tnr, dict(n_res_rows=0), -1), (tnr, dict(short, n_res_rows=0), -1),
+          (tnr, dict(n_res_rows=0, ldpb=_L23), -4), (tnr, dict(n_res_rows=0, ldpb=_L23 - 16), -1), (tnr, short, -3),
+          (tnr2, dict(b_rows=None), -1), (tnr2, dict(b2_res=None), -1), (tnr2, dict(nseg=0), -1), (tnr2, dict(nseg=0, ldpb=_L23), -1),
+          (tnr2, dict(ldpb2=768), -4), (tnr2, dict(ldpb2=768, n_res_rows=0), -4), (tnr2, dict(ldpb2=768, c=None), -1),
+          (tnr2, dict(ldpb2=368), -1), (tnr2, dict(n_res_rows=0), -1), (tnr2, dict(short, n_res_rows=0), -1), (tnr2, short, -3)]
+    return t
+
+
+def test_planes_gemm_entry_points_refuse_invalid_calls_with_their_codes():
+    """Every public planes-GEMM entry point against a table of invalid calls: negative sizes, each required pointer null, each leading
+    dimension below its minimum, row strides at the limit and below it, the 2 GB operand bound where an entry point has one, an
+    empty resident image, differing row strides behind one row map, a workspace one byte short, and calls wrong in two ways (which
+    return the code of the check that stands first).  All return before the first launch: the pointers are dummies."""
+    lib = _lib.load()
+    valid = _p3_valid_calls(lib)
+    assert set(valid) == set(_P3_PARAMS)
+    table = _p3_invalid_calls(lib)
+    assert {name for name, _, _ in table} == set(_P3_PARAMS) and len(table) >= 200
+    wrong = []
+    for name, change, want in table:
+        assert set(change) <= set(valid[name]), (name, change)
+        args = dict(valid[name], **change)
+        got = getattr(lib, name)(*[args[k] for k in _P3_PARAMS[name].split()])
+        if got != want:
+            wrong.append((name, change, want, got, lib.gte_last_error().decode()))
+    assert not wrong, wrong
+    # the fragments other tests and callers look for in the message
+    args = dict(valid["gte_gemm_p3_nt_rows"], n_res_rows=0)
+    assert lib.gte_gemm_p3_nt_rows(*[args[k] for k in _P3_PARAMS["gte_gemm_p3_nt_rows"].split()]) == -1
+    assert b"empty resident image" in lib.gte_last_error()
+    args = dict(valid["gte_gemm_p3_tn"], a=None)
+    assert lib.gte_gemm_p3_tn(*[args[k] for k in _P3_PARAMS["gte_gemm_p3_tn"].split()]) == -1 and b"null" in lib.gte_last_error()
