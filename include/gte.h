@@ -784,6 +784,10 @@ int gte_gemm_f32(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
  *   dlogits (nullable) = grad_scale * d loss / d logits.
  *   out3: f32[3] = {loss, sum of weights, #correct (argmax == label)}.
  *   labels: int64[n]  (labels_f32 != 0: float32 holding integers, loader.py:350-354).
+ *   A node whose label is outside [0, n_classes) is ignored: it adds nothing to the loss, the sum of
+ *   weights or #correct, and its dlogits row is zero.
+ *   When the sum of weights is 0 (every node ignored or of a zero-weight class) the loss is 0 and
+ *   every dlogits row is zero.
  * workspace: gte_weighted_ce_workspace_bytes(n).
  * ---------------------------------------------------------------------------------------- */
 int64_t gte_weighted_ce_workspace_bytes(int64_t n_nodes);

@@ -619,6 +619,7 @@ def test_smallk_input_layer_backward_in_one_pass(m, k1, k2, n_out, relu):
 @pytest.mark.parametrize("n,c,weighted,float_labels", [(1, 9, False, False), (1000, 9, True, False),
                                                        (7777, 9, False, True), (300, 13, True, True)])
 def test_weighted_ce_vs_torch(n, c, weighted, float_labels):
+    # (the edges -- ignored labels, sum_w == 0, ties, ld > C, > 256 partials -- against float64: tests/test_gpu_loss_optim.py)
     rng = np.random.default_rng(n)
     logits = (3 * rng.standard_normal((n, c))).astype(np.float32)
     y = rng.integers(0, c, n)
@@ -635,6 +636,7 @@ def test_weighted_ce_vs_torch(n, c, weighted, float_labels):
 
 
 def test_adam_step_vs_torch_adam():
+    # (every Adam entry point, its tails, shards and late steps against float64: tests/test_gpu_loss_optim.py)
     rng = np.random.default_rng(0)
     n = 100003
     p0 = rng.standard_normal(n).astype(np.float32)
