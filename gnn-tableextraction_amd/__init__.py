@@ -7,5 +7,6 @@ from . import _lib, function, graph, ops                                   # noq
 from .graph import PageGraph, batch, from_edge_index                       # noqa: F401
 from .components.graphs.models import GcnSAGE, GcnSAGELayer, MeanSAGE, WeightedMeanSAGELayer  # noqa: F401
 from .components.graphs.gat import GAT, GATLayer                          # noqa: F401
+from .ops import relu_l2norm                                               # noqa: F401
 
 __version__ = "0.1.0"

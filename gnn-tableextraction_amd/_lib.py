@@ -182,6 +182,11 @@ SIGNATURES = {
     "gte_ln_relu_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                 c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                 c_void_p, c_int64, c_void_p]),
+    # ReLU + row L2-normalise (csrc/l2norm.hip)
+    "gte_relu_l2norm_fwd": (c_int, [c_void_p, c_int64, c_int, c_float, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "gte_relu_l2norm_bwd_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "gte_relu_l2norm_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                    c_int64, c_int64, c_void_p, c_int64, c_void_p]),
     "gte_gemm_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "gte_gemm_f32": (c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                              c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),

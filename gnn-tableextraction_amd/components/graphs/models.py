@@ -7,7 +7,8 @@ signatures, same attribute names (``layers[i].linear``, ``layers[i].lynorm``, ``
 the reference's weights), same ``model(g) -> logits[N, n_classes]`` call.  What changes is the
 execution: per layer ONE autograd node whose forward and backward are HIP kernels behind the
 C ABI -- CSR gather aggregation with the 1/in-degree norm folded in, a split-weight fp32-MFMA
-GEMM instead of ``cat`` + ``Linear``, LayerNorm/ReLU kernels.  There is no CPU fallback.
+GEMM instead of ``cat`` + ``Linear``, LayerNorm/ReLU kernels (MeanSAGE: ReLU + row L2-normalise kernels, csrc/l2norm.hip).
+There is no CPU fallback.
 """
 import math
 
@@ -117,7 +118,11 @@ class WeightedMeanSAGELayer(nn.Module):
         super().__init__()
         self.linear = nn.Linear(in_feat * 2, out_feat)
 
-    def forward(self, g, h, w):
+    def forward(self, g, h, w, l2norm=False):
+        """``l2norm``: the layer followed by the reference's ``F.normalize(F.relu(.))`` (models.py:166-168), in the same
+        autograd node (csrc/l2norm.hip)."""
+        if l2norm:
+            return ops.sage_layer(g, h, self.linear.weight, self.linear.bias, None, None, w, relu=True, l2norm=True)
         return ops.sage_layer(g, h, self.linear.weight, self.linear.bias, None, None, w, relu=False)
 
 
@@ -130,10 +135,14 @@ class MeanSAGE(nn.Module):
             self.layers.append(WeightedMeanSAGELayer(h_feats, h_feats))
         self.layers.append(WeightedMeanSAGELayer(h_feats, num_classes))
 
-    def forward(self, g, h, w):
+    def forward(self, g, h=None, w=None):
+        """``model(g)`` with the features in ``g.ndata['feat']`` and the edge weights in ``g.edata['feat']`` (a missing key
+        means 1.0, as in GcnSAGELayer), or the reference's ``model(g, h, w)``."""
+        if h is None:
+            h = g.ndata['feat']
+        if w is None:
+            w = g.edata.get("feat") if hasattr(g, "edata") else None
         last = len(self.layers) - 1
         for i, layer in enumerate(self.layers):
-            h = layer(g, h, w)
-            if i != last:
-                h = F.normalize(F.relu(h))
+            h = layer(g, h, w, l2norm=i != last)
         return h

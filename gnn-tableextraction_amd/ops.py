@@ -401,6 +401,39 @@ def ln_relu_bwd(dy, z, stats, gamma, beta, relu: bool, dgamma, dbeta, dbias) -> 
     return dz
 
 
+def relu_l2norm_fwd(z: torch.Tensor, relu: bool = True, eps: float = 1e-12, out: Optional[torch.Tensor] = None,
+                    want_norm: bool = True):
+    """y = relu?(z) / max(||relu?(z)||_2, eps) per row (gte_relu_l2norm_fwd); ``out`` may be ``z`` itself (in place).
+    Returns (y, norm) -- norm = the unclamped row norms the backward needs, None unless ``want_norm``."""
+    require_device(z, "relu_l2norm_fwd")
+    z = _row_major(z)
+    if z.dtype != torch.float32:
+        raise TypeError("relu_l2norm_fwd: fp32 rows only")
+    m, n = z.shape
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=z.device)
+    norm = torch.empty(m, dtype=torch.float32, device=z.device) if want_norm else None
+    check(_lib.load().gte_relu_l2norm_fwd(ptr(z), _ld(z), int(relu), float(eps), ptr(out), _ld(out), ptr(norm), m, n,
+                                          current_stream()), "gte_relu_l2norm_fwd")
+    return out, norm
+
+
+def relu_l2norm_bwd(dy, y, norm, relu: bool = True, eps: float = 1e-12, dbias: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dz of relu_l2norm_fwd from dy and the forward's (y, norm); writes the column sums of dz into ``dbias`` when given
+    (gte_relu_l2norm_bwd).  ``out`` may be ``dy`` itself."""
+    lib = _lib.load()
+    dy, y = _row_major(dy), _row_major(y)
+    m, n = dy.shape
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=dy.device)
+    ws = _workspace(lib.gte_relu_l2norm_bwd_workspace_bytes(m, n), dy.device, "l2nbwd") if dbias is not None else None
+    check(lib.gte_relu_l2norm_bwd(ptr(dy), _ld(dy), ptr(y), _ld(y), ptr(norm), int(relu), float(eps), ptr(out), _ld(out),
+                                  ptr(dbias), m, n, ptr(ws), 0 if ws is None else ws.numel(), current_stream()),
+          "gte_relu_l2norm_bwd")
+    return out
+
+
 def sage_smallk_bwd(dy, a1, a2, weight, bias, gamma, beta, stats, relu: bool, dW, dbias=None, dgamma=None, dbeta=None):
     """LayerNorm(+ReLU) backward and dW = dz^T [a1 | a2] of the short-input INPUT layer in one pass (gte_sage_smallk_bwd): z is
     recomputed from the inputs, dz is never stored.  ``stats`` = the forward's [mean | rstd]."""
@@ -488,7 +521,7 @@ class _SageLayer(torch.autograd.Function):
     aggregation -> split-weight MFMA GEMM (no concat) -> LayerNorm/ReLU; hand-written backward."""
 
     @staticmethod
-    def forward(ctx, h, weight, bias, gamma, beta, graph, w, relu, eps, use_pp):
+    def forward(ctx, h, weight, bias, gamma, beta, graph, w, relu, eps, use_pp, l2norm=False, l2_eps=1e-12):
         h = _row_major(h)
         # grad mode is off inside Function.forward: ask the ctx which inputs need a gradient
         need_grad = any(ctx.needs_input_grad[:5])
@@ -497,7 +530,13 @@ class _SageLayer(torch.autograd.Function):
             csr = graph.in_csr()
             ahn = spmm_csr(csr.indptr, csr.indices, graph.in_weights(w), h, graph.num_nodes(), mean=True,
                            tiles=graph.in_tiles())
-        y, z, stats = sage_linear_fwd(h, ahn, weight, bias, gamma, beta, eps, relu, need_grad)
+        ctx.l2norm, ctx.l2_eps = l2norm, l2_eps
+        if l2norm:
+            # y = normalize(relu?([h | ahn] W^T + b)): the linear map without LayerNorm, then ReLU + row L2-normalise in place
+            y, z, _ = sage_linear_fwd(h, ahn, weight, bias, None, None, eps, False, need_grad)
+            y, stats = relu_l2norm_fwd(y, relu, l2_eps, out=y, want_norm=need_grad)       # (stats = the row norms)
+        else:
+            y, z, stats = sage_linear_fwd(h, ahn, weight, bias, gamma, beta, eps, relu, need_grad)
         ctx.graph, ctx.w, ctx.relu, ctx.use_pp = graph, w, relu, use_pp
         ctx.has_bias, ctx.has_ln = bias is not None, gamma is not None
         ctx.save_for_backward(h, ahn, weight, gamma, beta, z, stats, y)
@@ -512,8 +551,12 @@ class _SageLayer(torch.autograd.Function):
         dgamma = torch.empty(n_out, dtype=torch.float32, device=dev) if ctx.has_ln else None
         dbeta = torch.empty(n_out, dtype=torch.float32, device=dev) if ctx.has_ln else None
         dbias = torch.empty(n_out, dtype=torch.float32, device=dev) if ctx.has_bias else None
-        # (1) LayerNorm/ReLU backward (+ bias/gamma/beta column sums); relu without LN masks on y
-        dz = ln_relu_bwd(dy, z if ctx.has_ln else y, stats, gamma, beta, ctx.relu, dgamma, dbeta, dbias)
+        # (1) LayerNorm/ReLU backward (+ bias/gamma/beta column sums); relu without LN masks on y.  L2-normalised layer: dz and
+        # the bias column sums from (dy, y, row norms) in one pass
+        if ctx.l2norm:
+            dz = relu_l2norm_bwd(dy, y, stats, ctx.relu, ctx.l2_eps, dbias)
+        else:
+            dz = ln_relu_bwd(dy, z if ctx.has_ln else y, stats, gamma, beta, ctx.relu, dgamma, dbeta, dbias)
         # (2) dW = dZ^T [h | ahn]  (reduction over the nodes, split-K inside)
         dweight = None
         if need_w:
@@ -529,7 +572,7 @@ class _SageLayer(torch.autograd.Function):
                 rcsr = g.out_csr()
                 spmm_csr(rcsr.indptr, rcsr.indices, g.out_weights(ctx.w, True), dahn, g.num_nodes(), out=dh,
                          accumulate=True, tiles=g.out_tiles())
-        return dh, dweight, dbias, dgamma, dbeta, None, None, None, None, None
+        return dh, dweight, dbias, dgamma, dbeta, None, None, None, None, None, None, None
 
 
 class _NarrowSageLayer(torch.autograd.Function):
@@ -573,8 +616,14 @@ class _NarrowSageLayer(torch.autograd.Function):
 
 
 def sage_layer(graph, h, weight, bias=None, gamma=None, beta=None, edge_weight=None, relu: bool = False,
-               eps: float = 1e-5, use_pp: bool = False) -> torch.Tensor:
+               eps: float = 1e-5, use_pp: bool = False, l2norm: bool = False, l2_eps: float = 1e-12) -> torch.Tensor:
+    """``l2norm``: the layer's output is normalize(relu?(linear), p=2, dim=1, eps=l2_eps) (MeanSAGE's hidden layers; no
+    LayerNorm); always the general path (_SageLayer)."""
     require_device(h, "sage_layer")
+    if l2norm:
+        if gamma is not None:
+            raise ValueError("sage_layer: l2norm and LayerNorm do not combine")
+        return _SageLayer.apply(h, weight, bias, None, None, graph, edge_weight, relu, eps, use_pp, True, float(l2_eps))
     if (gamma is None and not relu and not use_pp and bias is not None and h.dim() == 2
             and _lib.load().gte_sage_narrow_supported(h.shape[1], weight.shape[0])):
         return _NarrowSageLayer.apply(h, weight, bias, graph, edge_weight)
@@ -615,6 +664,25 @@ def _sage_layer_transform_first(graph, h, weight, bias, gamma, beta, edge_weight
     check(lib.gte_ln_relu_fwd(ptr(t), 2 * fout, ptr(gamma), ptr(beta), float(eps), int(relu), ptr(y), fout, None, n, fout,
                               current_stream()), "gte_ln_relu_fwd")
     return y
+
+
+class _ReluL2Norm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, relu, eps):
+        y, norm = relu_l2norm_fwd(z, relu, eps, want_norm=ctx.needs_input_grad[0])
+        ctx.relu, ctx.eps = relu, eps
+        ctx.save_for_backward(y, norm)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, norm = ctx.saved_tensors
+        return relu_l2norm_bwd(dy, y, norm, ctx.relu, ctx.eps), None, None
+
+
+def relu_l2norm(z: torch.Tensor, relu: bool = True, eps: float = 1e-12) -> torch.Tensor:
+    """``F.normalize(F.relu(z) if relu else z, p=2, dim=1, eps=eps)`` in HIP, differentiable in ``z``."""
+    return _ReluL2Norm.apply(z, bool(relu), float(eps))
 
 
 class _WeightedCE(torch.autograd.Function):

@@ -764,6 +764,22 @@ int gte_ln_relu_bwd(const float* dy, int64_t lddy, const float* z, int64_t ldz, 
                     float* dz, int64_t lddz, float* dgamma, float* dbeta, float* dbias,
                     int64_t M, int64_t n_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ReLU + row L2-normalise (row-wise over n_out), torch.nn.functional.normalize(relu?(z), p=2, dim=1, eps):
+ *   r = relu ? max(z, 0) : z;  s = sqrt(sum_j r_j^2);  y = r / max(s, eps);  norm[i] = s (unclamped; f32[M], nullable).
+ * replaces models.py:166-168 (`F.normalize(F.relu(h))` between the layers of MeanSAGE).  In place (y == z) is allowed.
+ * Any n_out >= 1 (<= 2^30) and any ld >= n_out; columns beyond n_out are neither read nor written.  eps > 0. */
+int gte_relu_l2norm_fwd(const float* z, int64_t ldz, int relu, float eps, float* y, int64_t ldy, float* norm, int64_t M,
+                        int64_t n_out, void* stream);
+/* Its backward (+ bias grad), from dy, the forward's y and norm (same relu and eps):
+ *   d = max(norm[i], eps);  proj = norm[i] >= eps ? sum_j y_j dy_j : 0;  dr = (dy - y proj) / d;
+ *   dz = relu ? (y > 0 ? dr : 0) : dr;  dbias[c] = sum_i dz[i][c]  (f32[n_out], nullable; WRITTEN, no zero-init needed; summed
+ *   in a fixed order: deterministic).  dz may alias dy.
+ * workspace: gte_relu_l2norm_bwd_workspace_bytes(M, n_out), read only when dbias is given (may be NULL otherwise). */
+int64_t gte_relu_l2norm_bwd_workspace_bytes(int64_t M, int64_t n_out);
+int gte_relu_l2norm_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy, const float* norm, int relu, float eps,
+                        float* dz, int64_t lddz, float* dbias, int64_t M, int64_t n_out, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+
 /* General fp32 MFMA GEMM used by the backward:  C[M,N] (+)= op(A)[M,K] * op(B)[K,N]
  *   trans_a = 0: A is [M,K] row-major (lda);  1: A is stored [K,M] (lda) and used transposed
  *   trans_b = 0: B is [K,N] row-major (ldb);  1: B is stored [N,K] (ldb) and used transposed
