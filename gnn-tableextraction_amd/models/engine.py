@@ -104,6 +104,7 @@ class TrainStep:
 from .. import _lib                                                     # noqa: E402
 from .._lib import LAYER_PLANES, LAYER_SMALLK, LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT      # noqa: E402
 from ..components.graphs.models import GcnSAGE, _is_relu               # noqa: E402
+from .call_schedule import CallSchedule, batch_shape, f32_rows         # noqa: E402
 import torch.nn as nn                                                  # noqa: E402
 
 
@@ -169,8 +170,10 @@ class FusedGcnSageStep(TrainStep):
         first_upper = next((p for p in model.layers[1].parameters() if p.requires_grad), None) if len(model.layers) > 1 else None
         self._dp_split = (os.environ.get("GTE_DP_OVERLAP", "0") == "1" and first_upper is not None and self.dropout_p == 0
                           and self._gslice[id(first_upper)].storage_offset() == self._n0)
-        self._bufs = {}
-        self._graph_bufs = {}
+        self._bufs = {}                               # one-call plans: _plan_key -> capacity-sized shared buffer set
+        self._graph_bufs = {}                         # (captured batch, buffer-set key of either schedule) -> its private set
+        self._reserved = {}                           # input width -> capacity asked for by reserve()
+        self._calls = CallSchedule(self)              # the call-by-call schedule: its own buffer sets and weight images
         self._private_key = None
         self._graphs = {}
         self._graph_owner = {}
@@ -190,12 +193,9 @@ class FusedGcnSageStep(TrainStep):
         self.fuse_ln_narrow = os.environ.get("GTE_FUSE_LN_NARROW", "1") == "1"
         # dX of layer 1 with the whole backward of a short-input layer 0 as its epilogue (gte_gemm_p3_nt_smallk_bwd)
         self.fuse_smallk_dx = os.environ.get("GTE_FUSE_SMALLK_DX", "1") == "1"
-        self._smallk_done = False
-        self._ln_p3_done = None
         # LayerNorm(+ReLU) forward of the last hidden layer inside the output layer's forward kernel (gte_sage_narrow_fwd_ln):
         # one launch and one pass over [n, hidden] less
         self.fuse_ln_fwd = os.environ.get("GTE_FUSE_LN_FWD", "1") == "1"
-        self._head_scale = None
         self._tail_ws = None
         # planes path (GTE_PLANES=0 disables): in the split-bf16 GEMM mode the operands of the transform GEMMs are written as P3
         # images (three bf16 planes, csrc/p3.h) by their producers and multiplied by the planes GEMMs (csrc/gemm_p3.hip)
@@ -207,7 +207,7 @@ class FusedGcnSageStep(TrainStep):
         # run): z = [x | ahn] W^T from two resident images behind the batch's row map, no aggregation / q / feature copy in the
         # step for layer 0 (GTE_LAYER_CACHED).  Costs a second resident image; GTE_CACHE_AGG=0 turns it off
         self.cache_input_agg = os.environ.get("GTE_CACHE_AGG", "1") == "1"
-        # call-by-call schedule: layer index -> (forward image, backward image or None); one-call plans: _plan_key -> their image set
+        # one-call plans: _plan_key -> their image set (the call-by-call schedule keeps its own)
         self._wimg = {}
         # weight images in the block-major layout (ops.P3): a K block of the weights is ONE contiguous run, whole cache lines for
         # every NT planes GEMM, and the block-major-weights kernel (gemm_p3_nt_sq_kernel) loads its fragments straight into
@@ -219,6 +219,10 @@ class FusedGcnSageStep(TrainStep):
         # p.copy_, flat_param.copy_) move the counters; raw writes through ``p.data`` do not: invalidate_weight_images() then.
         self.wimg_in_fold = os.environ.get("GTE_WIMG_IN_FOLD", "1") == "1"
         self._wimg_sig = None
+        self._last_wimg = None                        # (descriptors an unfused optimiser launch may still rewrite: _c_step)
+        self._keep = ()                               # what the last one-call step's plan points at: alive until the next step
+        # optimiser state on the device, made at the first step (_adam_state)
+        self._hyper, self._step_dev, self._ticket, self._hyper_host, self._step_dev_host = None, None, None, None, 0
         # the whole step through ONE C entry point (gte_gcnsage_step) when the configuration allows (GTE_C_STEP=0: call by call)
         self.use_c_step = os.environ.get("GTE_C_STEP", "1") == "1"
         # called (once per step, no arguments) right before the LAST big kernel of a step is launched -- layer 0's dW GEMM,
@@ -238,60 +242,6 @@ class FusedGcnSageStep(TrainStep):
                              "configuration; use TrainStep")
 
     # -- buffers -------------------------------------------------------------------------------------
-    def _alloc(self, cap: int, f0: int):
-        """Buffer set of the call-by-call schedule (_run) only; a one-call plan has its own (_alloc_plan)."""
-        dev = self.flat_param.device
-        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-        layers = self.model.layers
-        dims = [f0] + [l.out_feats for l in layers]
-        tf = [self._transform_first(l, dims[i]) for i, l in enumerate(layers)]
-        qf = [self._qform(i, l, dims[i]) for i, l in enumerate(layers)]
-        b = {"cap": cap,
-             # aggregated input [cap, fin] of an aggregate-first layer; a q-form layer reuses it for q in the backward
-             "ahn": [None if tf[i] else new(cap, dims[i]) for i in range(len(layers))],
-             # transform-first layer: t = [x W_s^T + b | x W_n^T]; z is accumulated into the left half, q reuses the right
-             "t": [new(cap, 2 * dims[i + 1]) if tf[i] else None for i in range(len(layers))],
-             "z": [new(cap, dims[i + 1]) if (isinstance(l.lynorm, nn.LayerNorm) and not tf[i]) else None
-                   for i, l in enumerate(layers)],
-             "stats": [new(2 * cap) if isinstance(l.lynorm, nn.LayerNorm) else None for l in layers],
-             "y": [new(cap, dims[i + 1]) for i in range(len(layers))],
-             "dy": [new(cap, dims[i + 1]) for i in range(len(layers))],      # grad w.r.t. layer output (dz in place)
-             "dahn": new(cap, max([dims[i] for i in range(1, len(layers)) if not qf[i] and not self._narrow(layers[i], dims[i])]
-                                  + [1])),
-             "tn": new(cap, dims[-1]), "q": new(cap, dims[-1]),       # narrow (class-count-wide) output layer
-             "out3": new(3)}
-        lib = self.lib
-        # planes layers: P3 images of the layer input (layer 0: only when the batch does not bring one), of dz and of q, and
-        # the split-K workspace of the dW planes GEMM
-        pl = [self._planes_layer(i, l, dims[i]) for i, l in enumerate(layers)]
-        b["pl"] = pl
-        b["hp"] = [ops.P3.empty(cap, dims[i], dev) if pl[i] else None for i in range(len(layers))]
-        b["dzp"] = [ops.P3.empty(cap, dims[i + 1], dev) if pl[i] else None for i in range(len(layers))]
-        b["qp"] = [ops.P3.empty(cap, dims[i + 1], dev) if pl[i] else None for i in range(len(layers))]
-        b["ws_p3"] = [torch.empty(int(lib.gte_gemm_p3_tn_workspace_bytes(dims[i + 1], 2 * dims[i], dims[i], cap)), dtype=torch.uint8,
-                                  device=dev) if pl[i] else None for i in range(len(layers))]
-        for i in range(len(layers)):
-            if pl[i] and b["t"][i] is None:
-                b["t"][i] = new(cap, 2 * dims[i + 1])
-        # every workspace requirement grows with the node count, so the capacity's requirement covers any n <= cap
-        ws = max([lib.gte_weighted_ce_workspace_bytes(cap)] +
-                 [lib.gte_ln_relu_bwd_workspace_bytes(cap, d) for d in dims[1:]] +
-                 [lib.gte_gemm_workspace_bytes(dims[i + 1], dims[i], cap) for i in range(len(layers))] +
-                 [lib.gte_sage_narrow_bwd_workspace_bytes(cap, min(dims[-2], 256), min(dims[-1], 16))])
-        b["ws"] = torch.empty(int(ws), dtype=torch.uint8, device=dev)
-        # the backward defers its partial-sum folds to one launch (gte_fold_defer_*): every producer keeps its partials
-        # in a workspace of its own until the flush
-        b["ws_ln"] = [torch.empty(int(max(lib.gte_ln_relu_bwd_workspace_bytes(cap, dims[i + 1]),
-                                          lib.gte_gemm_p3_nt_ln_bwd_workspace_bytes(cap, dims[i + 1]),
-                                          lib.gte_sage_narrow_bwd_ln_workspace_bytes(cap, min(dims[i + 1], 256)))),
-                                  dtype=torch.uint8, device=dev) for i in range(len(layers))]
-        b["ce_part"] = torch.empty(int(lib.gte_head_agg_ce_workspace_bytes(cap)), dtype=torch.uint8, device=dev)
-        b["ws_nar"] = torch.empty(int(lib.gte_sage_narrow_bwd_workspace_bytes(cap, min(dims[-2], 256), min(dims[-1], 16))),
-                                  dtype=torch.uint8, device=dev)
-        # one private workspace per layer for the dW GEMMs: they run on the side stream, several at once
-        b["ws_dw"] = [torch.empty(int(self._ws_dw_bytes(i, dims, cap)), dtype=torch.uint8, device=dev) for i in range(len(layers))]
-        return b
-
     def _ws_dw_bytes(self, i: int, dims, cap: int) -> int:
         """Workspace of layer i's weight-gradient launch: split-K slabs of the dW GEMM; for the input layer additionally the
         partials of the one-pass short-input backward -- only where that path exists (k1 + k2 <= 28: at F0 = 831 the size
@@ -371,13 +321,13 @@ class FusedGcnSageStep(TrainStep):
         return ("gen", f0, tuple(kinds), bool(out_gemm))
 
     def _buffers_plan(self, n: int, f0: int, kinds, out_gemm: bool):
-        """The (capacity-sized, shared or captured-batch-private) buffer set of a one-call plan; see _buffers."""
+        """The (capacity-sized, shared or captured-batch-private) buffer set of a one-call plan; see CallSchedule._full_set."""
         key = self._plan_key(f0, kinds, out_gemm)
         if self._private_key is not None:
             return self._private_set(key, n, lambda m: self._alloc_plan(m, f0, kinds, out_gemm))
         full = self._bufs.get(key)
         if full is None or full["cap"] < n:
-            cap = max(-(-int(n * 1.125) // 4096) * 4096, getattr(self, "_reserved", {}).get(f0, 0))
+            cap = max(-(-int(n * 1.125) // 4096) * 4096, self._reserved.get(f0, 0))
             self._bufs.pop(key, None)
             full = self._bufs[key] = self._alloc_plan(cap, f0, kinds, out_gemm)
         return full
@@ -386,8 +336,7 @@ class FusedGcnSageStep(TrainStep):
         """(buffer set, layer kinds, out_gemm) of the one-call plan a training step on ``batch`` runs on -- the shared set, or the
         private set of the batch captured under ``private_key`` (capture(): ``id`` of its graph) -- for tests and tools that read
         what a step left behind.  None when that step is not on a plan (call-by-call schedule), or no such step has run yet."""
-        xp = getattr(batch, "feat_p3", None)
-        n, f0 = (xp.rows, xp.cols) if xp is not None else batch.ndata['feat'].shape
+        _xp, n, f0 = batch_shape(batch)
         kinds = self._plan_kinds(f0, n, self._batch_cached(batch))
         if kinds is None:
             return None
@@ -396,58 +345,20 @@ class FusedGcnSageStep(TrainStep):
         full = self._bufs.get(key) if private_key is None else self._graph_bufs.get((private_key, key))
         return None if full is None else (full, kinds, out_gemm)
 
-    def _buffers(self, n: int, f0: int):
-        """Row views [0:n] of the call-by-call schedule's (_run) buffers, allocated for a CAPACITY, not for n: in the real loop
-        every batch has a different node count, and per-count buffers would grow without bound (~300 MB per new count at F0=831).
-        The shared set grows geometrically to the largest batch seen.  A captured HIP graph bakes pointers in,
-        so each captured batch owns a private exact-size set that is never reallocated."""
-        key = (f0, self._planes_on())                  # the layer plan (which layers take P3 operands) depends on the GEMM mode
-        if self._private_key is not None:
-            full = self._private_set(key, n, lambda m: self._alloc(m, f0))
-        else:
-            full = self._bufs.get(key)
-            if full is None or full["cap"] < n:
-                # (at least the reserved capacity: a shape whose steps usually run on a plan is not sized by reserve())
-                cap = max(-(-int(n * 1.125) // 4096) * 4096, getattr(self, "_reserved", {}).get(f0, 0))
-                self._bufs = {k: v for k, v in self._bufs.items() if k[0] != f0}     # one call-by-call set per input width alive
-                full = self._bufs[key] = self._alloc(cap, f0)
-        v = lambda t: None if t is None else t[:n]
-        return {"ahn": [v(t) for t in full["ahn"]], "t": [v(t) for t in full["t"]], "z": [v(t) for t in full["z"]],
-                "stats": [None if t is None else t[:2 * n] for t in full["stats"]], "y": [v(t) for t in full["y"]],
-                "dy": [v(t) for t in full["dy"]], "dahn": v(full["dahn"]), "tn": v(full["tn"]), "q": v(full["q"]),
-                "out3": full["out3"], "ws": full["ws"], "ws_ln": full["ws_ln"], "ws_nar": full["ws_nar"],
-                "ce_part": full["ce_part"],
-                "ws_dw": full["ws_dw"], "pl": full["pl"], "ws_p3": full["ws_p3"], "_full": full,
-                "hp": [None if t is None else t.view_rows(n) for t in full["hp"]],
-                "dzp": [None if t is None else t.view_rows(n) for t in full["dzp"]],
-                "qp": [None if t is None else t.view_rows(n) for t in full["qp"]]}
-
     def reserve(self, n_nodes: int, f0: int, cached: bool = False) -> None:
         """Size the shared per-batch buffers for batches of up to ``n_nodes`` nodes (the train loop knows the largest batch
         its page table can produce): no reallocation -- a device synchronisation plus ~12 KB per node of new buffers -- later,
         in the middle of an epoch.  A one-call plan takes the recorded capacity when it allocates its set at the first step
         (``cached``: the batches bring the aggregate image); the call-by-call schedule's set is allocated here."""
         cap = -(-int(n_nodes) // 4096) * 4096
-        if not hasattr(self, "_reserved"):
-            self._reserved = {}
         self._reserved[f0] = max(self._reserved.get(f0, 0), cap)
         if self._plan_kinds(f0, 0, cached) is not None:
             return                      # a one-call plan allocates its own set (_buffers_plan) at this capacity on first use
-        key = (f0, self._planes_on())
-        full = self._bufs.get(key)
-        if n_nodes > 0 and (full is None or full["cap"] < n_nodes):
-            self._bufs = {k: v for k, v in self._bufs.items() if k[0] != f0}    # drop the old set first: both need not be alive
-            self._bufs[key] = self._alloc(cap, f0)
+        self._calls.reserve(n_nodes, f0)
 
     def _narrow(self, layer, fin: int) -> bool:
         return (not isinstance(layer.lynorm, nn.LayerNorm) and layer.activation is None and layer.linear.bias is not None
                 and bool(self.lib.gte_sage_narrow_supported(fin, layer.out_feats)))
-
-    def _ln_rows_below(self, i: int, layers, fin: int, b) -> bool:
-        """The output layer's backward runs the LayerNorm(+ReLU) backward of the PLANES layer below in the row form
-        (gte_sage_narrow_bwd_ln_p3: dz as fp32 + image)."""
-        return (self.fuse_ln_narrow and i > 0 and i == len(layers) - 1 and bool(b["pl"][i - 1])
-                and self._narrow(layers[i], fin) and fin % 16 == 0 and bool(self.lib.gte_head_supported(fin, layers[i].out_feats)))
 
     def _narrow_padded(self, layer, fin: int) -> bool:
         """The narrow output kernels on PADDED hidden rows (gte_sage_narrow_fwd_pad / gte_sage_narrow_bwd_ln_p3_pad): a hidden width
@@ -466,13 +377,6 @@ class FusedGcnSageStep(TrainStep):
         moves out_feats columns instead of fin (gte_sage_transform_fwd)."""
         return (self.transform_first and isinstance(layer.lynorm, nn.LayerNorm) and layer.linear.bias is not None
                 and not self._narrow(layer, fin) and fin > layer.out_feats)
-
-    def _qform(self, i: int, layer, fin: int) -> bool:
-        """Backward through q = A_w^T(norm * dz): dW = [dz^T h | q^T h], dh = dz W_s + q W_n.  Always for a transform-first
-        layer (nothing else was saved); for an inner layer when q is not wider than the classic dahn."""
-        if self._narrow(layer, fin):
-            return False
-        return self._transform_first(layer, fin) or (self.transform_first and i > 0 and layer.out_feats <= fin)
 
     # -- planes path ---------------------------------------------------------------------------------
     def _planes_on(self) -> bool:
@@ -502,40 +406,6 @@ class FusedGcnSageStep(TrainStep):
         """The parameters were changed behind torch's version counters (a raw ``p.data`` write, a foreign kernel): the next
         forward converts the weight images again."""
         self._wimg_sig = None
-
-    def _weight_images(self, dims):
-        """The call-by-call schedule's (_run) conversion launch: P3 images of the planes layers' weights, forward [W_s rows ; W_n rows]
-        x fin, backward (dX) [fin rows] x [W_s^T | W_n^T].  ONE launch in front of every forward (the parameters change every step;
-        the launch is part of a captured step).  A one-call plan has its own images and descriptors (_weight_images_gen)."""
-        layers = self.model.layers
-        descs = []
-        for i, L in enumerate(layers):
-            fin, fout = dims[i], L.out_feats
-            if not self._planes_layer(i, L, fin):
-                continue
-            img = self._wimg.get(i)
-            if img is None:
-                # (weight images are BLOCK-MAJOR: the B operand of every NT planes GEMM -- ops.P3)
-                fwd = ops.P3.empty(2 * fout, fin, self.flat_param.device, block_major=self.block_major_weights)
-                fwd.data.zero_()
-                bwd = None
-                if i > 0:
-                    bwd = ops.P3.empty(fin, 2 * fout, self.flat_param.device, block_major=self.block_major_weights)
-                    bwd.data.zero_()
-                img = self._wimg[i] = (fwd, bwd)
-            fwd, bwd = img
-            W = L.linear.weight
-            wp, ld = W.data_ptr(), W.stride(0)
-            descs.append(_lib.P3Desc(wp, ld, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
-            descs.append(_lib.P3Desc(wp + 4 * fin, ld, fout, fin, 0, fwd.at(fout, 0), fwd.ldp))
-            if bwd is not None:
-                descs.append(_lib.P3Desc(wp, ld, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
-                descs.append(_lib.P3Desc(wp + 4 * fin, ld, fin, fout, 1, bwd.at(0, fout // 16), bwd.ldp))
-        st = _lib.current_stream()
-        for k in range(0, len(descs), 16):
-            chunk = descs[k:k + 16]
-            arr = (_lib.P3Desc * len(chunk))(*chunk)
-            _lib.check(self.lib.gte_p3_from_f32_batch(ctypes.addressof(arr), len(chunk), st), "gte_p3_from_f32_batch")
 
     # -- the whole step as one host call (gte_gcnsage_step) ---------------------------------------------
     def _smallk_bwd(self, i: int, layer, fin: int) -> bool:
@@ -639,8 +509,7 @@ class FusedGcnSageStep(TrainStep):
         """Bit mask of the hidden layers a training step on ``g`` runs in the wide addressing form (gte_gcnsage_step_wide_layers on
         the step's own plan: a dropout layer whose row buffers reach 2 GB, or every dropout layer under gte_dropout_set_wide(1) on
         this thread); 0 for a model without dropout or a step that is not on a plan."""
-        xp = getattr(g, "feat_p3", None)
-        n, f0 = (xp.rows, xp.cols) if xp is not None else g.ndata['feat'].shape
+        _xp, n, f0 = batch_shape(g)
         kinds = self._plan_kinds(f0, n, self._batch_cached(g))
         if kinds is None or self.dropout_p == 0:
             return 0
@@ -754,13 +623,11 @@ class FusedGcnSageStep(TrainStep):
         per-batch fields -- graph, features, node count -- set for ``g``.  Returns (plan, fused flag, {out3, logits rows, image-set
         tag}, node count, tensors the plan points at)."""
         lib, P = self.lib, _lib.ptr
-        xp = getattr(g, "feat_p3", None)
-        if xp is not None:
-            x, n, f0 = None, xp.rows, xp.cols
-        else:
-            x = ops._row_major(g.ndata['feat'])
+        xp, n, f0 = batch_shape(g)
+        x = None
+        if xp is None:
+            x = f32_rows(g)
             _lib.require_device(x, "FusedGcnSageStep")
-            n, f0 = x.shape
         out_gemm = self._plan_mode(kinds, f0)[1]
         b = self._buffers_plan(n, f0, kinds, out_gemm)
         layers = list(self.model.layers)
@@ -858,14 +725,14 @@ class FusedGcnSageStep(TrainStep):
         plan.fuse_ln_dx = (int(self.fuse_ln_dx) | (2 if self.fuse_ln_narrow else 0) | (8 if self.fuse_smallk_dx else 0)
                            | (4 if self.fuse_head_gemm else 0) | (16 if self.fuse_ln_fwd else 0))
         L0 = plan.layer[0]
+        rows = (P(xp.row_map), xp.res_rows) if xp is not None and xp.row_map is not None else (None, 0)     # the batch's row map
         if kinds[0] == LAYER_DROPOUT:
             # dropout: the input as fp32 rows or as the (resident) image; the masks of this seed / rank at the device step counter
             if xp is not None:
                 L0.xp, L0.ldp_x, L0.x, L0.ldx = P(xp.data), xp.ldp, None, 0
-                L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
             else:
-                L0.xp, L0.ldp_x, L0.h_rows, L0.n_res_rows = None, 0, None, 0
-                L0.x, L0.ldx = P(x), ops._ld(x)
+                L0.xp, L0.ldp_x, L0.x, L0.ldx = None, 0, P(x), ops._ld(x)
+            L0.h_rows, L0.n_res_rows = rows
             self._adam_state()
             plan.dropout_p, plan.dropout_seed, plan.rank = float(self.dropout_p), self.dropout_seed, self.rank
             plan.step_counter = P(self._step_dev)
@@ -875,22 +742,18 @@ class FusedGcnSageStep(TrainStep):
                 raise _lib.GteError("a cached-aggregate input layer needs feat_p3 and agg_p3 (resident images behind a row map, or the graph's own)")
             L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
             L0.ahnp, L0.ldp_ahn = P(ap.data), ap.ldp
-            L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
+            L0.h_rows, L0.n_res_rows = rows
         elif kinds[0] == LAYER_PLANES:
             if xp is not None:
                 L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
-                L0.h_rows, L0.n_res_rows = (P(xp.row_map), xp.res_rows) if xp.row_map is not None else (None, 0)
             else:
                 L0.hp, L0.ldp_h, L0.make_hp = P(b["hp"][0].data), b["hp"][0].ldp, 1
-                L0.h_rows, L0.n_res_rows = None, 0
                 L0.x, L0.ldx = P(x), ops._ld(x)
+            L0.h_rows, L0.n_res_rows = rows
         else:
-            if x is None:
-                # an image-only batch on a layer that reads fp32 rows (copied image rows without the aggregate image, GTE_P3_ROWS=0):
-                # the rows back from the image -- exactly the fp32 values; slow, a measurement configuration
-                if 'feat' not in g.ndata:
-                    g.ndata['feat'] = ops.p3_to_f32(xp)
-                x = ops._row_major(g.ndata['feat'])
+            # (an image-only batch on a layer that reads fp32 rows -- copied image rows without the aggregate image, GTE_P3_ROWS=0 --
+            # gets the rows back from the image: slow, a measurement configuration)
+            x = f32_rows(g) if x is None else x
             L0.x, L0.ldx = P(x), ops._ld(x)
         plan.indptr, plan.indices, plan.w_in = P(csr.indptr), P(csr.indices), P(w_in)
         plan.rindptr, plan.rindices, plan.w_out = P(rcsr.indptr), P(rcsr.indices), P(w_out)
@@ -962,8 +825,7 @@ class FusedGcnSageStep(TrainStep):
         forward on this engine overwrites.  Configurations the one-call plan does not cover -- and large graphs that bring fp32
         features to a planes input layer (a validation graph: the plan would write their image first) -- run the module path."""
         self._last_wimg = None
-        xp = getattr(g, "feat_p3", None)
-        n, f0 = (xp.rows, xp.cols) if xp is not None else g.ndata['feat'].shape
+        xp, n, f0 = batch_shape(g)
         kinds = self._plan_kinds(f0, n, self._batch_cached(g), train=False) if n > 0 else None
         if kinds is not None and xp is None and kinds[0] == LAYER_PLANES and n * f0 > self.FORWARD_IMAGE_MAX_ELEMS:
             # fp32 features under a planes input layer: the one-call plan would first write their P3 image (65 us at 21.5 k x 831)
@@ -971,10 +833,8 @@ class FusedGcnSageStep(TrainStep):
             # (profiles/debug/val_forward_time.py: 0.241 against 0.275 ms at 21.5 k nodes, 1.24 against 1.43 ms at 124 k)
             kinds = None
         if kinds is None:
-            if xp is not None and 'feat' not in g.ndata:
-                # a resident batch in image mode carries its features as a P3 image only: the module path reads fp32 rows (the
-                # image holds exactly the fp32 values)
-                g.ndata['feat'] = ops.p3_to_f32(xp)
+            if xp is not None:
+                f32_rows(g)     # (the module path reads fp32 rows: a resident batch in image mode carries the image only)
             was = self.model.training
             self.model.eval()                 # (no dropout in the evaluation forward)
             try:
@@ -996,14 +856,21 @@ class FusedGcnSageStep(TrainStep):
         """Forward, loss and the backward of layers n_layers-1 .. upto_layer (gradients of those layers final on return:
         their folds are flushed).  upto_layer > 0 leaves the rest to :meth:`backward_rest` -- the data-parallel step
         all-reduces the upper layers' gradient slice while the (longest) backward of layer 0 runs."""
+        with_adam = bool(self._fuse_adam_req)
         if upto_layer == 0:
-            xp = getattr(g, "feat_p3", None)
-            n, f0 = (xp.rows, xp.cols) if xp is not None else g.ndata['feat'].shape
+            _xp, n, f0 = batch_shape(g)
             kinds = self._plan_kinds(f0, n, self._batch_cached(g))
             if kinds is not None:
-                return self._c_step(g, labels, grad_scale, kinds, with_adam=bool(self._fuse_adam_req))
+                return self._c_step(g, labels, grad_scale, kinds, with_adam)
         self._refuse_dropout()
-        return self._run(g, labels, grad_scale, len(self.model.layers) - 1, upto_layer, forward=True)
+        out3, self._adam_fused = self._calls.run(g, labels, grad_scale, len(self.model.layers) - 1, upto_layer, with_adam=with_adam)
+        return out3
+
+    def _plan_images_stale(self) -> None:
+        """A call-by-call pass begins: the one-call plans' weight images no longer follow the parameters, and no later optimiser
+        launch may rewrite them."""
+        self._wimg_sig = None
+        self._last_wimg = None
 
     def _refuse_dropout(self) -> None:
         if self.dropout_p > 0:
@@ -1013,386 +880,10 @@ class FusedGcnSageStep(TrainStep):
                                "nodes (2^30: 32-bit row indices; the plan has no byte bound). Use TrainStep for it.")
 
     def backward_rest(self, g, from_layer: int) -> None:
-        """Backward of layers from_layer-1 .. 0 after ``forward_backward(..., upto_layer=from_layer)`` on the same batch."""
+        """Backward of layers from_layer-1 .. 0 after ``forward_backward(..., upto_layer=from_layer)`` on the same batch (the same
+        graph object, no other batch in between: RuntimeError otherwise)."""
         self._refuse_dropout()
-        self._run(g, None, 1.0, from_layer - 1, 0, forward=False)
-
-    def _run(self, g, labels, grad_scale, hi, lo, forward):
-        lib, P, check = self.lib, _lib.ptr, _lib.check
-        self._wimg_sig = None                         # (this schedule converts the weight images in front of every forward)
-        self._last_wimg = None                        # (... and no later optimiser launch may rewrite another plan's images)
-        st = _lib.current_stream()
-        timed = ops._timed
-        xp = getattr(g, "feat_p3", None)              # resident batches in image mode bring the features as a P3 image only
-        if xp is not None:
-            x, n, f0 = None, xp.rows, xp.cols
-            if not self._planes_layer(0, self.model.layers[0], f0, n):
-                # an image batch on a layer that reads fp32 rows (this schedule runs layer 0 on planes for fewer shapes than the
-                # one-call plans, and does not know the cached-aggregate form; or the GEMM mode changed after the resident pages
-                # were converted): the rows back from the image -- exactly the fp32 values
-                if 'feat' not in g.ndata:
-                    g.ndata['feat'] = ops.p3_to_f32(xp)
-                x, xp = ops._row_major(g.ndata['feat']), None
-        else:
-            x = ops._row_major(g.ndata['feat'])
-            _lib.require_device(x, "FusedGcnSageStep")
-            n, f0 = x.shape
-        b = self._buffers(n, f0)
-        b["xp"] = xp
-        # (kept with the buffer set, not with this call's row views: backward_rest() of the data-parallel overlap reads what the
-        # forward of forward_backward() left)
-        b["hp_used"] = b["_full"].setdefault("_hp_used", [None] * len(self.model.layers))
-        layers = list(self.model.layers)
-        ew = g.edata.get("feat")
-        csr, rcsr = g.in_csr(), g.out_csr()
-        w_in, w_out = g.in_weights(ew), g.out_weights(ew, True)
-        if forward and any(b["pl"]):
-            self._weight_images([f0] + [l.out_feats for l in layers])
-        big = n * max(f0, max(l.out_feats for l in self.model.layers)) * 4 >= min(ops.TILED_FULL_MIN_BYTES, ops.TILED_MIN_BYTES)
-        t_in, t_out = (g.in_tiles(), g.out_tiles()) if big else (None, None)
-
-        PP = lambda a: a if isinstance(a, int) else P(a)           # tensor or raw device address (a column offset into one)
-
-        def aggregate(csr_, w_, tiles_, src, ldsrc, dst, lddst, f, reduce, accumulate):
-            nbytes = 2.0 * n * f * 4 + 8.0 * csr_.indices.numel() + 4.0 * (n + 1)
-            if tiles_ is not None and ops.use_tiled(n, f, csr_.indices.numel()):
-                with timed("spmm_tiled", nbytes):
-                    check(lib.gte_spmm_csr_tiled(P(csr_.indptr), P(csr_.indices), P(tiles_.local_index), P(w_),
-                                                 P(tiles_.tile_ptr), P(tiles_.tile_src), PP(src), ldsrc, PP(dst), lddst,
-                                                 n, f, reduce, int(accumulate), st), "gte_spmm_csr_tiled")
-            else:
-                fn = lib.gte_spmm_csr_accumulate if accumulate else lib.gte_spmm_csr
-                with timed("spmm_csr", nbytes):
-                    check(fn(P(csr_.indptr), P(csr_.indices), P(w_), PP(src), ldsrc, PP(dst), lddst, n, f, _lib.GTE_F32,
-                             reduce, st), "gte_spmm_csr")
-        # scratch for the GEMM tail split (see gte_gemm_set_tail_workspace): registered for this launch sequence only
-        if self._tail_ws is None:
-            self._tail_ws = torch.empty(int(lib.gte_gemm_tail_workspace_bytes()), dtype=torch.uint8, device=self.flat_param.device)
-        check(lib.gte_gemm_set_tail_workspace(P(self._tail_ws) if self.tail_split else None,
-                                              self._tail_ws.numel() if self.tail_split else 0), "gte_gemm_set_tail_workspace")
-        try:
-            if forward:
-                self._forward_loss(g, labels, grad_scale, x, n, f0, b, layers, csr, w_in, t_in, aggregate, st)
-                self._ln_p3_done = None
-                self._smallk_done = False
-            # ---------------- backward of layers hi .. lo ----------------
-            check(lib.gte_fold_defer_begin(st), "gte_fold_defer_begin")
-            try:
-                self._backward(g, b, layers, x, n, aggregate, rcsr, w_out, t_out, st, hi, lo)
-            finally:
-                if self._fuse_adam_req and lo == 0:
-                    # the folds produce every gradient element: the optimiser step rides in the same launch (falls back to a
-                    # plain flush, fused = 0, when some gradient was written directly)
-                    fused = ctypes.c_int(0)
-                    check(lib.gte_fold_defer_flush_adam(P(self.flat_param), P(self.flat_grad), P(self.exp_avg), P(self.exp_avg_sq),
-                                                        self.flat_param.numel(), P(self._hyper), P(self._step_dev),
-                                                        P(self._ticket), ctypes.byref(fused)), "gte_fold_defer_flush_adam")
-                    self._adam_fused = bool(fused.value)
-                else:
-                    check(lib.gte_fold_defer_flush(), "gte_fold_defer_flush")
-            return b["out3"]
-        finally:
-            lib.gte_gemm_set_tail_workspace(None, 0)
-
-    def _forward_loss(self, g, labels, grad_scale, x, n, f0, b, layers, csr, w_in, t_in, aggregate, st):
-        lib, P, check = self.lib, _lib.ptr, _lib.check
-        timed, ld = ops._timed, ops._ld
-        ws, wsn = P(b["ws"]), b["ws"].numel()
-        # ---------------- forward ----------------
-        h = x
-        b["hp_used"][:] = [None] * len(layers)
-        fused_head = False
-        pending_ln = None            # (layer, z, y, stats) of a LayerNorm left to the output layer's forward kernel
-        hp_in = None                 # P3 image of the current layer's input (set by the producer of h)
-        for i, L in enumerate(layers):
-            fin, fout = (f0 if i == 0 else layers[i - 1].out_feats), L.out_feats
-            W, bias = L.linear.weight, L.linear.bias
-            ln = isinstance(L.lynorm, nn.LayerNorm)
-            relu = L.activation is not None
-            ahn, y = b["ahn"][i], b["y"][i]
-            if b["pl"][i]:
-                # ---- planes layer: t = h [W_s ; W_n]^T + [b | 0] (planes GEMM), then z = t_self + mean-aggregate(t_neigh),
-                # LayerNorm, ReLU in ONE pass that writes y as the next planes layer's input image (and / or fp32)
-                if hp_in is None:
-                    hp_in = b["xp"] if (i == 0 and b["xp"] is not None) else b["hp"][i]
-                    if not (i == 0 and b["xp"] is not None):
-                        check(lib.gte_p3_from_f32(P(h), ld(h), n, fin, 0, P(hp_in.data), hp_in.ldp, st), "gte_p3_from_f32")
-                b["hp_used"][i] = hp_in
-                wf = self._wimg[i][0]
-                t = b["t"][i]
-                with timed("gemm_nt", 4.0 * n * fin * fout) as tm:
-                    for _ in tm.repeat():
-                        if hp_in.row_map is not None:      # the RESIDENT image through the batch's row map
-                            check(lib.gte_gemm_p3_nt_rows(P(hp_in.data), hp_in.ldp, fin, P(hp_in.row_map), hp_in.res_rows, P(wf.data),
-                                                          wf.ldp, P(bias), fout, P(t), 2 * fout, n, 2 * fout, 0, 0, st),
-                                  "gte_gemm_p3_nt_rows")
-                        else:
-                            check(lib.gte_gemm_p3_nt(P(hp_in.data), hp_in.ldp, fin, None, 0, 0, P(wf.data), wf.ldp, P(bias), fout, P(t),
-                                                     2 * fout, n, 2 * fout, 0, 0, st), "gte_gemm_p3_nt")
-                nxt_planes = i + 1 < len(layers) and b["pl"][i + 1]
-                yp = b["hp"][i + 1] if nxt_planes else None
-                with timed("spmm_csr", 3.0 * n * fout * 4 + 8.0 * csr.indices.numel() + 4.0 * (n + 1)):
-                    check(lib.gte_spmm_csr_accumulate_ln_p3(P(csr.indptr), P(csr.indices), P(w_in), P(t) + 4 * fout, 2 * fout, P(t),
-                                                            2 * fout, n, fout, _lib.REDUCE_MEAN, P(L.lynorm.weight),
-                                                            P(L.lynorm.bias), float(L.lynorm.eps), int(relu),
-                                                            None if nxt_planes else P(y), fout,
-                                                            P(yp.data) if yp is not None else None, yp.ldp if yp is not None else 0,
-                                                            P(b["stats"][i]), st), "gte_spmm_csr_accumulate_ln_p3")
-                h, hp_in = y, yp
-                continue
-            hp_in = None
-            if self._narrow(L, fin):
-                # class-count-wide layer: logits = h W_s^T + b + mean-aggregate(h W_n^T)  (aggregation on C columns)
-                with timed("narrow_fwd", 2.0 * n * fin * 4):
-                    if pending_ln is not None:
-                        # the layer below left its pre-LayerNorm z: normalise, write y / stats and multiply in one pass
-                        Lb, zb, yb, sb = pending_ln
-                        check(lib.gte_sage_narrow_fwd_ln(P(zb), ld(zb), fin, P(Lb.lynorm.weight), P(Lb.lynorm.bias),
-                                                         float(Lb.lynorm.eps), int(Lb.activation is not None), P(yb), fin, P(sb),
-                                                         P(W), 2 * fin, P(bias), fout, P(y), fout, P(b["tn"]), fout, n, st),
-                              "gte_sage_narrow_fwd_ln")
-                        pending_ln = None
-                    else:
-                        check(lib.gte_sage_narrow_fwd(P(h), ld(h), fin, P(W), 2 * fin, P(bias), fout, P(y), fout, P(b["tn"]),
-                                                      fout, n, st), "gte_sage_narrow_fwd")
-                fused_head = self._fused_head(i, L, fin)
-                if not fused_head:
-                    aggregate(csr, w_in, None, b["tn"], fout, y, fout, fout, _lib.REDUCE_MEAN, True)
-                h = y
-                continue
-            if self._transform_first(L, fin):
-                t = b["t"][i]
-                with timed("gemm_nt", 4.0 * n * fin * fout) as tm:
-                    for _ in tm.repeat():
-                        check(lib.gte_sage_transform_fwd(P(h), ld(h), fin, P(W), 2 * fin, P(bias), fout, P(t), 2 * fout, n,
-                                                         st), "gte_sage_transform_fwd")
-                if (fout % 4 == 0 and lib.gte_spmm_csr_accumulate_ln_supported(fout)
-                        and not (t_in is not None and ops.use_tiled(n, fout, csr.indices.numel(), fused_ln=True))):
-                    # z = t_self + mean-aggregate(t_neigh) and y = relu(LayerNorm(z)) in one pass over the rows
-                    with timed("spmm_csr", 3.0 * n * fout * 4 + 8.0 * csr.indices.numel() + 4.0 * (n + 1)):
-                        check(lib.gte_spmm_csr_accumulate_ln(P(csr.indptr), P(csr.indices), P(w_in), P(t) + 4 * fout, 2 * fout,
-                                                             P(t), 2 * fout, n, fout, _lib.REDUCE_MEAN, P(L.lynorm.weight),
-                                                             P(L.lynorm.bias), float(L.lynorm.eps), int(relu), P(y), fout,
-                                                             P(b["stats"][i]), st), "gte_spmm_csr_accumulate_ln")
-                else:
-                    aggregate(csr, w_in, t_in, P(t) + 4 * fout, 2 * fout, t, 2 * fout, fout, _lib.REDUCE_MEAN, True)
-                    check(lib.gte_ln_relu_fwd(P(t), 2 * fout, P(L.lynorm.weight), P(L.lynorm.bias), float(L.lynorm.eps),
-                                              int(relu), P(y), fout, P(b["stats"][i]), n, fout, st), "gte_ln_relu_fwd")
-                h = y
-                continue
-            aggregate(csr, w_in, t_in, h, ld(h), ahn, fin, fin, _lib.REDUCE_MEAN, False)
-            if ln and lib.gte_sage_linear_fwd_fuses_ln(2 * fin, fout):
-                # short K (BBOX features, 13 + 13 inputs): linear + LayerNorm + ReLU in one pass over the rows; when the next
-                # layer is a planes layer its input image is written by the same pass (and y itself is not needed)
-                zs = None if self._smallk_bwd(i, L, fin) else P(b["z"][i])   # (the one-pass backward recomputes z)
-                if i + 1 < len(layers) and b["pl"][i + 1] and fout % 16 == 0:
-                    yp = b["hp"][i + 1]
-                    check(lib.gte_sage_linear_fwd_p3(P(h), ld(h), fin, P(ahn), fin, fin, P(W), 2 * fin, P(bias), P(L.lynorm.weight),
-                                                     P(L.lynorm.bias), float(L.lynorm.eps), int(relu), zs, fout,
-                                                     P(b["stats"][i]), None, fout, P(yp.data), yp.ldp, n, fout, st),
-                          "gte_sage_linear_fwd_p3")
-                    h, hp_in = y, yp
-                    continue
-                check(lib.gte_sage_linear_fwd(P(h), ld(h), fin, P(ahn), fin, fin, P(W), 2 * fin, P(bias), P(L.lynorm.weight),
-                                              P(L.lynorm.bias), float(L.lynorm.eps), int(relu), zs, fout,
-                                              P(b["stats"][i]), P(y), fout, n, fout, st), "gte_sage_linear_fwd")
-                h = y
-                continue
-            lin_out = b["z"][i] if ln else y
-            with timed("gemm_nt", 4.0 * n * fin * fout) as tm:
-                for _ in tm.repeat():
-                    check(lib.gte_sage_linear_fwd(P(h), ld(h), fin, P(ahn), fin, fin, P(W), 2 * fin, P(bias), None, None,
-                                                  1e-5, int(relu and not ln), None, 0, None, P(lin_out), fout, n, fout, st),
-                          "gte_sage_linear_fwd")
-            if ln:
-                nxt = layers[i + 1] if i + 1 < len(layers) else None
-                if (self.fuse_ln_fwd and nxt is not None and i + 1 == len(layers) - 1 and self._narrow(nxt, fout)
-                        and lib.gte_sage_narrow_fwd_ln_supported(fout, nxt.out_feats)):
-                    pending_ln = (L, lin_out, y, b["stats"][i])
-                else:
-                    check(lib.gte_ln_relu_fwd(P(lin_out), fout, P(L.lynorm.weight), P(L.lynorm.bias), float(L.lynorm.eps),
-                                              int(relu), P(y), fout, P(b["stats"][i]), n, fout, st), "gte_ln_relu_fwd")
-            h = y
-        logits = h
-
-        # ---------------- loss ----------------
-        lab = labels if labels.dtype in (torch.float32, torch.int64) else labels.to(torch.int64)
-        dl = b["dy"][-1]
-        self._head_scale = None
-        if fused_head:
-            # one launch: logits += mean-aggregate(t_neigh), CE terms, UNNORMALISED gradient; 1 / sum(w) is applied (and
-            # the loss published) by the output layer's backward kernel -- see gte_head_agg_ce in include/gte.h
-            with timed("spmm_csr", 2.0 * n * logits.shape[1] * 4 + 8.0 * csr.indices.numel() + 4.0 * (n + 1)):
-                check(lib.gte_head_agg_ce(P(csr.indptr), P(csr.indices), P(w_in), P(b["tn"]), logits.shape[1], P(logits),
-                                          logits.shape[1], P(lab), int(lab.dtype == torch.float32), P(self.class_weights), n,
-                                          logits.shape[1], _lib.REDUCE_MEAN, P(dl), dl.shape[1], P(b["ce_part"]),
-                                          b["ce_part"].numel(), st), "gte_head_agg_ce")
-            self._head_scale = float(grad_scale)
-        else:
-            check(lib.gte_weighted_ce(P(logits), logits.shape[1], P(lab), int(lab.dtype == torch.float32),
-                                      P(self.class_weights), n, logits.shape[1], float(grad_scale), P(dl), dl.shape[1],
-                                      P(b["out3"]), ws, wsn, st), "gte_weighted_ce")
-
-    def _backward(self, g, b, layers, x, n, aggregate, rcsr, w_out, t_out, st, hi, lo) -> None:
-        lib, P, check = self.lib, _lib.ptr, _lib.check
-        timed, ld = ops._timed, ops._ld
-        ws, wsn = P(b["ws"]), b["ws"].numel()
-        for i in range(hi, lo - 1, -1):
-            L = layers[i]
-            hin = x if i == 0 else b["y"][i - 1]
-            fin, fout = (L.linear.weight.shape[1] // 2), L.out_feats
-            W = L.linear.weight
-            ln = isinstance(L.lynorm, nn.LayerNorm)
-            relu = L.activation is not None
-            dy = b["dy"][i]
-            gW = self._gslice[id(W)]
-            gb = self._gslice[id(L.linear.bias)] if L.linear.bias is not None else None
-            gg = self._gslice[id(L.lynorm.weight)] if ln else None
-            gbe = self._gslice[id(L.lynorm.bias)] if ln else None
-            if self._narrow(L, fin):
-                # q = A_w^T (norm * dlogits) on C columns; dW = [dl^T h | q^T h], dh = dl W_s + q W_n, dbias = colsum(dl)
-                aggregate(rcsr, w_out, None, dy, fout, b["q"], fout, fout, _lib.REDUCE_SUM, False)
-                dh = b["dy"][i - 1] if i > 0 else None
-                with timed("narrow_bwd", 3.0 * n * fin * 4):
-                    if self._ln_rows_below(i, layers, fin, b):
-                        # the LayerNorm(+ReLU) backward of the planes layer below on the dh tile of every row block (row form):
-                        # d(loss)/d(y) of that layer is never stored, its dz comes out as fp32 + image
-                        Lb, gsl, dzb, wsl = layers[i - 1], self._gslice, b["dzp"][i - 1], b["ws_ln"][i - 1]
-                        hs = self._head_scale
-                        check(lib.gte_sage_narrow_bwd_ln_p3(
-                            P(dy), fout, P(b["q"]), fout, P(hin), ld(hin), fin, P(W), 2 * fin, fout, P(dh), fin,
-                            P(dzb.data), dzb.ldp,
-                            P(gW), 2 * fin, P(gb), n, P(b["ws_nar"]), b["ws_nar"].numel(), P(b["ce_part"]) if hs is not None else None,
-                            hs if hs is not None else 1.0, P(b["out3"]) if hs is not None else None, P(b["t"][i - 1]), 2 * fin,
-                            P(b["stats"][i - 1]), P(Lb.lynorm.weight), P(Lb.lynorm.bias), int(Lb.activation is not None),
-                            P(gsl[id(Lb.lynorm.weight)]), P(gsl[id(Lb.lynorm.bias)]), P(gsl[id(Lb.linear.bias)]), P(wsl), wsl.numel(),
-                            st), "gte_sage_narrow_bwd_ln_p3")
-                        self._ln_p3_done = i - 1
-                    elif self._head_scale is not None and i == len(layers) - 1:
-                        check(lib.gte_sage_narrow_bwd_ce(P(dy), fout, P(b["q"]), fout, P(hin), ld(hin), fin, P(W), 2 * fin, fout,
-                                                         P(dh), fin, P(gW), 2 * fin, P(gb), n, P(b["ws_nar"]),
-                                                         b["ws_nar"].numel(), P(b["ce_part"]), self._head_scale, P(b["out3"]),
-                                                         st), "gte_sage_narrow_bwd_ce")
-                    else:
-                        check(lib.gte_sage_narrow_bwd(P(dy), fout, P(b["q"]), fout, P(hin), ld(hin), fin, P(W), 2 * fin, fout,
-                                                      P(dh), fin, P(gW), 2 * fin, P(gb), n, P(b["ws_nar"]),
-                                                      b["ws_nar"].numel(), st), "gte_sage_narrow_bwd")
-                continue
-            if b["pl"][i]:
-                # ---- planes layer: dz (fp32 for the transpose aggregation + image), q = A_w^T (norm dz) as an image,
-                # dW = [dz^T h | q^T h] and dh = dz W_s + q W_n on the planes GEMMs
-                t, dzp, qp, hp = b["t"][i], b["dzp"][i], b["qp"][i], b["hp_used"][i]
-                if self._ln_p3_done != i:         # (else: the launch above ran this layer's LayerNorm backward as its epilogue)
-                    check(lib.gte_ln_relu_bwd_p3(P(dy), fout, P(t), 2 * fout, P(b["stats"][i]), P(L.lynorm.weight),
-                                                 P(L.lynorm.bias), int(relu), P(dy), fout, P(dzp.data), dzp.ldp, P(gg), P(gbe), P(gb),
-                                                 n, fout, P(b["ws_ln"][i]), b["ws_ln"][i].numel(), st), "gte_ln_relu_bwd_p3")
-                with timed("spmm_csr", 2.0 * n * fout * 4 + 8.0 * rcsr.indices.numel() + 4.0 * (n + 1)):
-                    check(lib.gte_spmm_csr_p3(P(rcsr.indptr), P(rcsr.indices), P(w_out), P(dy), fout, P(qp.data), qp.ldp, n, fout,
-                                              _lib.REDUCE_SUM, st), "gte_spmm_csr_p3")
-                if i == 0 and self.before_last_gemm is not None:
-                    self.before_last_gemm()
-                wsp = b["ws_p3"][i]
-
-                def dw_planes(stream):
-                    if hp.row_map is not None:
-                        check(lib.gte_gemm_p3_tn_rows(P(dzp.data), dzp.ldp, P(qp.data), qp.ldp, P(hp.data), hp.ldp, P(hp.row_map),
-                                                      hp.res_rows, fin, P(gW), 2 * fin, fout, 2 * fin, n, P(wsp), wsp.numel(), stream),
-                              "gte_gemm_p3_tn_rows")
-                    else:
-                        check(lib.gte_gemm_p3_tn(P(dzp.data), dzp.ldp, P(qp.data), qp.ldp, P(hp.data), hp.ldp, None, 0, fin, P(gW),
-                                                 2 * fin, fout, 2 * fin, n, P(wsp), wsp.numel(), stream), "gte_gemm_p3_tn")
-                with timed("gemm_tn", 4.0 * n * fin * fout) as tm:
-                    for _ in tm.repeat():
-                        dw_planes(st)
-                if i > 0:
-                    wb = self._wimg[i][1]
-                    Lb = layers[i - 1]
-                    fin_b = Lb.linear.weight.shape[1] // 2
-                    if (self.fuse_smallk_dx and i == 1 and self._smallk_bwd(0, Lb, fin_b)
-                            and lib.gte_gemm_p3_nt_smallk_bwd_supported(2 * fin_b, fin)):
-                        # dX with the WHOLE backward of the short-input layer below as its epilogue: nothing of layer 0 is left
-                        gsl, wsd = self._gslice, b["ws_dw"][0]
-                        check(lib.gte_gemm_p3_nt_smallk_bwd(P(dzp.data), dzp.ldp, fout, P(qp.data), qp.ldp, fout, P(wb.data), wb.ldp,
-                                                            P(x), ld(x), fin_b, P(b["ahn"][0]), fin_b, fin_b, P(Lb.linear.weight),
-                                                            2 * fin_b, P(Lb.linear.bias), P(Lb.lynorm.weight), P(Lb.lynorm.bias),
-                                                            P(b["stats"][0]), int(Lb.activation is not None), P(gsl[id(Lb.linear.weight)]),
-                                                            2 * fin_b, P(gsl[id(Lb.linear.bias)]), P(gsl[id(Lb.lynorm.weight)]),
-                                                            P(gsl[id(Lb.lynorm.bias)]), n, fin, P(wsd), wsd.numel(), st),
-                              "gte_gemm_p3_nt_smallk_bwd")
-                        self._smallk_done = True
-                    elif self.fuse_ln_dx and b["pl"][i - 1] and lib.gte_gemm_p3_nt_ln_bwd_supported(fin):
-                        # dX with the LayerNorm(+ReLU) backward of the layer below as its epilogue: d(loss)/d(y) of that layer
-                        # is never stored, its dz comes out as fp32 + image
-                        gsl, dzb, wsl = self._gslice, b["dzp"][i - 1], b["ws_ln"][i - 1]
-                        check(lib.gte_gemm_p3_nt_ln_bwd(P(dzp.data), dzp.ldp, fout, P(qp.data), qp.ldp, fout, P(wb.data), wb.ldp,
-                                                        P(b["t"][i - 1]), 2 * fin, P(b["stats"][i - 1]), P(Lb.lynorm.weight),
-                                                        P(Lb.lynorm.bias), int(Lb.activation is not None), P(b["dy"][i - 1]), fin,
-                                                        P(dzb.data), dzb.ldp, P(gsl[id(Lb.lynorm.weight)]), P(gsl[id(Lb.lynorm.bias)]),
-                                                        P(gsl[id(Lb.linear.bias)]), n, fin, P(wsl), wsl.numel(), st),
-                              "gte_gemm_p3_nt_ln_bwd")
-                        self._ln_p3_done = i - 1
-                    else:
-                        with timed("gemm_nn", 4.0 * n * fin * fout) as tm:
-                            for _ in tm.repeat():
-                                check(lib.gte_gemm_p3_nt(P(dzp.data), dzp.ldp, fout, P(qp.data), qp.ldp, fout, P(wb.data), wb.ldp, None,
-                                                         0, P(b["dy"][i - 1]), fin, n, fin, 0, 0, st), "gte_gemm_p3_nt dX")
-                continue
-            if self._smallk_bwd(i, L, fin) and self._smallk_done:
-                if self.before_last_gemm is not None:                  # (its backward ran as the epilogue of the layer above's dX)
-                    self.before_last_gemm()
-                continue
-            if self._smallk_bwd(i, L, fin):
-                # short-input layer 0: LayerNorm(+ReLU) backward and dW in ONE pass over dy (z recomputed, dz never stored)
-                if self.before_last_gemm is not None:
-                    self.before_last_gemm()
-                wdw = b["ws_dw"][i]
-                check(lib.gte_sage_smallk_bwd(P(dy), fout, P(hin), ld(hin), fin, P(b["ahn"][i]), fin, fin, P(W), 2 * fin,
-                                              P(L.linear.bias), P(L.lynorm.weight), P(L.lynorm.bias), P(b["stats"][i]), int(relu),
-                                              P(gW), 2 * fin, P(gb), P(gg), P(gbe), n, fout, P(wdw), wdw.numel(), st),
-                      "gte_sage_smallk_bwd")
-                continue
-            tfirst, qform = self._transform_first(L, fin), self._qform(i, L, fin)
-            zsrc = b["t"][i] if tfirst else (b["z"][i] if ln else b["y"][i])
-            # dz in place of dy; column sums straight into the flat gradient
-            check(lib.gte_ln_relu_bwd(P(dy), fout, P(zsrc), 2 * fout if tfirst else fout, P(b["stats"][i]) if ln else None,
-                                      P(L.lynorm.weight) if ln else None, P(L.lynorm.bias) if ln else None, int(relu),
-                                      P(dy), fout, P(gg), P(gbe), P(gb), n, fout, P(b["ws_ln"][i]), b["ws_ln"][i].numel(),
-                                      st), "gte_ln_relu_bwd")
-            dz, ahn = dy, b["ahn"][i]
-            if qform:
-                # q = A_w^T (norm * dz) into the dead right half of t (transform-first) or the dead ahn buffer
-                qp, ldq = (P(b["t"][i]) + 4 * fout, 2 * fout) if tfirst else (P(ahn), fin)
-                aggregate(rcsr, w_out, t_out, dz, fout, qp, ldq, fout, _lib.REDUCE_SUM, False)
-            # dW is MFMA-bound and nothing downstream needs it before Adam; the rest of the backward chain (dX, the
-            # transpose aggregation, the next LayerNorm backward) is mostly HBM-bound: run dW on the side stream so
-            # the two kinds of work share the chip.  dz (= dy_i, final for this step) and ahn/h are read-only here.
-            wdw = b["ws_dw"][i]
-            if i == 0 and self.before_last_gemm is not None:
-                self.before_last_gemm()
-
-            def dw_launch(stream):
-                if qform:
-                    check(lib.gte_sage_qform_dw(P(dz), fout, qp, ldq, P(hin), ld(hin), fin, P(gW), 2 * fin, fout, n, P(wdw),
-                                                wdw.numel(), stream), "gte_sage_qform_dw")
-                else:
-                    check(lib.gte_sage_linear_dw(P(dz), fout, P(hin), ld(hin), fin, P(ahn), fin, fin, P(gW), 2 * fin, fout,
-                                                 n, P(wdw), wdw.numel(), stream), "gte_sage_linear_dw")
-            with timed("gemm_tn", 4.0 * n * fin * fout) as tm:
-                for _ in tm.repeat():
-                    dw_launch(st)
-            if i > 0 and qform:
-                with timed("gemm_nn", 4.0 * n * fin * fout) as tm:
-                    for _ in tm.repeat():
-                        check(lib.gte_sage_qform_dx(P(dz), fout, qp, ldq, P(W), 2 * fin, fin, fout, P(b["dy"][i - 1]), fin, n,
-                                                    st), "gte_sage_qform_dx")
-            elif i > 0:
-                dh, dahn = b["dy"][i - 1], b["dahn"]
-                with timed("gemm_nn", 4.0 * n * fin * fout):
-                    check(lib.gte_gemm_f32(0, 0, n, fin, fout, P(dz), fout, P(W), 2 * fin, P(dh), fin, 0, ws, wsn, st),
-                          "gte_gemm_f32 dh_self")
-                    check(lib.gte_gemm_f32(0, 0, n, fin, fout, P(dz), fout, P(W) + 4 * fin, 2 * fin, P(dahn), fin, 0, ws,
-                                           wsn, st), "gte_gemm_f32 dh_neigh")
-                aggregate(rcsr, w_out, t_out, dahn, fin, dh, fin, fin, _lib.REDUCE_SUM, True)
+        self._calls.run(g, None, 1.0, from_layer - 1, 0, forward=False)
 
     def step(self, g, labels: torch.Tensor, n_global: Optional[int] = None,
              loss_scale: Optional[float] = None) -> torch.Tensor:
@@ -1460,7 +951,7 @@ class FusedGcnSageStep(TrainStep):
                 float(np.float32(1.0 - c1 ** t_next)), float(np.float32(np.sqrt(1.0 - c2 ** t_next))))
 
     def _adam_state(self) -> None:
-        if getattr(self, "_hyper", None) is None:
+        if self._hyper is None:
             dev = self.flat_param.device
             self._hyper_host = self._adam_host_state(1)
             self._hyper = torch.tensor(self._hyper_host, dtype=torch.float32, device=dev)
@@ -1486,8 +977,7 @@ class FusedGcnSageStep(TrainStep):
     def _adam_dev_launch(self) -> None:
         P = _lib.ptr
         self._wimg_sig = None
-        last = getattr(self, "_last_wimg", None)
-        self._last_wimg = None
+        last, self._last_wimg = self._last_wimg, None
         if (last is not None and self.wimg_in_fold and 0 < last[1] <= 12 and not torch.cuda.is_current_stream_capturing()):
             # the optimiser launch behind the all-reduce also writes the weight images of the step that just ran (one launch instead
             # of Adam + a conversion launch in front of the next forward: the one-GPU step has both inside its fold launch)

@@ -13,8 +13,8 @@ masks has no branch left to disagree on: every remaining difference is device ro
 Where ``z`` lives (``device_relu_masks``):
   * one-call plan (engine._alloc_plan, found through engine.plan_buffers): ``t[i]``, columns [0, fout) -- a planes layer's
     [z | t_neigh] (z accumulated into the left half), or the aggregate-first / cached input layer's z;
-  * the call-by-call schedule (engine._alloc): ``t[i]`` (left half) where the layer has one (transform-first or planes layer),
-    else ``z[i]``;
+  * the call-by-call schedule (models/call_schedule.py, CallSchedule._alloc, found through engine._calls.buffer_set): ``t[i]``
+    (left half) where the layer has one (transform-first or planes layer), else ``z[i]``;
   * the one-pass short-input layer (BBOX features, gte_sage_smallk_bwd / gte_gemm_p3_nt_smallk_bwd) does NOT save z: its
     backward recomputes z with the forward kernel's instruction sequence (csrc/smallk_step.h: bit-identical z) and reads the
     forward's stats.  The forward wrote y = fmaxf(fmaf(xh, gamma, beta), 0) from that same z, so there the mask is ``y > 0``
@@ -49,7 +49,7 @@ def _layer_buffers(engine, batch):
     on_plan = engine.plan_buffers(batch)
     if on_plan is not None:
         return on_plan + (n, f0)
-    return engine._bufs[(f0, engine._planes_on())], None, False, n, f0
+    return engine._calls.buffer_set(batch), None, False, n, f0
 
 
 def device_relu_masks(engine, batch, state) -> list:

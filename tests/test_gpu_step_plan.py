@@ -1,4 +1,4 @@
-"""gte_gcnsage_step (the whole optimisation step as one host call) against the call-by-call schedule of models/engine.py."""
+"""gte_gcnsage_step (the whole optimisation step as one host call) against the call-by-call schedule of models/call_schedule.py."""
 import numpy as np
 import pytest
 import torch
