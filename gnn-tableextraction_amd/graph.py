@@ -18,7 +18,7 @@ the user set it; the CSR-ordered copies are cached per tensor version.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -715,6 +715,56 @@ def bbox_features(bbox: torch.Tensor, char_counts: torch.Tensor) -> torch.Tensor
     _lib.check(_lib.load().gte_bbox_features(_lib.ptr(bbox), _lib.ptr(counts), _lib.ptr(out), 13, bbox.shape[0],
                                              _lib.current_stream()), "gte_bbox_features")
     return out
+
+
+# ---- page regions from node predictions ------------------------------------------------------------------
+# group id of each of the 9 converted classes = the reference's ORIGINAL category value (src/utils/const.py Categories_names):
+# other -> no region, text 1, title 2, list 3, figure 5, caption 6, and the three table classes (column header, spanning cell,
+# table cell) -> 4, the TABLE category that "has no nodes" upstream.
+DEFAULT_CLASS_GROUP = (-1, 1, 2, 3, 5, 6, 4, 4, 4)
+GROUP_NAMES = {1: "text", 2: "title", 3: "list", 4: "table", 5: "figure", 6: "caption"}      # lower-case category names
+
+
+class PageRegions(NamedTuple):
+    """Result of :func:`page_regions`: ``comp`` per node, then the regions in ascending root order."""
+    comp: torch.Tensor        # int32 [n]    smallest node id of the node's region, -1 for nodes outside every region
+    root: torch.Tensor        # int64 [R]    the region's smallest node
+    page: torch.Tensor        # int64 [R]    page of the batch
+    group: torch.Tensor       # int32 [R]    region kind
+    box: torch.Tensor         # int32 [R, 4] union of the words' boxes (x0, y0, x1, y1)
+    n_words: torch.Tensor     # int32 [R]
+
+
+def page_regions(g: PageGraph, group: torch.Tensor, bbox: torch.Tensor) -> PageRegions:
+    """Regions of a batched page graph (a :class:`PageGraph` from :func:`batch` / :func:`knn_graph_from_boxes`, or a
+    :class:`ResidentBatch`): the connected components of ``g`` restricted to nodes of one ``group`` (int [n]; < 0: in no region),
+    each with the union of its words' boxes (``bbox`` int [n, 4]) -- one launch of gte_page_regions over ``g.in_csr()`` and the
+    batch's page offsets, then a torch compaction of the root rows (``nonzero`` on the counts: plumbing, one synchronisation)."""
+    _lib.require_device(group, "page_regions")
+    _lib.require_device(bbox, "page_regions")
+    lib, P = _lib.load(), _lib.ptr
+    dev = group.device
+    n = g.num_nodes()
+    group = group.to(torch.int32).contiguous()
+    bbox = bbox.to(torch.int32).contiguous()
+    if group.numel() != n or tuple(bbox.shape) != (n, 4):
+        raise ValueError(f"page_regions: the graph has {n} nodes, group has {group.numel()} entries, bbox is {tuple(bbox.shape)}")
+    sizes = torch.as_tensor(g.batch_num_nodes_, dtype=torch.int64)
+    if int(sizes.sum()) != n:
+        raise ValueError(f"page_regions: the pages of the batch hold {int(sizes.sum())} nodes, the graph {n}")
+    node_off_h = torch.zeros(sizes.numel() + 1, dtype=torch.int64)
+    node_off_h[1:] = torch.cumsum(sizes, 0)
+    node_off = node_off_h.to(torch.int32).to(dev)
+    csr = g.in_csr()
+    _lib.require_device(csr.indptr, "page_regions")
+    comp = torch.empty(n, dtype=torch.int32, device=dev)
+    rbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(lib.gte_page_regions(P(csr.indptr), P(csr.indices), P(node_off), sizes.numel(), n, int(sizes.max()) if sizes.numel() else 0,
+                                    P(group), P(bbox), P(comp), P(rbox), P(count), _lib.current_stream()), "gte_page_regions")
+    root = torch.nonzero(count).flatten()
+    page = torch.bucketize(root, node_off[1:].long(), right=True)
+    return PageRegions(comp, root, page, group[root], rbox[root], count[root])
 
 
 def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, max_dist: int = 500, bidirectional: bool = True,

@@ -13,6 +13,8 @@ Output contract (what post-processing consumes):
                                       'wb'))`` of model_predict.py:151,172-174; ``postprocessing.py:199-216`` slices it
                                       back into pages by ``graph.num_nodes()``
   ``{output}/predictions/{logs}.pkl`` extra, not in the reference: ``{'all_pred': [per-page lists], 'num_nodes': [...]}``
+  ``{output}/regions/{logs}.json``    ``test(..., regions=True)`` only: the regions of every page (``extract_regions``) in the layout
+                                      the reference's box-level evaluation reads (``regions_json``)
 The printed accuracy is the reference's "Mean Test Accuracy": the MEAN OVER PAGES of the per-page accuracy (:150,163),
 not the node-weighted accuracy (returned as ``accuracy_nodes``).
 """
@@ -156,7 +158,65 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None) -> torch.Ten
     return pred
 
 
-def test(data, config, weights_path=None, save_predictions=True):
+def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=64, device=None):
+    """Regions of every page from the node predictions: connected components of the page graph among words of one predicted
+    kind, each with the union of its words' boxes (``graph.page_regions`` -> gte_page_regions; the reference's
+    ``get_subgraph_bbox`` is a stub, its PyMuPDF block voting is out of scope -- DESIGN 10).
+
+    ``all_pred``: per-page class ids in ``data.graphs`` order (``test()``'s ``'all_pred'``);
+    ``class_group[c]`` = region kind of class c, < 0 for none (default ``graph.DEFAULT_CLASS_GROUP``: the reference's category
+    values, the three table classes merged into TABLE = 4); boxes from ``data.pages[i]['bboxs']``.  ``batch_pages`` pages go
+    through one launch.  Returns, per page, a list of ``(group, [x0, y0, x1, y1], n_words)`` in ascending order of the region's
+    first word; regions of fewer than ``min_words`` words are dropped after the compaction."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    sizes = [g.num_nodes() for g in data.graphs]
+    if len(all_pred) != len(sizes):
+        raise ValueError(f"extract_regions: {len(all_pred)} prediction lists for {len(sizes)} pages")
+    table = torch.as_tensor(G.DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32, device=device)
+    out = [[] for _ in sizes]
+    bp = max(1, int(batch_pages))
+    for b0 in range(0, len(sizes), bp):
+        ids = range(b0, min(b0 + bp, len(sizes)))
+        if sum(sizes[i] for i in ids) == 0:
+            continue
+        parts = []
+        for i in ids:
+            h = data.graphs[i].local_var()                # the structure alone: no feature rows travel for this
+            h.ndata.clear()
+            h.edata.clear()
+            parts.append(h.to(device))
+        bg = G.batch(parts)
+        pred = np.concatenate([np.asarray(all_pred[i], dtype=np.int64).reshape(-1) for i in ids])
+        boxes = np.concatenate([np.asarray(data.pages[i]['bboxs'], dtype=np.int32).reshape(-1, 4) for i in ids])
+        if pred.shape[0] != bg.num_nodes() or boxes.shape[0] != bg.num_nodes():
+            raise ValueError(f"extract_regions: pages {ids.start}..{ids.stop - 1} have {bg.num_nodes()} nodes, {pred.shape[0]} "
+                             f"predictions and {boxes.shape[0]} boxes")
+        group = table[torch.from_numpy(pred).to(device)]                                  # class -> kind: a gather
+        reg = G.page_regions(bg, group, torch.from_numpy(boxes).to(device))
+        keep = reg.n_words >= int(min_words)
+        for p, k, bx, nw in zip(reg.page[keep].tolist(), reg.group[keep].tolist(), reg.box[keep].tolist(), reg.n_words[keep].tolist()):
+            out[b0 + p].append((k, bx, nw))
+    return out
+
+
+def regions_json(data, regions):
+    """``{kind_name: {page_name: {'bboxes': [...], 'scores': [...]}}}``: the layout the reference's box-level evaluation reads
+    (postprocessing.py:326-345 write_json -> utils/metrics.py), kind names = the lower-case category names; every score is
+    1.0, as in the reference's own writer."""
+    doc = {name: {} for name in G.GROUP_NAMES.values()}
+    for i, page in enumerate(regions):
+        name = str(data.pages[i]['page'])
+        for kind, box, _ in page:
+            entry = doc.setdefault(G.GROUP_NAMES.get(kind, str(kind)), {}).setdefault(name, {'bboxes': [], 'scores': []})
+            entry['bboxes'].append([int(v) for v in box])
+            entry['scores'].append(1.0)
+    return doc
+
+
+def test(data, config, weights_path=None, save_predictions=True, regions=False):
+    """``regions=True``: the result gains ``'regions'`` (``extract_regions`` of the predictions: per page a list of
+    ``(group, [x0, y0, x1, y1], n_words)``), and with ``save_predictions`` ``{output}/regions/{logs}.json`` is written
+    (``regions_json``).  No region confidence exists yet: every score in that file is 1.0."""
     if not (config.TRAINING.gpu >= 0 and torch.cuda.is_available()):
         raise RuntimeError("model_predict runs on the MI355X HIP path only (no CPU fallback)")
     device = torch.device('cuda', config.TRAINING.gpu)
@@ -226,5 +286,14 @@ def test(data, config, weights_path=None, save_predictions=True):
         os.makedirs(pred_dir, exist_ok=True)
         with open(os.path.join(pred_dir, f'{logs}.pkl'), 'wb') as f:
             pickle.dump({'all_pred': [a.tolist() for a in all_pred], 'num_nodes': [len(a) for a in all_pred]}, f)
-    return {'accuracy': acc, 'accuracy_nodes': acc_nodes, 'precision': p, 'recall': r, 'f1': f1, 'confusion': conf,
-            'all_pred': all_pred, 'all_pred_flat': flat}
+    result = {'accuracy': acc, 'accuracy_nodes': acc_nodes, 'precision': p, 'recall': r, 'f1': f1, 'confusion': conf,
+              'all_pred': all_pred, 'all_pred_flat': flat}
+    if regions:
+        result['regions'] = extract_regions(data, all_pred, batch_pages=bs, device=device)
+        if save_predictions:
+            import json
+            reg_dir = os.path.join(out_root, 'regions')
+            os.makedirs(reg_dir, exist_ok=True)
+            with open(os.path.join(reg_dir, f'{logs}.json'), 'w') as f:
+                json.dump(regions_json(data, result['regions']), f)
+    return result

@@ -165,6 +165,25 @@ int gte_knn_csr(const int32_t* sel, const int32_t* node_off, const int32_t* page
 int gte_island_mask(const int32_t* indptr, const int32_t* indices, const int32_t* label, int64_t n_nodes, int khop,
                     int text_label, uint8_t* island, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- page regions from node predictions (no reference counterpart: graphs/utils.py get_subgraph_bbox() is a stub) -
+ * Inputs: the in-edge CSR of the batch (rows = destinations; any CSR over the batch's nodes does: a directed one gives the answer
+ * of its symmetric closure), node_off[n_pages + 1] (node_off[0] = 0, node_off[n_pages] = n_nodes; empty pages are legal), group
+ * int32 [n_nodes] = the region kind of every node (< 0: the node belongs to no region), bbox int32 [n_nodes, 4] (x0, y0, x1, y1).
+ * Take the undirected graph on the nodes with group >= 0 that has an edge {u, v} wherever the CSR holds u -> v or v -> u and
+ * group[u] == group[v] (self loops and duplicate entries change nothing; an entry that leaves its page is skipped):
+ *   comp[v]          the smallest node id of v's connected component (global ids); -1 where group[v] < 0.  A node with
+ *                    comp[v] == v is a ROOT; a node without a same-group neighbour is a region of one word.
+ *   region_count[v]  roots: the number of members of the component; every other row 0.
+ *   region_box[v]    roots: (min x0, min y0, max x1, max y1) over the members; every other row (0, 0, 0, 0).
+ * Every row of the three outputs is written.  One launch for the batch, one workgroup per page with the page's labels in LDS
+ * (pages of at most gte_region_max_page_nodes() >= gte_knn_max_page_nodes() nodes: any page the graph builder accepts;
+ * GTE_ERR_UNSUPPORTED above); max_page_nodes = the largest page of the batch (it sizes the launch's LDS).  Integer work on LDS
+ * atomic min / max / add: deterministic.  No allocation, no workspace, no synchronisation.  bbox and region_box 16-byte aligned. */
+int gte_region_max_page_nodes(void);
+int gte_page_regions(const int32_t* indptr, const int32_t* indices, const int32_t* node_off, int64_t n_pages, int64_t n_nodes,
+                     int64_t max_page_nodes, const int32_t* group, const int32_t* bbox, int32_t* comp, int32_t* region_box,
+                     int32_t* region_count, void* stream);
+
 /* The whole batch in ONE launch (what the train loop calls every step; gte_batch_csr / gte_batch_rows are its pieces):
  * a page's rows are CONTIGUOUS in the resident arrays and in the batch, so every array of the batch is the concatenation
  * of per-page runs -- features and labels copied, indptr / indices copied with a per-page constant added.  Workgroup
