@@ -29,6 +29,22 @@ def f32_rows(g) -> torch.Tensor:
     return ops._row_major(g.ndata['feat'])
 
 
+def row_capacity(n: int, slack: bool = False) -> int:
+    """Rows a shared buffer set is allocated for: ``n`` -- with ``slack`` an eighth more, so that the set of the largest batch seen
+    so far also holds the slightly larger ones that follow -- rounded up to 4096."""
+    return -(-int(n * 1.125 if slack else n) // 4096) * 4096
+
+
+def weight_pair(W: torch.Tensor, transpose: int, img, row: int = 0, block: int = 0):
+    """The two conversion descriptors (gte_p3_desc) of a layer's weight W = [W_s | W_n] ([fout][2 fin], or transposed: [fin] x
+    [fout] each) into ONE image: the W_s half at the image's origin, then the W_n half at row ``row``, 16-column block ``block``."""
+    fout, fin = W.shape[0], W.shape[1] // 2
+    wp, ld = W.data_ptr(), W.stride(0)
+    rows, cols = (fin, fout) if transpose else (fout, fin)
+    return [_lib.P3Desc(wp, ld, rows, cols, transpose, img.at(0, 0), img.ldp),
+            _lib.P3Desc(wp + 4 * fin, ld, rows, cols, transpose, img.at(row, block), img.ldp)]
+
+
 @dataclass
 class Pass:
     """One pass of the schedule over one batch: what the batch brings, the row views of the buffer set it runs on, and what the
@@ -66,7 +82,7 @@ class CallSchedule:
 
     # -- buffers -------------------------------------------------------------------------------------
     def _alloc(self, cap: int, f0: int):
-        """Buffer set of the call-by-call schedule only; a one-call plan has its own (engine._alloc_plan)."""
+        """Buffer set of the call-by-call schedule only; a one-call plan has its own (step_plan.OneCallPlan._alloc)."""
         eng = self.eng
         dev = eng.flat_param.device
         new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
@@ -132,7 +148,7 @@ class CallSchedule:
         full = self.bufs.get(key)
         if full is None or full["cap"] < n:
             # (at least the reserved capacity: a shape whose steps usually run on a plan is not sized by reserve())
-            full = self._grow(key, max(-(-int(n * 1.125) // 4096) * 4096, eng._reserved.get(f0, 0)))
+            full = self._grow(key, max(row_capacity(n, slack=True), eng._reserved.get(f0, 0)))
         return full
 
     def _grow(self, key, cap: int):
@@ -145,7 +161,7 @@ class CallSchedule:
         key = (f0, self.eng._planes_on())
         full = self.bufs.get(key)
         if n_nodes > 0 and (full is None or full["cap"] < n_nodes):
-            self._grow(key, -(-int(n_nodes) // 4096) * 4096)
+            self._grow(key, row_capacity(n_nodes))
 
     def buffer_set(self, batch, private_key=None):
         """The buffer set a step of this schedule on ``batch`` ran on -- the shared set, or the private set of the batch captured
@@ -185,7 +201,7 @@ class CallSchedule:
     def _weight_images(self, dims):
         """The schedule's conversion launch: P3 images of the planes layers' weights, forward [W_s rows ; W_n rows]
         x fin, backward (dX) [fin rows] x [W_s^T | W_n^T].  ONE launch in front of every forward (the parameters change every step;
-        the launch is part of a captured step).  A one-call plan has its own images and descriptors (engine._weight_images_gen)."""
+        the launch is part of a captured step).  A one-call plan has its own images and descriptors (OneCallPlan.weight_images)."""
         eng = self.eng
         layers = eng.model.layers
         descs = []
@@ -196,21 +212,12 @@ class CallSchedule:
             img = self.wimg.get(i)
             if img is None:
                 # (weight images are BLOCK-MAJOR: the B operand of every NT planes GEMM -- ops.P3)
-                fwd = ops.P3.empty(2 * fout, fin, eng.flat_param.device, block_major=eng.block_major_weights)
-                fwd.data.zero_()
-                bwd = None
-                if i > 0:
-                    bwd = ops.P3.empty(fin, 2 * fout, eng.flat_param.device, block_major=eng.block_major_weights)
-                    bwd.data.zero_()
-                img = self.wimg[i] = (fwd, bwd)
+                zeros = lambda rows, cols: ops.P3.zeros(rows, cols, eng.flat_param.device, block_major=eng.block_major_weights)
+                img = self.wimg[i] = (zeros(2 * fout, fin), zeros(fin, 2 * fout) if i > 0 else None)
             fwd, bwd = img
-            W = L.linear.weight
-            wp, ld = W.data_ptr(), W.stride(0)
-            descs.append(_lib.P3Desc(wp, ld, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
-            descs.append(_lib.P3Desc(wp + 4 * fin, ld, fout, fin, 0, fwd.at(fout, 0), fwd.ldp))
+            descs += weight_pair(L.linear.weight, 0, fwd, row=fout)
             if bwd is not None:
-                descs.append(_lib.P3Desc(wp, ld, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
-                descs.append(_lib.P3Desc(wp + 4 * fin, ld, fin, fout, 1, bwd.at(0, fout // 16), bwd.ldp))
+                descs += weight_pair(L.linear.weight, 1, bwd, block=fout // 16)
         st = _lib.current_stream()
         for k in range(0, len(descs), 16):
             chunk = descs[k:k + 16]
@@ -264,12 +271,13 @@ class CallSchedule:
         full = self._begin(g) if forward else self._recorded(g)
         ps = full["_pass"]
         ps.st = _lib.current_stream()
-        eng._plan_images_stale()                      # (this schedule converts its own weight images in front of every forward)
+        # (this schedule converts its own weight images in front of every forward: the one-call plans' no longer follow the
+        # parameters, and no later optimiser launch may rewrite them)
+        eng._plan.images.stale()
         # scratch for the GEMM tail split (see gte_gemm_set_tail_workspace): registered for this launch sequence only
-        if eng._tail_ws is None:
-            eng._tail_ws = torch.empty(int(lib.gte_gemm_tail_workspace_bytes()), dtype=torch.uint8, device=eng.flat_param.device)
-        check(lib.gte_gemm_set_tail_workspace(P(eng._tail_ws) if eng.tail_split else None,
-                                              eng._tail_ws.numel() if eng.tail_split else 0), "gte_gemm_set_tail_workspace")
+        tail = eng._tail_workspace()
+        check(lib.gte_gemm_set_tail_workspace(P(tail) if eng.tail_split else None, tail.numel() if eng.tail_split else 0),
+              "gte_gemm_set_tail_workspace")
         fused = ctypes.c_int(0)
         try:
             if forward:

@@ -19,8 +19,13 @@ from typing import Optional
 
 import numpy as np
 import torch
+import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
+from .._lib import LAYER_PLANES, LAYER_SMALLK, LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT
+from ..components.graphs.models import GcnSAGE, _is_relu
+from .call_schedule import CallSchedule, batch_shape, f32_rows, row_capacity
+from .step_plan import OneCallPlan, _c16
 
 
 class TrainStep:
@@ -101,18 +106,12 @@ class TrainStep:
 # ======================================================================================================
 # Hand-scheduled step for GcnSAGE: no autograd, no per-step allocation, HIP-graph capturable
 # ======================================================================================================
-from .. import _lib                                                     # noqa: E402
-from .._lib import LAYER_PLANES, LAYER_SMALLK, LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT      # noqa: E402
-from ..components.graphs.models import GcnSAGE, _is_relu               # noqa: E402
-from .call_schedule import CallSchedule, batch_shape, f32_rows         # noqa: E402
-import torch.nn as nn                                                  # noqa: E402
-
-
 DROPOUT_MAX_ROWS = 1 << 30          # GTE_DROPOUT_MAX_ROWS of include/gte.h: nodes of a dropout plan
 
 
-def _c16(x: int) -> int:
-    return -(-int(x) // 16) * 16
+def _switch(name: str, default: str = "1") -> bool:
+    """An on / off switch of the engine, from the environment."""
+    return os.environ.get(name, default) == "1"
 
 
 class FusedGcnSageStep(TrainStep):
@@ -168,63 +167,57 @@ class FusedGcnSageStep(TrainStep):
         # about what hiding a 0.5 MB all-reduce can win back on 8 GPUs.  To be re-measured on a multi-GPU node.
         self._n0 = sum(p.numel() for p in model.layers[0].parameters() if p.requires_grad)
         first_upper = next((p for p in model.layers[1].parameters() if p.requires_grad), None) if len(model.layers) > 1 else None
-        self._dp_split = (os.environ.get("GTE_DP_OVERLAP", "0") == "1" and first_upper is not None and self.dropout_p == 0
+        self._dp_split = (_switch("GTE_DP_OVERLAP", "0") and first_upper is not None and self.dropout_p == 0
                           and self._gslice[id(first_upper)].storage_offset() == self._n0)
-        self._bufs = {}                               # one-call plans: _plan_key -> capacity-sized shared buffer set
         self._graph_bufs = {}                         # (captured batch, buffer-set key of either schedule) -> its private set
         self._reserved = {}                           # input width -> capacity asked for by reserve()
         self._calls = CallSchedule(self)              # the call-by-call schedule: its own buffer sets and weight images
+        self._plan = OneCallPlan(self)                # the one-call plans: their buffer sets, weight images and the images' freshness
         self._private_key = None
         self._graphs = {}
         self._graph_owner = {}
         # transform-then-aggregate where a layer narrows + q-form backward (see _transform_first / _qform); "0" keeps
         # the reference's aggregate-then-transform order everywhere (same math, different summation order)
-        self.transform_first = os.environ.get("GTE_TRANSFORM_FIRST", "1") == "1"
-        self.tail_split = os.environ.get("GTE_TAIL_SPLIT", "1") == "1"
+        self.transform_first = _switch("GTE_TRANSFORM_FIRST")
+        self.tail_split = _switch("GTE_TAIL_SPLIT")
         # single-GPU steps: the Adam update runs inside the gradient-fold launch (gte_fold_defer_flush_adam)
-        self.fuse_adam = os.environ.get("GTE_FUSE_ADAM", "1") == "1"
+        self.fuse_adam = _switch("GTE_FUSE_ADAM")
         self._fuse_adam_req, self._adam_fused = False, False
         self.adam_fused_steps = 0                     # steps whose optimiser update ran inside the fold launch
-        self.fused_head = os.environ.get("GTE_FUSED_HEAD", "1") == "1"
-        self.fuse_head_gemm = os.environ.get("GTE_FUSE_HEAD_GEMM", "1") == "1"     # (out_gemm plans: the fused head on the GEMM output path)
+        self.fused_head = _switch("GTE_FUSED_HEAD")
+        self.fuse_head_gemm = _switch("GTE_FUSE_HEAD_GEMM")     # (out_gemm plans: the fused head on the GEMM output path)
         # dX of a planes layer with the LayerNorm(+ReLU) backward of the planes layer below as its epilogue (gte_gemm_p3_nt_ln_bwd)
-        self.fuse_ln_dx = os.environ.get("GTE_FUSE_LN_DX", "1") == "1"
+        self.fuse_ln_dx = _switch("GTE_FUSE_LN_DX")
         # ... and of the last hidden layer inside the output layer's backward (gte_sage_narrow_bwd_ln_p3)
-        self.fuse_ln_narrow = os.environ.get("GTE_FUSE_LN_NARROW", "1") == "1"
+        self.fuse_ln_narrow = _switch("GTE_FUSE_LN_NARROW")
         # dX of layer 1 with the whole backward of a short-input layer 0 as its epilogue (gte_gemm_p3_nt_smallk_bwd)
-        self.fuse_smallk_dx = os.environ.get("GTE_FUSE_SMALLK_DX", "1") == "1"
+        self.fuse_smallk_dx = _switch("GTE_FUSE_SMALLK_DX")
         # LayerNorm(+ReLU) forward of the last hidden layer inside the output layer's forward kernel (gte_sage_narrow_fwd_ln):
         # one launch and one pass over [n, hidden] less
-        self.fuse_ln_fwd = os.environ.get("GTE_FUSE_LN_FWD", "1") == "1"
+        self.fuse_ln_fwd = _switch("GTE_FUSE_LN_FWD")
         self._tail_ws = None
         # planes path (GTE_PLANES=0 disables): in the split-bf16 GEMM mode the operands of the transform GEMMs are written as P3
         # images (three bf16 planes, csrc/p3.h) by their producers and multiplied by the planes GEMMs (csrc/gemm_p3.hip)
-        self.use_planes = os.environ.get("GTE_PLANES", "1") == "1"
+        self.use_planes = _switch("GTE_PLANES")
         # ... for EVERY hidden width up to 1024 and any input width through the one-call plan (padded rows, masked LayerNorm
         # kernels, aggregate-first input layer, output layer on the planes GEMMs); GTE_PLANES_GENERAL=0: the tuned range only
-        self.general_planes = os.environ.get("GTE_PLANES_GENERAL", "1") == "1"
+        self.general_planes = _switch("GTE_PLANES_GENERAL")
         # input layer on the CACHED mean aggregate of the input (graph.ResidentPages.build_agg_image: page-local, constant over a
         # run): z = [x | ahn] W^T from two resident images behind the batch's row map, no aggregation / q / feature copy in the
         # step for layer 0 (GTE_LAYER_CACHED).  Costs a second resident image; GTE_CACHE_AGG=0 turns it off
-        self.cache_input_agg = os.environ.get("GTE_CACHE_AGG", "1") == "1"
-        # one-call plans: _plan_key -> their image set (the call-by-call schedule keeps its own)
-        self._wimg = {}
+        self.cache_input_agg = _switch("GTE_CACHE_AGG")
         # weight images in the block-major layout (ops.P3): a K block of the weights is ONE contiguous run, whole cache lines for
         # every NT planes GEMM, and the block-major-weights kernel (gemm_p3_nt_sq_kernel) loads its fragments straight into
         # registers.  GTE_WIMG_BLOCK_MAJOR=0: row-major images (the layout up to round 5; A/B measurements, tests)
-        self.block_major_weights = os.environ.get("GTE_WIMG_BLOCK_MAJOR", "1") == "1"
+        self.block_major_weights = _switch("GTE_WIMG_BLOCK_MAJOR")
         # one-call step: the fold + Adam launch also writes the weight images of the updated parameters
-        # (gte_fold_defer_flush_adam_images) and the next step's forward skips their conversion launch.  _wimg_sig = the version
-        # counters of the parameters the images were made from (None: stale).  In-place writes through torch (load_state_dict,
-        # p.copy_, flat_param.copy_) move the counters; raw writes through ``p.data`` do not: invalidate_weight_images() then.
-        self.wimg_in_fold = os.environ.get("GTE_WIMG_IN_FOLD", "1") == "1"
-        self._wimg_sig = None
-        self._last_wimg = None                        # (descriptors an unfused optimiser launch may still rewrite: _c_step)
-        self._keep = ()                               # what the last one-call step's plan points at: alive until the next step
+        # (gte_fold_defer_flush_adam_images) and the next step's forward skips their conversion launch; whether the images still
+        # follow the parameters is step_plan.ImageFreshness's to say (``_plan.images``; read here as ``_wimg_sig``)
+        self.wimg_in_fold = _switch("GTE_WIMG_IN_FOLD")
         # optimiser state on the device, made at the first step (_adam_state)
         self._hyper, self._step_dev, self._ticket, self._hyper_host, self._step_dev_host = None, None, None, None, 0
         # the whole step through ONE C entry point (gte_gcnsage_step) when the configuration allows (GTE_C_STEP=0: call by call)
-        self.use_c_step = os.environ.get("GTE_C_STEP", "1") == "1"
+        self.use_c_step = _switch("GTE_C_STEP")
         # called (once per step, no arguments) right before the LAST big kernel of a step is launched -- layer 0's dW GEMM,
         # MFMA-bound, ~a quarter of the step.  The train loop hangs the assembly of the NEXT batch here (models/loop.py):
         # it then runs on the side stream under that GEMM, and the batch is still in the Infinity Cache when the next
@@ -233,7 +226,6 @@ class FusedGcnSageStep(TrainStep):
         # measurement hook of the one-call step (bench.py): a list of 2 x n_hidden torch.cuda.Event(enable_timing=True), recorded
         # around the forward transform GEMM of every hidden layer of the NEXT steps (None: off)
         self.fwd_events = None
-        self._fwd_ev_arr = None
         if self.dropout_p > 0 and self._plan_kinds(model.layers[0].in_feats, 0) is None:
             # dropout runs on the one-call plan only (the call-by-call schedule has no masks): a model the plan does not cover --
             # hidden width > 1024, more than 8 layers or 16 classes, GTE_C_STEP=0, GTE_PLANES_GENERAL=0, op timers -- is refused
@@ -255,55 +247,11 @@ class FusedGcnSageStep(TrainStep):
             need.append(lib.gte_gemm_p3_nt_smallk_bwd_workspace_bytes(cap, 2 * dims[0], dims[1]))
         return max(need)
 
-    # -- buffers of the one-call plan (padded rows) -----------------------------------------------------
-    def _alloc_plan(self, cap: int, f0: int, kinds, out_gemm: bool):
-        """Buffer set of a one-call plan: the fp32 row buffers of a hidden layer are PADDED to ld = hidden rounded up to 16 floats
-        (include/gte.h, gte_step_layer.ldf; no padding at a 16-aligned width), zero-initialised once (the kernels keep the padding
-        zero); images are padded to 16-column blocks by construction."""
-        dev, lib = self.flat_param.device, self.lib
-        layers = list(self.model.layers)
-        dims = [f0] + [l.out_feats for l in layers]
-        nh = len(layers) - 1
-        ld = [_c16(d) for d in dims[1:nh + 1]]
-        z32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        u8 = lambda nbytes: torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-
-        def img(rows, cols):
-            t = ops.P3.empty(rows, cols, dev)
-            t.data.zero_()
-            return t
-        b = {"cap": cap, "ld": ld}
-        b["t"] = [z32(cap, 2 * ld[i]) if kinds[i] == LAYER_PLANES else z32(cap, ld[i]) for i in range(nh)]     # [t_self | t_neigh], or z
-        b["y"] = [z32(cap, ld[i]) for i in range(nh)]
-        b["dy"] = [z32(cap, ld[i]) for i in range(nh)]
-        b["stats"] = [z32(2 * cap) for _ in range(nh)]
-        b["ahn"] = [z32(cap, dims[0]) if kinds[i] == LAYER_SMALLK else None for i in range(nh)]
-        b["ahnp"] = [img(cap, dims[i]) if kinds[i] in (LAYER_AGGFIRST, LAYER_DROPOUT) else None for i in range(nh)]
-        # a dropout layer above layer 0: G = dz W [n][2 ceil16(fin)] (self half, then the aggregate half from column ceil16(fin))
-        b["g"] = [z32(cap, 2 * _c16(dims[i])) if (kinds[i] == LAYER_DROPOUT and i > 0) else None for i in range(nh)]
-        # (a cached layer reads both operands from resident images)
-        b["hp"] = [img(cap, dims[i]) if kinds[i] not in (LAYER_SMALLK, LAYER_CACHED) else None for i in range(nh)]
-        b["dzp"] = [img(cap, dims[i + 1]) if kinds[i] != LAYER_SMALLK else None for i in range(nh)]
-        b["qp"] = [img(cap, dims[i + 1]) if kinds[i] == LAYER_PLANES else None for i in range(nh)]
-        b["ws_dw"] = [u8(lib.gte_gemm_p3_tn_workspace_bytes(dims[i + 1], 2 * dims[i], dims[i], cap) if kinds[i] != LAYER_SMALLK
-                         else self._ws_dw_bytes(i, dims, cap)) for i in range(nh)]
-        b["ws_ln"] = [u8(max(lib.gte_ln_relu_bwd_workspace_bytes(cap, dims[i + 1]),
-                             lib.gte_gemm_p3_nt_ln_bwd_workspace_bytes(cap, dims[i + 1]) if dims[i + 1] <= 256 else 0,
-                             lib.gte_sage_narrow_bwd_ln_workspace_bytes(cap, min(_c16(dims[i + 1]), 256)))) for i in range(nh)]
-        C = dims[-1]
-        b["out3"] = z32(3)
-        if out_gemm:
-            b["hp_out"] = img(cap, dims[-2])                       # image of the last hidden layer's output
-            b["t_out"], b["dlq"] = z32(cap, 32), z32(cap, 32)      # [logits .. | t_neigh ..], [dl .. | q ..]
-            b["dlqp"] = img(cap + 8, 32)
-            b["ws_out"] = u8(lib.gte_gemm_p3_tn_workspace_bytes(C, 2 * dims[-2], dims[-2], cap))
-            b["ws_ce"] = u8(max(lib.gte_weighted_ce_workspace_bytes(cap), lib.gte_head_agg_ce_workspace_bytes(cap)))
-            b["ws_cs"] = u8(max(lib.gte_colsum_workspace_bytes(cap, C), lib.gte_head_dlq_finish_workspace_bytes(cap)))
-        else:
-            b["logits"], b["tn"], b["q"], b["dl"] = z32(cap, C), z32(cap, C), z32(cap, C), z32(cap, C)
-            b["ce_part"] = u8(lib.gte_head_agg_ce_workspace_bytes(cap))
-            b["ws_nar"] = u8(lib.gte_sage_narrow_bwd_workspace_bytes(cap, min(_c16(dims[-2]), 256), min(C, 16)))
-        return b
+    def _tail_workspace(self) -> torch.Tensor:
+        """Scratch of the GEMM tail split (gte_gemm_set_tail_workspace), made at first use: both schedules register the same one."""
+        if self._tail_ws is None:
+            self._tail_ws = torch.empty(int(self.lib.gte_gemm_tail_workspace_bytes()), dtype=torch.uint8, device=self.flat_param.device)
+        return self._tail_ws
 
     def _private_set(self, key, n: int, alloc):
         """The exact-size buffer set ``key`` of the batch being captured (made by ``alloc(n)`` at first use, never reallocated)."""
@@ -315,45 +263,20 @@ class FusedGcnSageStep(TrainStep):
             raise RuntimeError(f"captured batch buffers hold {full['cap']} nodes; asked for {n} (a captured batch must not change)")
         return full
 
-    @staticmethod
-    def _plan_key(f0: int, kinds, out_gemm: bool):
-        """What names a one-call plan's layout: the key of its buffer set and the tag of its weight-image set."""
-        return ("gen", f0, tuple(kinds), bool(out_gemm))
-
-    def _buffers_plan(self, n: int, f0: int, kinds, out_gemm: bool):
-        """The (capacity-sized, shared or captured-batch-private) buffer set of a one-call plan; see CallSchedule._full_set."""
-        key = self._plan_key(f0, kinds, out_gemm)
-        if self._private_key is not None:
-            return self._private_set(key, n, lambda m: self._alloc_plan(m, f0, kinds, out_gemm))
-        full = self._bufs.get(key)
-        if full is None or full["cap"] < n:
-            cap = max(-(-int(n * 1.125) // 4096) * 4096, self._reserved.get(f0, 0))
-            self._bufs.pop(key, None)
-            full = self._bufs[key] = self._alloc_plan(cap, f0, kinds, out_gemm)
-        return full
-
     def plan_buffers(self, batch, private_key=None):
         """(buffer set, layer kinds, out_gemm) of the one-call plan a training step on ``batch`` runs on -- the shared set, or the
         private set of the batch captured under ``private_key`` (capture(): ``id`` of its graph) -- for tests and tools that read
         what a step left behind.  None when that step is not on a plan (call-by-call schedule), or no such step has run yet."""
-        _xp, n, f0 = batch_shape(batch)
-        kinds = self._plan_kinds(f0, n, self._batch_cached(batch))
-        if kinds is None:
-            return None
-        out_gemm = self._plan_mode(kinds, f0)[1]
-        key = self._plan_key(f0, kinds, out_gemm)
-        full = self._bufs.get(key) if private_key is None else self._graph_bufs.get((private_key, key))
-        return None if full is None else (full, kinds, out_gemm)
+        return self._plan.buffers(batch, private_key)
 
     def reserve(self, n_nodes: int, f0: int, cached: bool = False) -> None:
         """Size the shared per-batch buffers for batches of up to ``n_nodes`` nodes (the train loop knows the largest batch
         its page table can produce): no reallocation -- a device synchronisation plus ~12 KB per node of new buffers -- later,
         in the middle of an epoch.  A one-call plan takes the recorded capacity when it allocates its set at the first step
         (``cached``: the batches bring the aggregate image); the call-by-call schedule's set is allocated here."""
-        cap = -(-int(n_nodes) // 4096) * 4096
-        self._reserved[f0] = max(self._reserved.get(f0, 0), cap)
+        self._reserved[f0] = max(self._reserved.get(f0, 0), row_capacity(n_nodes))
         if self._plan_kinds(f0, 0, cached) is not None:
-            return                      # a one-call plan allocates its own set (_buffers_plan) at this capacity on first use
+            return                      # a one-call plan allocates its own set (OneCallPlan._buffers) at this capacity on first use
         self._calls.reserve(n_nodes, f0)
 
     def _narrow(self, layer, fin: int) -> bool:
@@ -402,10 +325,16 @@ class FusedGcnSageStep(TrainStep):
     def _param_sig(self):
         return (self.flat_param._version,) + tuple(p._version for p in self.model.parameters())
 
+    @property
+    def _wimg_sig(self):
+        """(version counters of the parameters, plan key) the one-call plans' weight images were written from; None: stale.
+        Read-only: step_plan.ImageFreshness owns it."""
+        return self._plan.images.sig
+
     def invalidate_weight_images(self) -> None:
         """The parameters were changed behind torch's version counters (a raw ``p.data`` write, a foreign kernel): the next
         forward converts the weight images again."""
-        self._wimg_sig = None
+        self._plan.images.stale()
 
     # -- the whole step as one host call (gte_gcnsage_step) ---------------------------------------------
     def _smallk_bwd(self, i: int, layer, fin: int) -> bool:
@@ -509,15 +438,7 @@ class FusedGcnSageStep(TrainStep):
         """Bit mask of the hidden layers a training step on ``g`` runs in the wide addressing form (gte_gcnsage_step_wide_layers on
         the step's own plan: a dropout layer whose row buffers reach 2 GB, or every dropout layer under gte_dropout_set_wide(1) on
         this thread); 0 for a model without dropout or a step that is not on a plan."""
-        _xp, n, f0 = batch_shape(g)
-        kinds = self._plan_kinds(f0, n, self._batch_cached(g))
-        if kinds is None or self.dropout_p == 0:
-            return 0
-        plan = self._bind_plan(g, kinds, with_adam=bool(self._fuse_adam_req))[0]
-        rc = int(self.lib.gte_gcnsage_step_wide_layers(ctypes.addressof(plan)))
-        if rc < 0:
-            _lib.check(rc, "gte_gcnsage_step_wide_layers")
-        return rc
+        return self._plan.wide_layers(g)
 
     def attach_feature_image(self, g) -> bool:
         """Give a graph that is evaluated again and again (the validation graph of train(): the same graph every epoch,
@@ -555,268 +476,6 @@ class FusedGcnSageStep(TrainStep):
                               or (k == LAYER_PLANES and not self._planes_layer(i, layers[i], dims[i])) for i, k in enumerate(kinds))
         return gen, out_gemm
 
-    def _weight_images_gen(self, dims, kinds, out_gemm: bool):
-        """Weight images of a one-call plan (kept per _plan_key) and their conversion descriptors.  A planes layer's forward
-        image holds [W_s rows ; zero rows up to ld ; W_n rows ; zero rows] (ld = fout rounded up to 16: the two halves of t start on
-        16-column boundaries), its backward image [fin] x [W_s^T | W_n^T] with the second segment at column block ld / 16; an
-        aggregate-first layer's image is [fout] x [W_s | W_n] with the second K segment at block ceil(fin / 16); the output
-        layer's images are [32] x [H] (rows 0.. = W_s, 16.. = W_n) and [H] x [32].  Allocated zeroed: the padding is never written."""
-        key = self._plan_key(dims[0], kinds, out_gemm)
-        hit = self._wimg.get(key)
-        if hit is not None:
-            return hit
-        dev = self.flat_param.device
-        layers = list(self.model.layers)
-
-        def img(rows, cols):                          # (weight images are BLOCK-MAJOR: the B operand of every NT planes GEMM -- ops.P3)
-            t = ops.P3.empty(rows, cols, dev, block_major=self.block_major_weights)
-            t.data.zero_()
-            return t
-        imgs, descs = {}, []
-        for i, k in enumerate(kinds):
-            L = layers[i]
-            fin, fout = dims[i], L.out_feats
-            W = L.linear.weight
-            wp, ldw = W.data_ptr(), W.stride(0)
-            if k == LAYER_PLANES:
-                ld = _c16(fout)
-                fwd = img(2 * ld, fin)
-                descs.append(_lib.P3Desc(wp, ldw, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
-                descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fout, fin, 0, fwd.at(ld, 0), fwd.ldp))
-                bwd = None
-                if i > 0:
-                    bwd = img(fin, 2 * ld)
-                    descs.append(_lib.P3Desc(wp, ldw, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
-                    descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fin, fout, 1, bwd.at(0, ld // 16), bwd.ldp))
-                imgs[i] = (fwd, bwd)
-            elif k in (LAYER_AGGFIRST, LAYER_CACHED, LAYER_DROPOUT):
-                kp = _c16(fin)
-                fwd = img(fout, 2 * kp)
-                descs.append(_lib.P3Desc(wp, ldw, fout, fin, 0, fwd.at(0, 0), fwd.ldp))
-                descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fout, fin, 0, fwd.at(0, kp // 16), fwd.ldp))
-                bwd = None
-                if k == LAYER_DROPOUT and i > 0:
-                    # G = dz W: the image [2 kp][fout] = [W_s^T ; zero rows ; W_n^T from row kp ; zero rows] (B operand of an NT GEMM)
-                    bwd = img(2 * kp, fout)
-                    descs.append(_lib.P3Desc(wp, ldw, fin, fout, 1, bwd.at(0, 0), bwd.ldp))
-                    descs.append(_lib.P3Desc(wp + 4 * fin, ldw, fin, fout, 1, bwd.at(kp, 0), bwd.ldp))
-                imgs[i] = (fwd, bwd)
-        if out_gemm:
-            Lo = layers[-1]
-            H, C = dims[-2], Lo.out_feats
-            W = Lo.linear.weight
-            wp, ldw = W.data_ptr(), W.stride(0)
-            fwd, bwd = img(32, H), img(H, 32)
-            descs.append(_lib.P3Desc(wp, ldw, C, H, 0, fwd.at(0, 0), fwd.ldp))
-            descs.append(_lib.P3Desc(wp + 4 * H, ldw, C, H, 0, fwd.at(16, 0), fwd.ldp))
-            descs.append(_lib.P3Desc(wp, ldw, H, C, 1, bwd.at(0, 0), bwd.ldp))
-            descs.append(_lib.P3Desc(wp + 4 * H, ldw, H, C, 1, bwd.at(0, 1), bwd.ldp))
-            imgs["out"] = (fwd, bwd)
-        if len(descs) > 32:
-            raise _lib.GteError("gte_gcnsage_step: more than 32 weight images")
-        arr = (_lib.P3Desc * max(len(descs), 1))(*descs)
-        hit = self._wimg[key] = (imgs, arr, len(descs))
-        return hit
-
-    def _bind_plan(self, g, kinds, with_adam: bool):
-        """The gte_step_plan of this layer plan (cached with the buffer set whose addresses it holds, _alloc_plan) with the
-        per-batch fields -- graph, features, node count -- set for ``g``.  Returns (plan, fused flag, {out3, logits rows, image-set
-        tag}, node count, tensors the plan points at)."""
-        lib, P = self.lib, _lib.ptr
-        xp, n, f0 = batch_shape(g)
-        x = None
-        if xp is None:
-            x = f32_rows(g)
-            _lib.require_device(x, "FusedGcnSageStep")
-        out_gemm = self._plan_mode(kinds, f0)[1]
-        b = self._buffers_plan(n, f0, kinds, out_gemm)
-        layers = list(self.model.layers)
-        dims = [f0] + [l.out_feats for l in layers]
-        nh = len(layers) - 1
-        ew = g.edata.get("feat")
-        csr, rcsr = g.in_csr(), g.out_csr()
-        w_in, w_out = g.in_weights(ew), g.out_weights(ew, True)
-        plans = b.setdefault("_plans", {})
-        cached = plans.get(with_adam)
-        if cached is None:
-            imgs, arr, n_desc = self._weight_images_gen(dims, kinds, out_gemm)
-            plan = _lib.StepPlan()
-            plan.n_hidden = nh
-            gs = self._gslice
-            for i, L in enumerate(layers[:-1]):
-                sl = plan.layer[i]
-                fin, fout = dims[i], L.out_feats
-                sl.kind, sl.fin, sl.fout, sl.ldf = kinds[i], fin, fout, b["ld"][i]
-                sl.W, sl.bias, sl.gamma, sl.beta = P(L.linear.weight), P(L.linear.bias), P(L.lynorm.weight), P(L.lynorm.bias)
-                sl.eps, sl.relu = float(L.lynorm.eps), int(L.activation is not None)
-                sl.gW, sl.gbias = P(gs[id(L.linear.weight)]), P(gs[id(L.linear.bias)])
-                sl.ggamma, sl.gbeta = P(gs[id(L.lynorm.weight)]), P(gs[id(L.lynorm.bias)])
-                last_hidden = i == nh - 1
-                nxt_img = (not last_hidden and kinds[i + 1] == LAYER_PLANES) or (last_hidden and out_gemm)
-                # the layer's output: as an image for a planes consumer, as fp32 rows for the narrow output kernels
-                if nxt_img:
-                    yp = b["hp_out"] if last_hidden else b["hp"][i + 1]
-                    sl.yp, sl.ldp_y = P(yp.data), yp.ldp
-                sl.y = P(b["y"][i]) if (last_hidden and not out_gemm) or not nxt_img else None
-                sl.t, sl.stats, sl.dy = P(b["t"][i]), P(b["stats"][i]), P(b["dy"][i])
-                sl.ws_ln, sl.ws_ln_bytes = P(b["ws_ln"][i]), b["ws_ln"][i].numel()
-                sl.ws_dw, sl.ws_dw_bytes = P(b["ws_dw"][i]), b["ws_dw"][i].numel()
-                if kinds[i] == LAYER_SMALLK:
-                    sl.ahn = P(b["ahn"][i])
-                    continue
-                wf, wb = imgs[i]
-                sl.wimg_fwd, sl.ldp_wfwd = P(wf.data), wf.ldp
-                if wb is not None:
-                    sl.wimg_bwd, sl.ldp_wbwd = P(wb.data), wb.ldp
-                sl.dzp, sl.ldp_o = P(b["dzp"][i].data), b["dzp"][i].ldp
-                if kinds[i] == LAYER_CACHED:
-                    continue                                      # (both operand images are the batch's: bound per call)
-                sl.hp, sl.ldp_h = P(b["hp"][i].data), b["hp"][i].ldp
-                if kinds[i] == LAYER_DROPOUT:
-                    # the masked operand images [D(x') | D(ahn')]; above layer 0 the input is y of the layer below, and G
-                    sl.ahnp, sl.ldp_ahn = P(b["ahnp"][i].data), b["ahnp"][i].ldp
-                    if i > 0:
-                        sl.x, sl.ldx = P(b["y"][i - 1]), b["ld"][i - 1]
-                        sl.g, sl.ldg = P(b["g"][i]), b["g"][i].shape[1]
-                    continue
-                if kinds[i] == LAYER_PLANES:
-                    sl.qp = P(b["qp"][i].data)
-                else:
-                    sl.ahnp, sl.ldp_ahn = P(b["ahnp"][i].data), b["ahnp"][i].ldp
-            Lo = layers[-1]
-            C = Lo.out_feats
-            plan.out_fin, plan.n_classes = dims[-2], C
-            plan.W_out, plan.b_out = P(Lo.linear.weight), P(Lo.linear.bias)
-            plan.gW_out, plan.gb_out = P(gs[id(Lo.linear.weight)]), P(gs[id(Lo.linear.bias)])
-            plan.ld_h_out = b["ld"][-1]
-            plan.dh_out = P(b["dy"][-1])
-            if out_gemm:
-                wf, wb = imgs["out"]
-                plan.out_gemm, plan.ld_lg = 1, 32
-                plan.hp_out, plan.ldp_hout = P(b["hp_out"].data), b["hp_out"].ldp
-                plan.wimg_out_fwd, plan.ldp_wout_fwd = P(wf.data), wf.ldp
-                plan.wimg_out_bwd, plan.ldp_wout_bwd = P(wb.data), wb.ldp
-                plan.logits, plan.tn = P(b["t_out"]), P(b["t_out"]) + 64
-                plan.dl, plan.q_out = P(b["dlq"]), P(b["dlq"]) + 64
-                plan.dlqp, plan.ldp_dlq = P(b["dlqp"].data), b["dlqp"].ldp
-                plan.ws_out, plan.ws_out_bytes = P(b["ws_out"]), b["ws_out"].numel()
-                plan.ws_ce, plan.ws_ce_bytes = P(b["ws_ce"]), b["ws_ce"].numel()
-                plan.ws_cs, plan.ws_cs_bytes = P(b["ws_cs"]), b["ws_cs"].numel()
-            else:
-                plan.h_out = P(b["y"][-1])
-                plan.logits, plan.tn, plan.q_out, plan.dl = P(b["logits"]), P(b["tn"]), P(b["q"]), P(b["dl"])
-                plan.ce_part, plan.ce_part_bytes = P(b["ce_part"]), b["ce_part"].numel()
-                plan.ws_nar, plan.ws_nar_bytes = P(b["ws_nar"]), b["ws_nar"].numel()
-            plan.out3 = P(b["out3"])
-            plan.wimg_descs, plan.n_wimg_descs = ctypes.addressof(arr), n_desc
-            if with_adam:
-                plan.param, plan.grad, plan.exp_avg, plan.exp_avg_sq = (P(self.flat_param), P(self.flat_grad), P(self.exp_avg),
-                                                                        P(self.exp_avg_sq))
-                plan.n_param = self.flat_param.numel()
-                plan.hyper, plan.step_counter, plan.ticket = P(self._hyper), P(self._step_dev), P(self._ticket)
-            if self._tail_ws is None:
-                self._tail_ws = torch.empty(int(lib.gte_gemm_tail_workspace_bytes()), dtype=torch.uint8, device=self.flat_param.device)
-            if self.tail_split:
-                plan.tail_ws, plan.tail_ws_bytes = P(self._tail_ws), self._tail_ws.numel()
-            cached = plans[with_adam] = (plan, arr, ctypes.c_int(0))
-        plan, _arr, fused = cached
-        # per call: switches and class weights (public attributes), the graph, the features
-        plan.class_weights = P(self.class_weights)
-        plan.fuse_ln_dx = (int(self.fuse_ln_dx) | (2 if self.fuse_ln_narrow else 0) | (8 if self.fuse_smallk_dx else 0)
-                           | (4 if self.fuse_head_gemm else 0) | (16 if self.fuse_ln_fwd else 0))
-        L0 = plan.layer[0]
-        rows = (P(xp.row_map), xp.res_rows) if xp is not None and xp.row_map is not None else (None, 0)     # the batch's row map
-        if kinds[0] == LAYER_DROPOUT:
-            # dropout: the input as fp32 rows or as the (resident) image; the masks of this seed / rank at the device step counter
-            if xp is not None:
-                L0.xp, L0.ldp_x, L0.x, L0.ldx = P(xp.data), xp.ldp, None, 0
-            else:
-                L0.xp, L0.ldp_x, L0.x, L0.ldx = None, 0, P(x), ops._ld(x)
-            L0.h_rows, L0.n_res_rows = rows
-            self._adam_state()
-            plan.dropout_p, plan.dropout_seed, plan.rank = float(self.dropout_p), self.dropout_seed, self.rank
-            plan.step_counter = P(self._step_dev)
-        elif kinds[0] == LAYER_CACHED:
-            ap = getattr(g, "agg_p3", None)
-            if xp is None or ap is None:
-                raise _lib.GteError("a cached-aggregate input layer needs feat_p3 and agg_p3 (resident images behind a row map, or the graph's own)")
-            L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
-            L0.ahnp, L0.ldp_ahn = P(ap.data), ap.ldp
-            L0.h_rows, L0.n_res_rows = rows
-        elif kinds[0] == LAYER_PLANES:
-            if xp is not None:
-                L0.hp, L0.ldp_h, L0.make_hp, L0.x = P(xp.data), xp.ldp, 0, None
-            else:
-                L0.hp, L0.ldp_h, L0.make_hp = P(b["hp"][0].data), b["hp"][0].ldp, 1
-                L0.x, L0.ldx = P(x), ops._ld(x)
-            L0.h_rows, L0.n_res_rows = rows
-        else:
-            # (an image-only batch on a layer that reads fp32 rows -- copied image rows without the aggregate image, GTE_P3_ROWS=0 --
-            # gets the rows back from the image: slow, a measurement configuration)
-            x = f32_rows(g) if x is None else x
-            L0.x, L0.ldx = P(x), ops._ld(x)
-        plan.indptr, plan.indices, plan.w_in = P(csr.indptr), P(csr.indices), P(w_in)
-        plan.rindptr, plan.rindices, plan.w_out = P(rcsr.indptr), P(rcsr.indices), P(w_out)
-        plan.n_nodes = n
-        C = layers[-1].out_feats
-        view = {"out3": b["out3"], "_wkey": self._plan_key(f0, kinds, out_gemm),
-                "logits": b["t_out"][:n, :C] if out_gemm else b["logits"][:n]}
-        return plan, fused, view, n, (csr, rcsr, w_in, w_out, self.class_weights)
-
-    def _c_step(self, g, labels, grad_scale, kinds, with_adam: bool):
-        """forward + loss + backward (+ Adam inside the fold launch) through gte_gcnsage_step: two host calls (the next batch's
-        assembly is queued between them) instead of ~19."""
-        lib, P = self.lib, _lib.ptr
-        st = _lib.current_stream()
-        plan, fused, b, n, keep = self._bind_plan(g, kinds, with_adam)
-        _arr = plan.wimg_descs                                       # (the descriptor array lives in the plan cache)
-        lab = labels if labels.dtype in (torch.float32, torch.int64) else labels.to(torch.int64)
-        plan.labels, plan.labels_f32 = P(lab), int(lab.dtype == torch.float32)
-        plan.grad_scale = float(grad_scale)
-        if self.fwd_events:
-            for e in self.fwd_events:
-                if not e.cuda_event:                  # (created lazily by the first record)
-                    e.record()
-            self._fwd_ev_arr = (ctypes.c_void_p * len(self.fwd_events))(*[e.cuda_event for e in self.fwd_events])
-            plan.fwd_events = ctypes.addressof(self._fwd_ev_arr)
-        else:
-            plan.fwd_events = None
-        capturing = torch.cuda.is_current_stream_capturing()
-        sig = self._param_sig()
-        sig = (sig, b["_wkey"])                   # (which image set: a plan of another layout keeps its own images)
-        plan.wimg_fresh = int(self.wimg_in_fold and not capturing and self._wimg_sig == sig)
-        plan.wimg_in_fold = int(self.wimg_in_fold and with_adam and not capturing)
-        self._wimg_sig = None
-        addr = ctypes.addressof(plan)
-        if self.before_last_gemm is not None:
-            _lib.check(lib.gte_gcnsage_step(addr, 1, ctypes.byref(fused), st), "gte_gcnsage_step")
-            # phase 1 returned with this thread's fold deferral OPEN and the tail workspace registered: whatever the callback (the
-            # next batch's assembly) or phase 2 raises, both are closed again -- a step that died here must not poison the next
-            # one ("a deferral is already open") or let later standalone calls queue folds nobody flushes
-            try:
-                self.before_last_gemm()
-                _lib.check(lib.gte_gcnsage_step(addr, 2, ctypes.byref(fused), st), "gte_gcnsage_step")
-            except BaseException:
-                lib.gte_fold_defer_flush()                      # (an error if phase 2 already closed it: ignored)
-                lib.gte_gemm_set_tail_workspace(None, 0)
-                self._wimg_sig = None
-                raise
-        else:
-            _lib.check(lib.gte_gcnsage_step(addr, 0, ctypes.byref(fused), st), "gte_gcnsage_step")
-        self._adam_fused = bool(fused.value & 1)
-        # the images now hold: the updated parameters (written by the fold launch), or -- no optimiser step in this call -- the
-        # unchanged ones the forward converted; otherwise Adam follows as its own launch and they are stale
-        if not capturing and ((fused.value & 2) or not with_adam):
-            self._wimg_sig = sig
-        self._keep = (lab,) + tuple(keep)                              # alive until the next step
-        # (the data-parallel step's own Adam launch writes the same images: gte_adam_step_dev_images)
-        # (kept only while an UNFUSED optimiser launch may still follow this very step -- a step whose fold launch already ran Adam
-        # must not leave descriptors behind for a later launch of another plan; the tuple keeps the descriptor array AND the image
-        # tensors it points into alive)
-        self._last_wimg = ((plan.wimg_descs, int(plan.n_wimg_descs), b["_wkey"], _arr, dict(self._wimg))
-                           if not capturing and not (fused.value & 1) else None)
-        return b["out3"]
-
     FORWARD_IMAGE_MAX_ELEMS = 1 << 21     # forward_logits: largest fp32 feature matrix that is converted to an image per call
 
     def forward_logits(self, g) -> torch.Tensor:
@@ -824,7 +483,6 @@ class FusedGcnSageStep(TrainStep):
         [n, n_classes] through ONE host call (gte_gcnsage_forward) on the step's own buffers -- a view that the next step or
         forward on this engine overwrites.  Configurations the one-call plan does not cover -- and large graphs that bring fp32
         features to a planes input layer (a validation graph: the plan would write their image first) -- run the module path."""
-        self._last_wimg = None
         xp, n, f0 = batch_shape(g)
         kinds = self._plan_kinds(f0, n, self._batch_cached(g), train=False) if n > 0 else None
         if kinds is not None and xp is None and kinds[0] == LAYER_PLANES and n * f0 > self.FORWARD_IMAGE_MAX_ELEMS:
@@ -842,14 +500,7 @@ class FusedGcnSageStep(TrainStep):
                     return self.model(g)
             finally:
                 self.model.train(was)
-        plan, _fused, b, n, keep = self._bind_plan(g, kinds, with_adam=False)
-        capturing = torch.cuda.is_current_stream_capturing()
-        sig = (self._param_sig(), b["_wkey"])
-        plan.wimg_fresh = int(self.wimg_in_fold and not capturing and self._wimg_sig == sig)
-        _lib.check(self.lib.gte_gcnsage_forward(ctypes.addressof(plan), _lib.current_stream()), "gte_gcnsage_forward")
-        self._wimg_sig = None if capturing else sig
-        self._keep = keep
-        return b["logits"]
+        return self._plan.forward(g, kinds)
 
     # -- the schedule ----------------------------------------------------------------------------------
     def forward_backward(self, g, labels: torch.Tensor, grad_scale: float = 1.0, upto_layer: int = 0) -> torch.Tensor:
@@ -861,16 +512,10 @@ class FusedGcnSageStep(TrainStep):
             _xp, n, f0 = batch_shape(g)
             kinds = self._plan_kinds(f0, n, self._batch_cached(g))
             if kinds is not None:
-                return self._c_step(g, labels, grad_scale, kinds, with_adam)
+                return self._plan.step(g, labels, grad_scale, kinds, with_adam)
         self._refuse_dropout()
         out3, self._adam_fused = self._calls.run(g, labels, grad_scale, len(self.model.layers) - 1, upto_layer, with_adam=with_adam)
         return out3
-
-    def _plan_images_stale(self) -> None:
-        """A call-by-call pass begins: the one-call plans' weight images no longer follow the parameters, and no later optimiser
-        launch may rewrite them."""
-        self._wimg_sig = None
-        self._last_wimg = None
 
     def _refuse_dropout(self) -> None:
         if self.dropout_p > 0:
@@ -976,8 +621,7 @@ class FusedGcnSageStep(TrainStep):
 
     def _adam_dev_launch(self) -> None:
         P = _lib.ptr
-        self._wimg_sig = None
-        last, self._last_wimg = self._last_wimg, None
+        last = self._plan.images.take_for_optimiser()            # (this launch changes the parameters: stale from here)
         if (last is not None and self.wimg_in_fold and 0 < last[1] <= 12 and not torch.cuda.is_current_stream_capturing()):
             # the optimiser launch behind the all-reduce also writes the weight images of the step that just ran (one launch instead
             # of Adam + a conversion launch in front of the next forward: the one-GPU step has both inside its fold launch)
@@ -987,7 +631,7 @@ class FusedGcnSageStep(TrainStep):
                                                          last[0], last[1], ctypes.byref(wrote), _lib.current_stream()),
                        "gte_adam_step_dev_images")
             if wrote.value:
-                self._wimg_sig = (self._param_sig(), last[2])
+                self._plan.images.wrote(last[2], False)
             self._step_dev_host += 1
             return
         _lib.check(self.lib.gte_adam_step_dev(P(self.flat_param), P(self.flat_grad), P(self.exp_avg), P(self.exp_avg_sq),
@@ -1036,7 +680,7 @@ class FusedGcnSageStep(TrainStep):
         self._adam_state()
         # GTE_DP_GRAPH_COLLECTIVE=1 (experimental, off): the RCCL all-reduce is captured INSIDE the step's HIP graph, so a
         # data-parallel step is one graph launch like the single-GPU step.  Verified with one rank only (1-GPU boxes).
-        graph_coll = self.distributed and os.environ.get("GTE_DP_GRAPH_COLLECTIVE", "0") == "1"
+        graph_coll = self.distributed and _switch("GTE_DP_GRAPH_COLLECTIVE", "0")
         in_graph_adam = (not self.distributed) or graph_coll   # otherwise the all-reduce sits between backward and Adam, eagerly
         split = self.distributed and self._dp_split and not graph_coll
         graph = torch.cuda.CUDAGraph()
@@ -1060,7 +704,7 @@ class FusedGcnSageStep(TrainStep):
             self._step_dev_host -= 1                  # capturing did not run it
 
         def replay():
-            self._wimg_sig = None                     # the graph updates the parameters; its own forward converts the images
+            self._plan.images.stale()                 # the graph updates the parameters; its own forward converts the images
             if in_graph_adam:
                 self.t += 1
                 self._sync_adam_state()               # no-op unless lr / t were changed from outside

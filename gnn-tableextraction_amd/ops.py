@@ -758,6 +758,13 @@ class P3:
                       block_major=True)
         return P3(torch.empty((max(rows_cap or rows, 1), ldp), dtype=torch.uint8, device=device), rows, cols)
 
+    @staticmethod
+    def zeros(rows: int, cols: int, device, block_major: bool = False) -> "P3":
+        """An all-zero image: for images whose padding (rows or column blocks no producer writes) must read as zero."""
+        t = P3.empty(rows, cols, device, block_major=block_major)
+        t.data.zero_()
+        return t
+
     def view_rows(self, rows: int) -> "P3":
         return P3(self.data, rows, self.cols, self.row_map, self.res_rows, self.block_major)
 

@@ -11,7 +11,7 @@ sign of the fma (the product of two fp32 values is exact in float64; rounding ke
 masks has no branch left to disagree on: every remaining difference is device rounding, so every case is checked tightly.
 
 Where ``z`` lives (``device_relu_masks``):
-  * one-call plan (engine._alloc_plan, found through engine.plan_buffers): ``t[i]``, columns [0, fout) -- a planes layer's
+  * one-call plan (models/step_plan.py, OneCallPlan._alloc, found through engine.plan_buffers): ``t[i]``, columns [0, fout) -- a planes layer's
     [z | t_neigh] (z accumulated into the left half), or the aggregate-first / cached input layer's z;
   * the call-by-call schedule (models/call_schedule.py, CallSchedule._alloc, found through engine._calls.buffer_set): ``t[i]``
     (left half) where the layer has one (transform-first or planes layer), else ``z[i]``;

@@ -1074,7 +1074,7 @@ def test_fused_step_buffers_do_not_grow_with_distinct_batch_sizes():
         sizes.add(bg.num_nodes())
         out3 = eng.step(bg, bg.ndata["label"])
     torch.cuda.synchronize()
-    assert len(sizes) > 15 and len(eng._bufs) + len(eng._calls.bufs) == 1      # one shared buffer set alive over both schedules
+    assert len(sizes) > 15 and len(eng._plan.bufs) + len(eng._calls.bufs) == 1      # one shared buffer set alive over both schedules
     assert torch.cuda.memory_allocated() - base < 8 << 20        # only the (freed) per-batch graphs' worth of slack
     assert np.isfinite(float(out3[0]))
 

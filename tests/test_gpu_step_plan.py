@@ -241,7 +241,7 @@ def test_fold_launch_writes_the_weight_images_of_the_updated_parameters(monkeypa
             assert tr.adam_fused_steps == 3 and tr._wimg_sig is not None          # the fold launch wrote them
             # every forward and backward image of the plan that ran, against the conversion launch on the plan's own descriptors
             _, kinds, out_gemm = tr.plan_buffers(g)
-            imgs, arr, n_desc = tr._weight_images_gen([f0] + [l.out_feats for l in model.layers], kinds, out_gemm)
+            imgs, arr, n_desc = tr._plan.weight_images([f0] + [l.out_feats for l in model.layers], kinds, out_gemm)
             have = {i: (fw.data.clone(), None if bw is None else bw.data.clone()) for i, (fw, bw) in imgs.items()}
             assert have and 0 < n_desc <= 16
             _lib.check(tr.lib.gte_p3_from_f32_batch(ctypes.addressof(arr), n_desc, _lib.current_stream()), "gte_p3_from_f32_batch")
@@ -294,3 +294,44 @@ def test_fold_flush_with_images_rejects_bad_image_lists():
     assert lib.gte_fold_defer_flush_adam_images(*args, ctypes.addressof(many), 9, ctypes.byref(fused)) == 0
     assert fused.value == 0                                                                          # nothing queued: no step either
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("f0", [144, 13])
+def test_weight_images_follow_the_parameters_across_both_schedules_and_the_forward(monkeypatch, f0):
+    """One engine, one batch: a one-call step (the fold launch writes the images), a call-by-call step (it updates the parameters
+    behind them), a one-call step again, the forward-only call, a step.  A forward that took images for current which are not
+    would multiply by an earlier step's weights: the final parameters, second moments and the logits are bit for bit those of the
+    same sequence under GTE_WIMG_IN_FOLD=0, where every forward converts.  (144, 128): a planes chain with forward and backward
+    images; (13, 128): the short-input layer below planes layers."""
+    import gnn_tableextraction_amd as gte
+    from gnn_tableextraction_amd import graph as G
+    from gnn_tableextraction_amd.data import synthetic as S
+    from gnn_tableextraction_amd.models.engine import FusedGcnSageStep
+    dev = "cuda:0"
+    src, dst, w, feat, label, off = S.concat_pages(S.make_pages(2, in_feats=f0))
+    g = G.PageGraph(src, dst, int(off[-1]), device=dev)
+    g.ndata["feat"], g.edata["feat"] = torch.from_numpy(feat).to(dev), torch.from_numpy(w).to(dev)
+    y = torch.from_numpy(label).to(dev)
+    finals = []
+    for flag in ("1", "0"):
+        monkeypatch.setenv("GTE_WIMG_IN_FOLD", flag)
+        monkeypatch.setenv("GTE_C_STEP", "1")
+        torch.manual_seed(5)
+        model = gte.GcnSAGE(f0, 128, 9, 3, torch.nn.functional.relu, 0).to(dev)
+        tr = FusedGcnSageStep(model, lr=0.01, weight_decay=5e-4)
+        if not tr._planes_on():
+            pytest.skip("the one-call step drives the planes path (default GEMM mode, GTE_PLANES=1)")
+        tr.step(g, y)
+        if _ran_on_plan(tr, g) is None:
+            pytest.skip("the engine's switches rule the one-call step out for this configuration")
+        tr.use_c_step = False
+        tr.step(g, y)
+        tr.use_c_step = True
+        tr.step(g, y)
+        logits = tr.forward_logits(g).clone()
+        tr.step(g, y)
+        assert tr.t == 4
+        finals.append((tr.flat_param.detach().cpu().numpy().copy(), tr.exp_avg_sq.detach().cpu().numpy().copy(), logits.cpu().numpy()))
+    for a, b in zip(*finals):
+        assert np.isfinite(a).all()
+        np.testing.assert_array_equal(a, b)
