@@ -46,6 +46,13 @@ SIGNATURES = {
     "gte_region_max_page_nodes": (c_int, []),
     "gte_page_regions": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
+    "gte_page_regions_scored": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # box matching of the box-level evaluation (csrc/box_match.hip)
+    "gte_box_match_max_boxes": (c_int, []),
+    "gte_box_match_max_candidates": (c_int, []),
+    "gte_box_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                              c_void_p]),
     "gte_batch_assemble": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_batch_assemble_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,

@@ -18,6 +18,10 @@
 // the loop's hard bound -- a logic error ends in a wrong answer, never in a hang.  The exit decision is one LDS word (one per
 // round parity) that every thread reads behind the barrier: the loop is uniform and no barrier stands under divergent control.
 // Counts and boxes are reduced per root with LDS atomics (integer add / min / max: order-free, deterministic).
+//
+// The SCORED instantiation (gte_page_regions_scored) adds a region confidence in the same launch: every member word adds the
+// softmax mass its logits give to the classes of its own kind, in 2^-19 fixed point, to one more LDS word of its root (an integer
+// add: the sum does not depend on the arrival order), and the root row receives the mean.  Everything else is the one body.
 #include "gte_common.h"
 
 #include <atomic>
@@ -28,24 +32,58 @@ namespace {
 constexpr int REGION_PAGE_MAX = 4096;                 // == the k-NN builder's page limit (knn_graph.hip: KNN_PAGE_MAX)
 constexpr int REGION_THREADS = 256;
 // LDS of a page of `cap` nodes: box[cap] (int4: min x0, min y0, max x1, max y1), lbl[cap], grp[cap], cnt[cap], flag[2] (+ pad)
+// (+ acc[cap], the fixed-point score sums, in the SCORED instantiation only: it follows flag, so the plain layout is unchanged)
 constexpr int REGION_NODE_BYTES = 16 + 4 + 4 + 4;
+constexpr int REGION_SCORE_BYTES = 4;
 constexpr int REGION_TAIL_BYTES = 16;
+constexpr int region_node_bytes(bool scored) { return REGION_NODE_BYTES + (scored ? REGION_SCORE_BYTES : 0); }
 constexpr int REGION_LDS_MAX = REGION_PAGE_MAX * REGION_NODE_BYTES + REGION_TAIL_BYTES;      // 114 704 of the CU's 160 KB
+constexpr int REGION_LDS_MAX_SCORED = REGION_PAGE_MAX * region_node_bytes(true) + REGION_TAIL_BYTES;      // 131 088
+static_assert(REGION_LDS_MAX_SCORED <= 160 * 1024, "a page of REGION_PAGE_MAX nodes must fit the CU's LDS");
+// q(v) = p(v) * 2^19 rounded: a page has <= 4096 = 2^12 words and p <= 1, so a root's sum is <= 2^31 -- an unsigned 32-bit word
+constexpr float REGION_SCORE_ONE = 524288.0f;
+static_assert((uint64_t)REGION_PAGE_MAX * (uint64_t)REGION_SCORE_ONE <= 0xFFFFFFFFull, "the fixed-point sum must fit 32 bits");
 
 __device__ __forceinline__ int lds_get(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_put(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
+// p(v) in 2^-19 fixed point: the fp32 max-subtracted softmax mass of row `lg` on the classes c with class_group[c] == kind; 0 for
+// a row with a non-finite logit.  den and num take the same terms in the same order, so num <= den and p == 1 exactly where
+// every class is of the kind.
+__device__ __forceinline__ unsigned region_word_score(const float* __restrict__ lg, int n_classes,
+                                                      const int32_t* __restrict__ class_group, int kind) {
+    float m = lg[0];
+    bool finite = isfinite(m);
+    for (int c = 1; c < n_classes; ++c) {
+        const float x = lg[c];
+        finite = finite && isfinite(x);
+        m = fmaxf(m, x);
+    }
+    if (!finite) return 0u;
+    float den = 0.f, num = 0.f;
+    for (int c = 0; c < n_classes; ++c) {
+        const float e = expf(lg[c] - m);
+        den += e;
+        if (class_group[c] == kind) num += e;
+    }
+    return (unsigned)((num / den) * REGION_SCORE_ONE + 0.5f);      // den >= exp(0) = 1
+}
+
 // grid = pages.  cap = the caller's max_page_nodes (the LDS the launch carries).
+template <bool SCORED>
 __global__ void __launch_bounds__(REGION_THREADS)
 page_regions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ indices, const int32_t* __restrict__ node_off,
                     const int32_t* __restrict__ group, const int32_t* __restrict__ bbox, int cap, int n_nodes,
-                    int32_t* __restrict__ comp, int32_t* __restrict__ region_box, int32_t* __restrict__ region_count) {
+                    int32_t* __restrict__ comp, int32_t* __restrict__ region_box, int32_t* __restrict__ region_count,
+                    const float* __restrict__ logits, int n_classes, const int32_t* __restrict__ class_group,
+                    float* __restrict__ region_score) {
     extern __shared__ __attribute__((aligned(16))) int smem[];
     int* box = smem;
     int* lbl = smem + 4 * cap;
     int* grp = lbl + cap;
     int* cnt = grp + cap;
     int* flag = cnt + cap;
+    unsigned* acc = reinterpret_cast<unsigned*>(flag + REGION_TAIL_BYTES / 4);      // SCORED only
     const int tid = threadIdx.x;
     const int n0 = node_off[blockIdx.x], n1 = node_off[blockIdx.x + 1];
     if (n0 < 0 || n1 > n_nodes || n1 <= n0) return;       // an empty page (or offsets that name no row of the outputs)
@@ -56,6 +94,7 @@ page_regions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restric
             comp[n0 + j] = -1;
             region_count[n0 + j] = 0;
             *reinterpret_cast<int4*>(region_box + (int64_t)(n0 + j) * 4) = zero4;
+            if constexpr (SCORED) region_score[n0 + j] = 0.f;
         }
         return;
     }
@@ -63,6 +102,7 @@ page_regions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restric
         lbl[j] = j;
         grp[j] = group[n0 + j];
         cnt[j] = 0;
+        if constexpr (SCORED) acc[j] = 0u;
         *reinterpret_cast<int4*>(box + 4 * j) = make_int4(INT_MAX, INT_MAX, INT_MIN, INT_MIN);
     }
     if (tid == 0) { flag[0] = 0; flag[1] = 0; }
@@ -115,6 +155,8 @@ page_regions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restric
         atomicMin(box + 4 * r + 1, b.y);
         atomicMax(box + 4 * r + 2, b.z);
         atomicMax(box + 4 * r + 3, b.w);
+        if constexpr (SCORED)
+            atomicAdd(acc + r, region_word_score(logits + (int64_t)(n0 + j) * n_classes, n_classes, class_group, grp[j]));
     }
     __syncthreads();
     for (int j = tid; j < np; j += REGION_THREADS) {
@@ -124,20 +166,51 @@ page_regions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restric
         const int4 b = *reinterpret_cast<const int4*>(box + 4 * j);
         *reinterpret_cast<int4*>(region_box + (int64_t)(n0 + j) * 4) =
             make_int4(root ? b.x : 0, root ? b.y : 0, root ? b.z : 0, root ? b.w : 0);
+        if constexpr (SCORED) region_score[n0 + j] = root ? (float)((double)acc[j] / ((double)cnt[j] * (double)REGION_SCORE_ONE)) : 0.f;
     }
 }
 
 // > 64 KB of dynamic LDS needs the opt-in once per kernel AND per device (a process-wide flag configures only
-// the device that is current at the first call): one bit per device id, ids past the mask set the attribute every time.
+// the device that is current at the first call): one bit per device id and instantiation, ids past the mask set the attribute
+// every time.
+template <bool SCORED>
 void allow_region_lds() {
     static std::atomic<uint64_t> configured{0};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = -1;
     const bool tracked = dev >= 0 && dev < 64;
     if (tracked && ((configured.load(std::memory_order_acquire) >> dev) & 1)) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&page_regions_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              REGION_LDS_MAX);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&page_regions_kernel<SCORED>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              SCORED ? REGION_LDS_MAX_SCORED : REGION_LDS_MAX);
     if (tracked) configured.fetch_or(uint64_t(1) << dev, std::memory_order_release);
+}
+
+// the checks and the launch of both entries (SCORED: + the three score arguments)
+template <bool SCORED>
+int page_regions_launch(const char* what, const int32_t* indptr, const int32_t* indices, const int32_t* node_off, int64_t n_pages,
+                        int64_t n_nodes, int64_t max_page_nodes, const int32_t* group, const int32_t* bbox, int32_t* comp,
+                        int32_t* region_box, int32_t* region_count, const float* logits, int n_classes, const int32_t* class_group,
+                        float* region_score, void* stream) {
+    if (n_pages < 0 || n_nodes < 0 || max_page_nodes < 0 || n_pages >= INT32_MAX || n_nodes >= INT32_MAX || (n_pages == 0 && n_nodes > 0))
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: bad sizes", what);
+    if (SCORED && n_classes < 1) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: n_classes = %d", what, n_classes);
+    if (max_page_nodes > REGION_PAGE_MAX)
+        return gte::fail(GTE_ERR_UNSUPPORTED, "%s: a page of %lld nodes exceeds %d", what, (long long)max_page_nodes, REGION_PAGE_MAX);
+    if (n_nodes == 0) return GTE_OK;
+    if (!indptr || !indices || !node_off || !group || !bbox || !comp || !region_box || !region_count ||
+        (SCORED && (!logits || !class_group || !region_score)))
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    if ((((uintptr_t)bbox | (uintptr_t)region_box) & 15) != 0)
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: bbox and region_box must be 16-byte aligned", what);
+    if (SCORED && ((((uintptr_t)logits | (uintptr_t)region_score) & 3) != 0))
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: logits and region_score must be 4-byte aligned", what);
+    const int cap = (int)(max_page_nodes > 0 ? max_page_nodes : 1);
+    const size_t shm = (size_t)cap * region_node_bytes(SCORED) + REGION_TAIL_BYTES;
+    allow_region_lds<SCORED>();
+    hipLaunchKernelGGL(page_regions_kernel<SCORED>, dim3((unsigned)n_pages), dim3(REGION_THREADS), shm, gte::as_stream(stream), indptr,
+                       indices, node_off, group, bbox, cap, (int)n_nodes, comp, region_box, region_count, logits, n_classes,
+                       class_group, region_score);
+    return gte::check_launch(what);
 }
 
 }  // namespace
@@ -147,19 +220,14 @@ extern "C" int gte_region_max_page_nodes(void) { return REGION_PAGE_MAX; }
 extern "C" int gte_page_regions(const int32_t* indptr, const int32_t* indices, const int32_t* node_off, int64_t n_pages,
                                 int64_t n_nodes, int64_t max_page_nodes, const int32_t* group, const int32_t* bbox, int32_t* comp,
                                 int32_t* region_box, int32_t* region_count, void* stream) {
-    if (n_pages < 0 || n_nodes < 0 || max_page_nodes < 0 || n_pages >= INT32_MAX || n_nodes >= INT32_MAX || (n_pages == 0 && n_nodes > 0))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "page_regions: bad sizes");
-    if (max_page_nodes > REGION_PAGE_MAX)
-        return gte::fail(GTE_ERR_UNSUPPORTED, "page_regions: a page of %lld nodes exceeds %d", (long long)max_page_nodes, REGION_PAGE_MAX);
-    if (n_nodes == 0) return GTE_OK;
-    if (!indptr || !indices || !node_off || !group || !bbox || !comp || !region_box || !region_count)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "page_regions: null pointer");
-    if ((((uintptr_t)bbox | (uintptr_t)region_box) & 15) != 0)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "page_regions: bbox and region_box must be 16-byte aligned");
-    const int cap = (int)(max_page_nodes > 0 ? max_page_nodes : 1);
-    const size_t shm = (size_t)cap * REGION_NODE_BYTES + REGION_TAIL_BYTES;
-    allow_region_lds();
-    hipLaunchKernelGGL(page_regions_kernel, dim3((unsigned)n_pages), dim3(REGION_THREADS), shm, gte::as_stream(stream), indptr, indices,
-                       node_off, group, bbox, cap, (int)n_nodes, comp, region_box, region_count);
-    return gte::check_launch("page_regions");
+    return page_regions_launch<false>("page_regions", indptr, indices, node_off, n_pages, n_nodes, max_page_nodes, group, bbox, comp,
+                                      region_box, region_count, nullptr, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int gte_page_regions_scored(const int32_t* indptr, const int32_t* indices, const int32_t* node_off, int64_t n_pages,
+                                       int64_t n_nodes, int64_t max_page_nodes, const int32_t* group, const int32_t* bbox,
+                                       const float* logits, int n_classes, const int32_t* class_group, int32_t* comp,
+                                       int32_t* region_box, int32_t* region_count, float* region_score, void* stream) {
+    return page_regions_launch<true>("page_regions_scored", indptr, indices, node_off, n_pages, n_nodes, max_page_nodes, group, bbox,
+                                     comp, region_box, region_count, logits, n_classes, class_group, region_score, stream);
 }

@@ -20,6 +20,7 @@ from __future__ import annotations
 import os
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -733,13 +734,19 @@ class PageRegions(NamedTuple):
     group: torch.Tensor       # int32 [R]    region kind
     box: torch.Tensor         # int32 [R, 4] union of the words' boxes (x0, y0, x1, y1)
     n_words: torch.Tensor     # int32 [R]
+    score: Optional[torch.Tensor] = None      # float32 [R]  region confidence (page_regions(..., logits=...) only)
 
 
-def page_regions(g: PageGraph, group: torch.Tensor, bbox: torch.Tensor) -> PageRegions:
+def page_regions(g: PageGraph, group: torch.Tensor, bbox: torch.Tensor, logits: Optional[torch.Tensor] = None,
+                 class_group=None) -> PageRegions:
     """Regions of a batched page graph (a :class:`PageGraph` from :func:`batch` / :func:`knn_graph_from_boxes`, or a
     :class:`ResidentBatch`): the connected components of ``g`` restricted to nodes of one ``group`` (int [n]; < 0: in no region),
     each with the union of its words' boxes (``bbox`` int [n, 4]) -- one launch of gte_page_regions over ``g.in_csr()`` and the
-    batch's page offsets, then a torch compaction of the root rows (``nonzero`` on the counts: plumbing, one synchronisation)."""
+    batch's page offsets, then a torch compaction of the root rows (``nonzero`` on the counts: plumbing, one synchronisation).
+
+    With ``logits`` (float [n, C], the model's output for the batch) the same launch (gte_page_regions_scored) also gives every
+    region a confidence, ``score``: the mean over its words of the softmax mass on the classes of the region's kind,
+    ``class_group[c]`` = kind of class c (default :data:`DEFAULT_CLASS_GROUP`; the table ``group`` was derived from)."""
     _lib.require_device(group, "page_regions")
     _lib.require_device(bbox, "page_regions")
     lib, P = _lib.load(), _lib.ptr
@@ -760,11 +767,65 @@ def page_regions(g: PageGraph, group: torch.Tensor, bbox: torch.Tensor) -> PageR
     comp = torch.empty(n, dtype=torch.int32, device=dev)
     rbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
     count = torch.empty(n, dtype=torch.int32, device=dev)
-    _lib.check(lib.gte_page_regions(P(csr.indptr), P(csr.indices), P(node_off), sizes.numel(), n, int(sizes.max()) if sizes.numel() else 0,
-                                    P(group), P(bbox), P(comp), P(rbox), P(count), _lib.current_stream()), "gte_page_regions")
+    largest = int(sizes.max()) if sizes.numel() else 0
+    score = None
+    if logits is None:
+        if class_group is not None:
+            raise ValueError("page_regions: class_group without logits")
+        _lib.check(lib.gte_page_regions(P(csr.indptr), P(csr.indices), P(node_off), sizes.numel(), n, largest,
+                                        P(group), P(bbox), P(comp), P(rbox), P(count), _lib.current_stream()), "gte_page_regions")
+    else:
+        _lib.require_device(logits, "page_regions")
+        logits = logits.to(torch.float32).contiguous()
+        table = torch.as_tensor(DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32).to(dev).contiguous()
+        if logits.dim() != 2 or logits.shape[0] != n or logits.shape[1] < 1 or table.numel() != logits.shape[1]:
+            raise ValueError(f"page_regions: the graph has {n} nodes, logits is {tuple(logits.shape)}, class_group has "
+                             f"{table.numel()} entries")
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.gte_page_regions_scored(P(csr.indptr), P(csr.indices), P(node_off), sizes.numel(), n, largest, P(group), P(bbox),
+                                               P(logits), logits.shape[1], P(table), P(comp), P(rbox), P(count), P(score),
+                                               _lib.current_stream()), "gte_page_regions_scored")
     root = torch.nonzero(count).flatten()
     page = torch.bucketize(root, node_off[1:].long(), right=True)
-    return PageRegions(comp, root, page, group[root], rbox[root], count[root])
+    return PageRegions(comp, root, page, group[root], rbox[root], count[root], None if score is None else score[root])
+
+
+def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, iou_thr) -> torch.Tensor:
+    """Match counts of the box-level evaluation (gte_box_match, one launch): ``tp`` int32 [n_thr, R] on the device.
+
+    Cell b (one page and kind) holds the predictions ``pred_box[pred_off[b]:pred_off[b + 1]]`` (int [R, 4], inside a cell ASCENDING
+    by score) and the ground truths ``gt_box[gt_off[b]:gt_off[b + 1]]``; the offsets are host sequences.
+    ``tp[j, pred_off[b] + k]`` = greedy matches (descending IoU, ``iou > iou_thr[j]`` strictly, +1 pixel convention; include/gte.h)
+    between the cell's ground truths and its predictions ``k ..``, i.e. after pruning its k lowest-scored boxes.  ``iou_thr``:
+    1 .. 16 ascending thresholds.  Raises ``ValueError`` naming the first cell whose candidate pairs exceed
+    ``gte_box_match_max_candidates()``; ``GteError`` when a cell has more than ``gte_box_match_max_boxes()`` boxes on a side.
+    One synchronisation (the cells' status words are read before the result is handed out)."""
+    import ctypes
+    _lib.require_device(pred_box, "box_match")
+    _lib.require_device(gt_box, "box_match")
+    lib, P = _lib.load(), _lib.ptr
+    dev = pred_box.device
+    pred_box = pred_box.to(torch.int32).reshape(-1, 4).contiguous()
+    gt_box = gt_box.to(dev).to(torch.int32).reshape(-1, 4).contiguous()
+    po, go = np.asarray(pred_off, dtype=np.int64).reshape(-1), np.asarray(gt_off, dtype=np.int64).reshape(-1)
+    if po.size < 1 or po.size != go.size or po[0] != 0 or go[0] != 0 or (np.diff(po) < 0).any() or (np.diff(go) < 0).any() \
+            or po[-1] != pred_box.shape[0] or go[-1] != gt_box.shape[0]:
+        raise ValueError(f"box_match: offsets of {po.size - 1} / {go.size - 1} cells do not partition {pred_box.shape[0]} predicted and "
+                         f"{gt_box.shape[0]} ground-truth boxes")
+    cells = po.size - 1
+    thr = np.ascontiguousarray(np.asarray(iou_thr, dtype=np.float64).reshape(-1))
+    tp = torch.empty((thr.size, pred_box.shape[0]), dtype=torch.int32, device=dev)
+    status = torch.empty(cells, dtype=torch.int32, device=dev)
+    d_po, d_go = torch.from_numpy(po.astype(np.int32)).to(dev), torch.from_numpy(go.astype(np.int32)).to(dev)
+    _lib.check(lib.gte_box_match(P(pred_box), P(d_po), P(gt_box), P(d_go), cells, int(np.diff(po).max()) if cells else 0,
+                                 int(np.diff(go).max()) if cells else 0, thr.ctypes.data_as(ctypes.c_void_p), thr.size, P(tp),
+                                 P(status), _lib.current_stream()), "gte_box_match")
+    bad = torch.nonzero(status).flatten()
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"box_match: cell {b} ({int(po[b + 1] - po[b])} predicted x {int(go[b + 1] - go[b])} ground-truth boxes) has more "
+                         f"than {lib.gte_box_match_max_candidates()} pairs above IoU {thr[0]} (status {int(status[b])})")
+    return tp
 
 
 def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, max_dist: int = 500, bidirectional: bool = True,

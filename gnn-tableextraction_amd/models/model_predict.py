@@ -15,6 +15,8 @@ Output contract (what post-processing consumes):
   ``{output}/predictions/{logs}.pkl`` extra, not in the reference: ``{'all_pred': [per-page lists], 'num_nodes': [...]}``
   ``{output}/regions/{logs}.json``    ``test(..., regions=True)`` only: the regions of every page (``extract_regions``) in the layout
                                       the reference's box-level evaluation reads (``regions_json``)
+                                      (``region_scores=True``: with the regions' confidences as scores; ``box_eval=True``: the
+                                      result also holds that evaluation, ``evaluate_regions``)
 The printed accuracy is the reference's "Mean Test Accuracy": the MEAN OVER PAGES of the per-page accuracy (:150,163),
 not the node-weighted accuracy (returned as ``accuracy_nodes``).
 """
@@ -122,12 +124,15 @@ class PageForwardGraphs:
         return b["logits"][:n], b["pred"][:n]
 
 
-def predict_resident(engine, pipe, batch_pages: int, page_ids=None) -> torch.Tensor:
+def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logits=False):
     """Predictions (arg-max class per node, int64, pages concatenated in ``page_ids`` order -- default: all resident pages) with
     ``batch_pages`` pages per forward.  The reference's loop (model_predict.py:141-151) is one forward per page from the host;
     here a forward is ONE host call (``engine.forward_logits`` -> gte_gcnsage_forward) on a batch that the pipeline
     (``loop.BatchPipeline``) assembled on its side stream while the forward before it ran, and nothing synchronises until the
-    caller reads the result."""
+    caller reads the result.
+
+    ``return_logits=True``: returns ``(pred, logits)``, the logits of all nodes as ONE device tensor float32 [nodes, n_classes]
+    in the same order (every batch's view is copied out before the next forward overwrites the engine's buffer)."""
     res = pipe.res
     ids = np.arange(len(res.page_sizes()), dtype=np.int64) if page_ids is None else np.asarray(page_ids, dtype=np.int64)
     steps = [ids[i:i + batch_pages] for i in range(0, ids.size, batch_pages)]
@@ -141,8 +146,9 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None) -> torch.Ten
     pipe.load(steps)
     total = sum(pipe.nodes(s) for s in range(len(steps)))
     pred = torch.empty(total, dtype=torch.int64, device=pipe.device)
+    all_logits = None
     if not steps:
-        return pred
+        return (pred, torch.empty((0, 0), dtype=torch.float32, device=pipe.device)) if return_logits else pred
     engine.reserve(pipe.max_batch_nodes(), f0, cached=bool(res.p3_mode == "rows" and res.agg_p3 is not None))
     pipe.start(0)
     off = 0
@@ -153,12 +159,16 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None) -> torch.Ten
         logits = engine.forward_logits(g)
         n = pipe.nodes(s)
         torch.argmax(logits, dim=1, out=pred[off:off + n])
+        if return_logits:
+            if all_logits is None:
+                all_logits = torch.empty((total, logits.shape[1]), dtype=torch.float32, device=pipe.device)
+            all_logits[off:off + n].copy_(logits[:n])
         pipe.release(s)
         off += n
-    return pred
+    return (pred, all_logits) if return_logits else pred
 
 
-def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=64, device=None):
+def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=64, device=None, logits=None):
     """Regions of every page from the node predictions: connected components of the page graph among words of one predicted
     kind, each with the union of its words' boxes (``graph.page_regions`` -> gte_page_regions; the reference's
     ``get_subgraph_bbox`` is a stub, its PyMuPDF block voting is out of scope -- DESIGN 10).
@@ -167,11 +177,20 @@ def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=6
     ``class_group[c]`` = region kind of class c, < 0 for none (default ``graph.DEFAULT_CLASS_GROUP``: the reference's category
     values, the three table classes merged into TABLE = 4); boxes from ``data.pages[i]['bboxs']``.  ``batch_pages`` pages go
     through one launch.  Returns, per page, a list of ``(group, [x0, y0, x1, y1], n_words)`` in ascending order of the region's
-    first word; regions of fewer than ``min_words`` words are dropped after the compaction."""
+    first word; regions of fewer than ``min_words`` words are dropped after the compaction.
+
+    ``logits`` (float [all nodes, n_classes], the pages concatenated in ``data.graphs`` order; a tensor on any device or an array):
+    the tuples become ``(group, box, n_words, score)``, score = the region's confidence from the same launch
+    (gte_page_regions_scored: the mean over the region's words of the softmax mass on the classes of its kind)."""
     device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     sizes = [g.num_nodes() for g in data.graphs]
     if len(all_pred) != len(sizes):
         raise ValueError(f"extract_regions: {len(all_pred)} prediction lists for {len(sizes)} pages")
+    node_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if logits is not None:
+        logits = torch.as_tensor(logits)
+        if logits.dim() != 2 or logits.shape[0] != int(node_off[-1]):
+            raise ValueError(f"extract_regions: logits of shape {tuple(logits.shape)} for {int(node_off[-1])} nodes")
     table = torch.as_tensor(G.DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32, device=device)
     out = [[] for _ in sizes]
     bp = max(1, int(batch_pages))
@@ -192,31 +211,141 @@ def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=6
             raise ValueError(f"extract_regions: pages {ids.start}..{ids.stop - 1} have {bg.num_nodes()} nodes, {pred.shape[0]} "
                              f"predictions and {boxes.shape[0]} boxes")
         group = table[torch.from_numpy(pred).to(device)]                                  # class -> kind: a gather
-        reg = G.page_regions(bg, group, torch.from_numpy(boxes).to(device))
+        if logits is None:
+            reg = G.page_regions(bg, group, torch.from_numpy(boxes).to(device))
+        else:
+            reg = G.page_regions(bg, group, torch.from_numpy(boxes).to(device),
+                                 logits=logits[int(node_off[ids.start]):int(node_off[ids.stop])].to(device), class_group=table)
         keep = reg.n_words >= int(min_words)
-        for p, k, bx, nw in zip(reg.page[keep].tolist(), reg.group[keep].tolist(), reg.box[keep].tolist(), reg.n_words[keep].tolist()):
-            out[b0 + p].append((k, bx, nw))
+        rows = [reg.page[keep].tolist(), reg.group[keep].tolist(), reg.box[keep].tolist(), reg.n_words[keep].tolist()]
+        if logits is not None:
+            rows.append(reg.score[keep].tolist())
+        for p, *rest in zip(*rows):
+            out[b0 + p].append(tuple(rest))
     return out
 
 
 def regions_json(data, regions):
     """``{kind_name: {page_name: {'bboxes': [...], 'scores': [...]}}}``: the layout the reference's box-level evaluation reads
-    (postprocessing.py:326-345 write_json -> utils/metrics.py), kind names = the lower-case category names; every score is
-    1.0, as in the reference's own writer."""
+    (postprocessing.py:326-345 write_json -> utils/metrics.py), kind names = the lower-case category names; the score of a
+    region is its confidence where its tuple carries one (``extract_regions(..., logits=...)``) and 1.0, as in the reference's
+    own writer, otherwise."""
     doc = {name: {} for name in G.GROUP_NAMES.values()}
     for i, page in enumerate(regions):
         name = str(data.pages[i]['page'])
-        for kind, box, _ in page:
+        for kind, box, *rest in page:
             entry = doc.setdefault(G.GROUP_NAMES.get(kind, str(kind)), {}).setdefault(name, {'bboxes': [], 'scores': []})
             entry['bboxes'].append([int(v) for v in box])
-            entry['scores'].append(1.0)
+            entry['scores'].append(float(rest[1]) if len(rest) > 1 else 1.0)
     return doc
 
 
-def test(data, config, weights_path=None, save_predictions=True, regions=False):
+def regions_gt_json(data, regions):
+    """``{kind_name: {page_name: [box, ...]}}``: regions as the GROUND-TRUTH document of the box-level evaluation
+    (``evaluate_regions``; the layout of the reference's ground-truth JSON, utils/metrics.py ``gt_boxes``)."""
+    doc = {name: {} for name in G.GROUP_NAMES.values()}
+    for i, page in enumerate(regions):
+        name = str(data.pages[i]['page'])
+        for kind, box, *_ in page:
+            doc.setdefault(G.GROUP_NAMES.get(kind, str(kind)), {}).setdefault(name, []).append([int(v) for v in box])
+    return doc
+
+
+def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, device=None):
+    """Box-level evaluation of predicted regions: the reference's AP at IoU thresholds (``get_avg_precision_at_iou`` of
+    src/utils/metrics.py:162-244 per kind and threshold, their mean as in evaluate.py:116-129), with the box matching of all
+    pages, kinds and thresholds in ONE launch (``graph.box_match`` -> gte_box_match) and the curve from its integer counts.
+
+    ``pred_doc[kind][page] = {'bboxes': [[x0, y0, x1, y1], ...], 'scores': [...]}`` (``regions_json``), ``gt_doc[kind][page] =
+    [[x0, y0, x1, y1], ...]`` (``regions_gt_json``); ``iou_thrs``: 1 .. 16 ascending thresholds (default
+    ``np.linspace(0.5, 0.95, 10)``).  What the reference computes is NOT the textbook sweep, and this restates it exactly:
+
+    * only PAIRED pages count: a page enters a kind's sums when it is a key of both ``pred_doc[kind]`` and ``gt_doc[kind]``.  The
+      boxes of a page that only one of the two knows are ignored (metrics.py:202-206) -- unless ``count_unpaired=True``, which
+      is NOT the reference: it counts the ground truths of such a page as false negatives and its predictions (those that the
+      page's state below keeps) as false positives;
+    * the score thresholds are the distinct scores of all the kind's predictions, ascending (unpaired pages included);
+    * a page's state LAGS: at threshold t it keeps its predictions with score >= c, c = the largest of the page's OWN scores
+      <= t (all of them below its first own score) -- a page is re-pruned only when the sweep reaches one of its own scores, so
+      a lower-scored box survives until the page's next own score;
+    * per page: IoU with the +1 pixel convention, candidates ``iou > thr`` strictly, greedy matching in descending IoU (among
+      equal IoUs the larger ``pred_index * n_gt + gt_index`` first; predictions in stable ascending score order); tp = matches,
+      fp = kept predictions - tp, fn = ground truths - tp;
+    * precision = sum tp / (sum tp + sum fp), recall with fn, 0.0 on a zero denominator; AP = the mean over the recall levels
+      ``linspace(0, 1, 11)`` of the largest precision at ``recall >= level`` (0.0 where there is none).
+
+    Returns ``{kind: {'ap': [per IoU threshold], 'map': mean, 'precisions': [[...] per IoU threshold], 'recalls': [[...]],
+    'thresholds': [score thresholds]}, ..., 'map': mean of the kinds' 'map'}`` over the kinds of ``gt_doc`` and ``pred_doc``."""
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    iou_thrs = np.linspace(0.5, 0.95, 10) if iou_thrs is None else np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    kinds = list(gt_doc) + [k for k in pred_doc if k not in gt_doc]
+    # ---- the cells: one per (kind, page) that counts, predictions in stable ascending score order --------------------------
+    cells, pbox, gbox, po, go = [], [], [], [0], [0]
+    for kind in kinds:
+        preds, gts = pred_doc.get(kind, {}), gt_doc.get(kind, {})
+        pages = [pg for pg in gts if pg in preds or count_unpaired] + [pg for pg in preds if pg not in gts and count_unpaired]
+        for pg in pages:
+            sc = np.asarray(preds[pg]['scores'], dtype=np.float64).reshape(-1) if pg in preds else np.zeros(0)
+            bx = np.asarray(preds[pg]['bboxes'], dtype=np.int64).reshape(-1, 4) if pg in preds else np.zeros((0, 4), dtype=np.int64)
+            gb = np.asarray(gts.get(pg, []), dtype=np.int64).reshape(-1, 4)
+            if sc.shape[0] != bx.shape[0]:
+                raise ValueError(f"evaluate_regions: {kind} / {pg}: {bx.shape[0]} boxes, {sc.shape[0]} scores")
+            for what, a in (("predicted", bx), ("ground-truth", gb)):
+                if a.size and ((a[:, 0] > a[:, 2]).any() or (a[:, 1] > a[:, 3]).any() or np.abs(a).max() >= 1 << 24):
+                    raise ValueError(f"evaluate_regions: {kind} / {pg}: a {what} box is malformed (metrics.py:35-40) or outside +-2^24")
+            order = np.argsort(sc, kind='stable')
+            cells.append((kind, sc[order]))
+            pbox.append(bx[order])
+            gbox.append(gb)
+            po.append(po[-1] + bx.shape[0])
+            go.append(go[-1] + gb.shape[0])
+    tp = np.zeros((iou_thrs.size, 0), dtype=np.int64)
+    if cells:
+        tp = G.box_match(torch.from_numpy(np.concatenate(pbox).astype(np.int32)).to(device), po,
+                         torch.from_numpy(np.concatenate(gbox).astype(np.int32)).to(device), go, iou_thrs).cpu().numpy().astype(np.int64)
+    # ---- the sweep: a page's counts change only at its own scores -> per-event deltas, one cumulative sum -------------------
+    out = {}
+    for kind in kinds:
+        thr = np.unique(np.asarray([s for e in pred_doc.get(kind, {}).values() for s in e['scores']], dtype=np.float64))
+        d_tp, d_fp, d_fn = (np.zeros((iou_thrs.size, thr.size), dtype=np.int64) for _ in range(3))
+        for b, (ck, sc) in enumerate(cells):
+            if ck != kind or thr.size == 0:
+                continue
+            r, g = sc.shape[0], go[b + 1] - go[b]
+            own = np.unique(sc)                                              # the page's own scores, ascending
+            k = np.concatenate([[0], np.searchsorted(sc, own[1:], side='left')]).astype(np.int64) if r else np.zeros(1, dtype=np.int64)
+            at = np.concatenate([[0], np.searchsorted(thr, own[1:])]).astype(np.int64) if r else np.zeros(1, dtype=np.int64)
+            t = tp[:, po[b] + k] if r else np.zeros((iou_thrs.size, 1), dtype=np.int64)      # [n_iou, events]
+            for acc, val in ((d_tp, t), (d_fp, (r - k)[None, :] - t), (d_fn, g - t)):
+                val = np.diff(val, axis=1, prepend=0)                        # the first event carries the whole state k = 0
+                acc[:, at] += val                                             # (own scores are distinct: so are the columns)
+        s_tp, s_fp, s_fn = (np.cumsum(d, axis=1) for d in (d_tp, d_fp, d_fn))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            prec = np.where(s_tp + s_fp > 0, s_tp / (s_tp + s_fp), 0.0)
+            rec = np.where(s_tp + s_fn > 0, s_tp / (s_tp + s_fn), 0.0)
+        ap = []
+        for j in range(iou_thrs.size):
+            levels = [prec[j][rec[j] >= lv] for lv in np.linspace(0.0, 1.0, 11)]
+            ap.append(float(np.mean([a.max() if a.size else 0.0 for a in levels])))
+        out[kind] = {'ap': ap, 'map': float(np.mean(ap)), 'precisions': prec.tolist(), 'recalls': rec.tolist(),
+                     'thresholds': thr.tolist()}
+    out['map'] = float(np.mean([out[k]['map'] for k in kinds])) if kinds else 0.0
+    return out
+
+
+def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False):
     """``regions=True``: the result gains ``'regions'`` (``extract_regions`` of the predictions: per page a list of
     ``(group, [x0, y0, x1, y1], n_words)``), and with ``save_predictions`` ``{output}/regions/{logs}.json`` is written
-    (``regions_json``).  No region confidence exists yet: every score in that file is 1.0."""
+    (``regions_json``) with every score 1.0.
+
+    ``region_scores=True`` (implies ``regions``): the tuples are ``(group, box, n_words, score)``, score = the region's
+    confidence from the model's own logits (gte_page_regions_scored), and the JSON carries these scores.
+
+    ``box_eval=True`` (implies ``region_scores``): the result gains ``'box_eval'`` = ``evaluate_regions`` of the scored regions
+    against the ground-truth regions that the same component rule forms from the pages' labels (``extract_regions(data,
+    labels)``: the only box-level ground truth that pre-built pages carry) -- the reference's AP at IoU 0.50 .. 0.95 and mAP."""
+    region_scores = bool(region_scores or box_eval)
+    regions = bool(regions or region_scores)
     if not (config.TRAINING.gpu >= 0 and torch.cuda.is_available()):
         raise RuntimeError("model_predict runs on the MI355X HIP path only (no CPU fallback)")
     device = torch.device('cuda', config.TRAINING.gpu)
@@ -235,6 +364,7 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False):
     all_pred, all_true = [], []
     mean_test_acc = 0.0
     engine = None
+    flat_logits = None                                     # region_scores: the logits of all nodes, pages in data.graphs order
     if len(data.graphs) > 0:
         # evaluation applies no dropout: a model trained with --dropout takes the same path (forward_logits binds the p = 0 plan);
         # only a model the engine refuses to build for (a dropout model outside the one-call plan) keeps the module loop below
@@ -249,7 +379,11 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False):
         # forward (predict_resident); one device -> host copy of all predictions at the end
         from .loop import BatchPipeline
         pipe = BatchPipeline(G.ResidentPages(data.graphs, device))
-        flat_pred = predict_resident(engine, pipe, bs).cpu().numpy()
+        if region_scores:
+            flat_pred, flat_logits = predict_resident(engine, pipe, bs, return_logits=True)
+            flat_pred = flat_pred.cpu().numpy()
+        else:
+            flat_pred = predict_resident(engine, pipe, bs).cpu().numpy()
         off = 0
         for g in data.graphs:
             n = g.num_nodes()
@@ -259,17 +393,23 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False):
             mean_test_acc += float((pp == tt).sum()) / max(n, 1)                          # per-page accuracy (:150)
             off += n
     else:
+        kept = []
         with torch.no_grad():
             for b0 in range(0, len(data.graphs), bs):
                 pages = [g.to(device) for g in data.graphs[b0:b0 + bs]]
                 bg = G.batch(pages)
-                pred = model(bg).argmax(dim=1).cpu().numpy()
+                logits = model(bg)
+                if region_scores:
+                    kept.append(logits.float().clone())
+                pred = logits.argmax(dim=1).cpu().numpy()
                 off = np.cumsum([0] + [g.num_nodes() for g in pages])
                 for i, g in enumerate(pages):
                     pp, tt = pred[off[i]:off[i + 1]], g.ndata['label'].long().cpu().numpy()
                     all_pred.append(pp)
                     all_true.append(tt)
                     mean_test_acc += float((pp == tt).sum()) / max(g.num_nodes(), 1)      # per-page accuracy (:150)
+        if kept:
+            flat_logits = torch.cat(kept)
     y_pred, y_true = np.concatenate(all_pred), np.concatenate(all_true)
     p, r, f1, conf = per_class_prf(y_true, y_pred, n_classes)
     acc_nodes = float((y_pred == y_true).mean()) if len(y_true) else 0.0
@@ -289,11 +429,18 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False):
     result = {'accuracy': acc, 'accuracy_nodes': acc_nodes, 'precision': p, 'recall': r, 'f1': f1, 'confusion': conf,
               'all_pred': all_pred, 'all_pred_flat': flat}
     if regions:
-        result['regions'] = extract_regions(data, all_pred, batch_pages=bs, device=device)
+        if region_scores and flat_logits is None:
+            flat_logits = torch.empty((0, n_classes), dtype=torch.float32, device=device)
+        result['regions'] = extract_regions(data, all_pred, batch_pages=bs, device=device, logits=flat_logits if region_scores else None)
+        doc = regions_json(data, result['regions']) if (save_predictions or box_eval) else None
         if save_predictions:
             import json
             reg_dir = os.path.join(out_root, 'regions')
             os.makedirs(reg_dir, exist_ok=True)
             with open(os.path.join(reg_dir, f'{logs}.json'), 'w') as f:
-                json.dump(regions_json(data, result['regions']), f)
+                json.dump(doc, f)
+        if box_eval:
+            labels = [g.ndata['label'].long().cpu().numpy() for g in data.graphs]
+            gt = regions_gt_json(data, extract_regions(data, labels, batch_pages=bs, device=device))
+            result['box_eval'] = evaluate_regions(doc, gt, device=device)
     return result

@@ -184,6 +184,46 @@ int gte_page_regions(const int32_t* indptr, const int32_t* indices, const int32_
                      int64_t max_page_nodes, const int32_t* group, const int32_t* bbox, int32_t* comp, int32_t* region_box,
                      int32_t* region_count, void* stream);
 
+/* gte_page_regions with a confidence per region, from the model's own logits, in the same launch.  logits float [n_nodes,
+ * n_classes] (packed rows), class_group int32 [n_classes] = the region kind of every class (the table the caller derived `group`
+ * from: group[v] = class_group[argmax logits[v]] is the usual choice, but `group` stays an input).  For a member word v of kind
+ * k = group[v]:  p(v) = sum over the classes c with class_group[c] == k of softmax(logits[v])[c]  (fp32, max-subtracted; 0 for a
+ * row that holds a non-finite logit), and
+ *   region_score[v]  roots: the mean of p over the members; every other row 0.0f (a page above max_page_nodes: all 0.0f).
+ * comp, region_box and region_count are bit for bit what gte_page_regions writes for the same `group`.  Deterministic: a word
+ * adds q(v) = (uint32)(p(v) * 2^19 + 0.5) to its root with an LDS integer atomic (<= 4096 words of q <= 2^19: the sum fits 32
+ * unsigned bits), and the score is (float)((double)sum / ((double)count * 2^19)) -- within 2^-18 of the exact mean.  n_classes
+ * >= 1; the same limits, alignment and error codes as gte_page_regions. */
+int gte_page_regions_scored(const int32_t* indptr, const int32_t* indices, const int32_t* node_off, int64_t n_pages, int64_t n_nodes,
+                            int64_t max_page_nodes, const int32_t* group, const int32_t* bbox, const float* logits, int n_classes,
+                            const int32_t* class_group, int32_t* comp, int32_t* region_box, int32_t* region_count,
+                            float* region_score, void* stream);
+
+/* ---- box matching for the box-level evaluation (AP at IoU thresholds; src/utils/metrics.py:20-114 get_single_image_results) ----
+ * A CELL is one (page, kind) pair: its predicted boxes pred_box[pred_off[b] .. pred_off[b + 1]) in ASCENDING order of their score
+ * and its ground-truth boxes gt_box[gt_off[b] .. gt_off[b + 1]); boxes are int32 (x0, y0, x1, y1), x0 <= x1, y0 <= y1, extents
+ * (x1 - x0 + 1) <= 2^25 (a box outside that overlaps nothing).  iou_thr: HOST array of n_thr (1 .. 16) finite thresholds >= 0 in
+ * ascending order.  With R_b / G_b the cell's box counts and R = pred_off[n_cells]:
+ *   iou(p, g)      0 where the boxes are disjoint (x1 < x0' ...: boxes that touch are NOT disjoint), otherwise
+ *                  inter / (area_p + area_g - inter) with the +1 pixel convention, exact integers divided in fp64;
+ *   tp[j * R + pred_off[b] + k]   the number of matches between the ground truths and the predictions k .. R_b - 1 (what is left
+ *                  after pruning the k lowest-scored boxes) at iou_thr[j]: candidates are the pairs with iou > iou_thr[j],
+ *                  strictly; they are taken greedily in descending IoU, among equal IoUs the larger p * G_b + g first (p, g:
+ *                  positions inside the cell), a pair is a match when neither of its boxes is matched yet.
+ *                  (false positives = R_b - k - tp, false negatives = G_b - tp: the caller's arithmetic.)
+ *   cell_status[b] 0: fine; 1: the cell has more than gte_box_match_max_candidates() pairs above iou_thr[0], its tp entries are
+ *                  all -1; 2: the cell exceeds max_pred_per_cell / max_gt_per_cell or its offsets are not ascending inside
+ *                  [0, R] / [0, G] (tp -1 where the rows exist).  Other cells are not affected.
+ * A cell with R_b = 0 or G_b = 0 writes its (possibly empty) rows of zeros and status 0.  max_pred_per_cell / max_gt_per_cell =
+ * the largest R_b / G_b (the offsets live on the device): above gte_box_match_max_boxes() the call returns GTE_ERR_UNSUPPORTED
+ * before any launch.  One launch, one workgroup per cell, integer outputs, no workspace, no synchronisation.  pred_box and gt_box
+ * 16-byte aligned. */
+int gte_box_match_max_boxes(void);        /* per cell and side: 256 */
+int gte_box_match_max_candidates(void);   /* per cell: 4096 */
+int gte_box_match(const int32_t* pred_box, const int32_t* pred_off, const int32_t* gt_box, const int32_t* gt_off, int64_t n_cells,
+                  int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr, int32_t* tp,
+                  int32_t* cell_status, void* stream);
+
 /* The whole batch in ONE launch (what the train loop calls every step; gte_batch_csr / gte_batch_rows are its pieces):
  * a page's rows are CONTIGUOUS in the resident arrays and in the batch, so every array of the batch is the concatenation
  * of per-page runs -- features and labels copied, indptr / indices copied with a per-page constant added.  Workgroup

@@ -1,0 +1,93 @@
+"""CPU-only: the limits and argument checks of gte_page_regions_scored and gte_box_match (every call returns before a launch: the
+device pointers are dummies; the IoU thresholds are a host array that the entry reads)."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_tableextraction_amd import _lib, graph as G
+from gnn_tableextraction_amd.models import model_predict
+
+_P = 0x10000          # a dummy 16-byte aligned address: never dereferenced, no call below reaches a launch
+INVALID, UNSUPPORTED = -1, -4
+
+
+def _scored(lib, **change):
+    args = dict(indptr=_P, indices=_P, node_off=_P, n_pages=3, n_nodes=100, max_page_nodes=50, group=_P, bbox=_P, logits=_P, n_classes=9,
+                class_group=_P, comp=_P, region_box=_P, region_count=_P, region_score=_P, stream=None)
+    assert set(change) <= set(args)
+    args.update(change)
+    return lib.gte_page_regions_scored(*args.values())
+
+
+def _match(lib, thr=(0.5, 0.75), **change):
+    thr = np.asarray(thr, dtype=np.float64)
+    args = dict(pred_box=_P, pred_off=_P, gt_box=_P, gt_off=_P, n_cells=4, max_pred=10, max_gt=10,
+                iou_thr=thr.ctypes.data_as(ctypes.c_void_p), n_thr=thr.size, tp=_P, cell_status=_P, stream=None)
+    assert set(change) <= set(args)
+    args.update(change)
+    return lib.gte_box_match(*args.values())
+
+
+def test_the_limits():
+    lib = _lib.load()
+    assert lib.gte_box_match_max_boxes() >= 256 and lib.gte_box_match_max_candidates() >= 4096
+
+
+def test_scored_regions_return_error_codes_without_launching():
+    lib = _lib.load()
+    limit = lib.gte_region_max_page_nodes()
+    assert _scored(lib, max_page_nodes=limit + 1) == UNSUPPORTED and b"exceeds" in lib.gte_last_error()
+    assert _scored(lib, n_pages=-1) == INVALID and _scored(lib, n_nodes=-1) == INVALID and _scored(lib, max_page_nodes=-1) == INVALID
+    assert _scored(lib, n_pages=0) == INVALID
+    assert _scored(lib, n_classes=0) == INVALID and _scored(lib, n_classes=-3) == INVALID
+    for name in ("comp", "region_box", "region_count", "region_score", "indptr", "indices", "node_off", "group", "bbox", "logits",
+                 "class_group"):
+        assert _scored(lib, **{name: None}) == INVALID and b"null" in lib.gte_last_error(), name
+    assert _scored(lib, bbox=_P + 4) == INVALID and b"aligned" in lib.gte_last_error()
+    assert _scored(lib, region_box=_P + 8) == INVALID
+    assert _scored(lib, logits=_P + 2) == INVALID and b"aligned" in lib.gte_last_error()
+    assert _scored(lib, n_nodes=0, n_pages=0, region_score=None) == 0          # nothing to do
+
+
+def test_box_match_returns_error_codes_without_launching():
+    lib = _lib.load()
+    limit = lib.gte_box_match_max_boxes()
+    assert _match(lib, n_cells=-1) == INVALID and _match(lib, max_pred=-1) == INVALID and _match(lib, max_gt=-1) == INVALID
+    assert _match(lib, n_thr=0) == INVALID and b"thresholds" in lib.gte_last_error()
+    assert _match(lib, thr=np.linspace(0.1, 0.9, 17)) == INVALID and b"thresholds" in lib.gte_last_error()
+    assert _match(lib, iou_thr=None) == INVALID and b"null" in lib.gte_last_error()
+    assert _match(lib, thr=(0.75, 0.5)) == INVALID and b"ascending" in lib.gte_last_error()
+    assert _match(lib, thr=(0.5, float("nan"))) == INVALID and _match(lib, thr=(-0.5, 0.5)) == INVALID
+    assert _match(lib, max_pred=limit + 1) == UNSUPPORTED and b"exceeds" in lib.gte_last_error()
+    assert _match(lib, max_gt=limit + 1) == UNSUPPORTED
+    assert _match(lib, max_gt=limit + 1, tp=None) == UNSUPPORTED               # the check that stands first
+    for name in ("pred_box", "pred_off", "gt_box", "gt_off", "tp", "cell_status"):
+        assert _match(lib, **{name: None}) == INVALID and b"null" in lib.gte_last_error(), name
+    assert _match(lib, pred_box=_P + 4) == INVALID and b"aligned" in lib.gte_last_error()
+    assert _match(lib, gt_box=_P + 8) == INVALID
+    assert _match(lib, n_cells=0, cell_status=None) == 0                       # nothing to do
+    with pytest.raises(_lib.GteError):
+        _lib.check(_match(lib, n_thr=17), "probe")
+
+
+def test_the_wrappers_refuse_host_tensors_and_bad_documents():
+    g = G.PageGraph([0, 1], [1, 0], 2)
+    with pytest.raises(_lib.GteError):
+        G.page_regions(g, torch.zeros(2, dtype=torch.int32), torch.zeros((2, 4), dtype=torch.int32), logits=torch.zeros((2, 9)))
+    with pytest.raises(_lib.GteError):
+        G.box_match(torch.zeros((1, 4), dtype=torch.int32), [0, 1], torch.zeros((1, 4), dtype=torch.int32), [0, 1], [0.5])
+    bad = {"table": {"p": {"bboxes": [[5, 0, 1, 9]], "scores": [1.0]}}}
+    with pytest.raises(ValueError, match="malformed"):
+        model_predict.evaluate_regions(bad, {"table": {"p": [[0, 0, 9, 9]]}}, device="cpu")
+
+
+def test_regions_json_writes_the_score_of_a_tuple_that_has_one():
+    class Data:
+        pages = [{"page": "a.png"}, {"page": "b.png"}]
+    doc = model_predict.regions_json(Data, [[(4, [0, 1, 2, 3], 7, 0.625), (1, [4, 5, 6, 7], 2)], []])
+    assert doc["table"] == {"a.png": {"bboxes": [[0, 1, 2, 3]], "scores": [0.625]}}
+    assert doc["text"] == {"a.png": {"bboxes": [[4, 5, 6, 7]], "scores": [1.0]}}
+    assert model_predict.regions_gt_json(Data, [[(4, [0, 1, 2, 3], 7)], [(4, [1, 1, 2, 2], 1, 0.5)]])["table"] == \
+        {"a.png": [[0, 1, 2, 3]], "b.png": [[1, 1, 2, 2]]}

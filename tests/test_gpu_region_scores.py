@@ -1,0 +1,182 @@
+"""Region confidences on the device (gte_page_regions_scored, graph.page_regions(..., logits=...), extract_regions(..., logits=...))
+against gte_page_regions (bit for bit) and the float64 score reference of tests/boxeval_ref.py.
+
+The score bound is derived, not measured: a word's q is p * 2^19 rounded (<= 2^-20), p comes from an fp32 max-subtracted softmax
+(expf and n_classes <= 16 additions: far below 2^-19), the mean of exact integers is one fp64 division and one rounding to fp32
+(<= 2^-25 at a score <= 1) -- in all below 2^-18."""
+import numpy as np
+import pytest
+import torch
+
+from gnn_tableextraction_amd import _lib
+from gnn_tableextraction_amd import graph as G
+from gnn_tableextraction_amd.components.graphs.loader import PrebuiltPages
+from gnn_tableextraction_amd.data import synthetic as S
+from gnn_tableextraction_amd.models import model_predict
+from tests import boxeval_ref as bref
+from tests import regions_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+SENTINEL = 0x5A5A5A5A
+BOUND = 2.0 ** -18
+
+
+def _t(a, dtype=np.int32):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dtype))).to(DEV)
+
+
+def _abi(indptr, indices, node_off, group, bbox, logits=None, class_group=None):
+    """One direct call of gte_page_regions (logits None) or gte_page_regions_scored on sentinel-prefilled outputs ->
+    (comp, box, count[, score]) as numpy arrays."""
+    lib, P = _lib.load(), _lib.ptr
+    n = len(group)
+    d_indptr, d_indices, d_off, d_group, d_bbox = _t(indptr), _t(indices), _t(node_off), _t(group), _t(np.asarray(bbox).reshape(-1, 4))
+    comp = torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV)
+    box = torch.full((n, 4), SENTINEL, dtype=torch.int32, device=DEV)
+    count = torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV)
+    sizes = np.diff(np.asarray(node_off))
+    if logits is None:
+        _lib.check(lib.gte_page_regions(P(d_indptr), P(d_indices), P(d_off), len(sizes), n, int(sizes.max()), P(d_group), P(d_bbox),
+                                        P(comp), P(box), P(count), _lib.current_stream()), "gte_page_regions")
+        torch.cuda.synchronize()
+        return comp.cpu().numpy(), box.cpu().numpy(), count.cpu().numpy()
+    d_logits, d_table = _t(logits, np.float32), _t(class_group)
+    score = torch.full((n,), 12345.0, dtype=torch.float32, device=DEV)
+    _lib.check(lib.gte_page_regions_scored(P(d_indptr), P(d_indices), P(d_off), len(sizes), n, int(sizes.max()), P(d_group), P(d_bbox),
+                                           P(d_logits), d_logits.shape[1], P(d_table), P(comp), P(box), P(count), P(score),
+                                           _lib.current_stream()), "gte_page_regions_scored")
+    torch.cuda.synchronize()
+    return comp.cpu().numpy(), box.cpu().numpy(), count.cpu().numpy(), score.cpu().numpy()
+
+
+def _boxes(rng, n):
+    x0, y0 = rng.integers(0, 1500, n), rng.integers(0, 2200, n)
+    return np.stack([x0, y0, x0 + rng.integers(1, 120, n), y0 + rng.integers(1, 40, n)], axis=1).astype(np.int32)
+
+
+@pytest.fixture(scope="module")
+def pages():
+    """pages of 1, 0, 7, 300 and 4096 nodes (tests/test_gpu_regions.py: a single node, an empty page, below and above one
+    workgroup's threads, the limit), random edges inside pages, groups from {-1, 0, 1, 2}; + the same graph with the entries of
+    every CSR row permuted; + the plain launch's outputs."""
+    rng = np.random.default_rng(11)
+    sizes = [1, 0, 7, 300, _lib.load().gte_region_max_page_nodes()]
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    n = int(off[-1])
+    src, dst = [], []
+    for p, s in enumerate(sizes):
+        e = int(0.7 * s)
+        src.append(off[p] + rng.integers(0, max(s, 1), e))
+        dst.append(off[p] + rng.integers(0, max(s, 1), e))
+    src, dst = np.concatenate(src), np.concatenate(dst)
+    group = rng.integers(-1, 3, n).astype(np.int32)
+    bbox = _boxes(rng, n)
+    indptr, indices = ref.in_csr(src, dst, n)
+    permuted = indices.copy()
+    for v in range(n):
+        permuted[indptr[v]:indptr[v + 1]] = rng.permutation(indices[indptr[v]:indptr[v + 1]])
+    assert (permuted != indices).any()
+    return dict(n=n, off=off, group=group, bbox=bbox, indptr=indptr, indices=indices, permuted=permuted,
+                plain=_abi(indptr, indices, off, group, bbox))
+
+
+@pytest.mark.parametrize("n_classes", [1, 9, 16])
+def test_scored_launch_over_page_sizes_and_class_counts(pages, n_classes):
+    """The bound 2^-18 is the derived one of this module's docstring.  Measured on an MI355X, maximum |score - float64 reference|:
+    0 at 1 class, 0.576 units of 2^-19 at 9 classes, 0.584 units at 16 -- the quantisation's half unit and a little: below 2^-19."""
+    g = pages
+    rng = np.random.default_rng(100 + n_classes)
+    class_group = rng.integers(-1, 3, n_classes).astype(np.int32)
+    class_group[0] = 0
+    logits = (4.0 * rng.standard_normal((g["n"], n_classes))).astype(np.float32)
+    comp, box, count, score = _abi(g["indptr"], g["indices"], g["off"], g["group"], g["bbox"], logits, class_group)
+    for name, a, b in zip(("comp", "region_box", "region_count"), (comp, box, count), g["plain"]):
+        np.testing.assert_array_equal(a, b, err_msg=name)
+    want = bref.region_scores_ref(comp, g["group"], logits, class_group)
+    root = comp == np.arange(g["n"])
+    assert root.sum() > 100 and count.max() > 3
+    err = float(np.abs(score.astype(np.float64) - want).max())
+    print(f"n_classes={n_classes}: max |score - ref| = {err:.3e} = {err * 2 ** 19:.3f} units of 2^-19")
+    assert err <= BOUND
+    assert score.dtype == np.float32 and (score[~root] == 0.0).all() and (score >= 0).all() and (score <= 1).all()
+    assert (want[root] > 0).any()
+    again = _abi(g["indptr"], g["indices"], g["off"], g["group"], g["bbox"], logits, class_group)
+    shuffled = _abi(g["indptr"], g["permuted"], g["off"], g["group"], g["bbox"], logits, class_group)
+    for a, b, c in zip((comp, box, count, score), again, shuffled):
+        assert a.tobytes() == b.tobytes() == c.tobytes()
+
+
+def test_a_full_page_of_one_class_in_one_region_scores_exactly_one():
+    """4096 words on a path, every class of the one kind: p = 1 for every word, the fixed-point sum is 2^31 -- the case that needs
+    all 32 bits of the accumulator."""
+    n = _lib.load().gte_region_max_page_nodes()
+    rng = np.random.default_rng(2)
+    order = rng.permutation(n)
+    indptr, indices = ref.in_csr(order[:-1], order[1:], n)
+    bbox = _boxes(rng, n)
+    for n_classes in (1, 9):
+        logits = (5.0 * rng.standard_normal((n, n_classes))).astype(np.float32)
+        comp, box, count, score = _abi(indptr, indices, [0, n], np.zeros(n, dtype=np.int32), bbox, logits, np.zeros(n_classes, dtype=np.int32))
+        assert (comp == 0).all() and count[0] == n
+        assert score[0] == np.float32(1.0) and not score[1:].any()
+
+
+def test_a_row_with_a_non_finite_logit_contributes_zero():
+    # one region of four words (a path), two classes of its kind 3 and one of another kind; rows 1 / 2 hold a NaN / an infinity
+    indptr, indices = ref.in_csr([0, 1, 2], [1, 2, 3], 4)
+    logits = np.log(np.array([[0.5, 0.25, 0.25], [0.2, 0.4, 0.4], [0.3, 0.3, 0.4], [0.1, 0.6, 0.3]])).astype(np.float32)
+    logits[1, 2], logits[2, 0] = np.nan, np.inf
+    group = np.full(4, 3, dtype=np.int32)
+    comp, _, count, score = _abi(indptr, indices, [0, 4], group, _boxes(np.random.default_rng(0), 4), logits, [3, 0, 3])
+    assert (comp == 0).all() and count[0] == 4
+    assert abs(float(score[0]) - (0.75 + 0.0 + 0.0 + 0.4) / 4) <= BOUND and not score[1:].any()
+    assert abs(float(score[0]) - bref.region_scores_ref(comp, group, logits, [3, 0, 3])[0]) <= BOUND
+
+
+def test_a_page_above_max_page_nodes_writes_no_regions_and_score_zero():
+    lib, P = _lib.load(), _lib.ptr
+    n = 40
+    indptr, indices = ref.in_csr(np.arange(n - 1), np.arange(1, n), n)
+    args = [_t(indptr), _t(indices), _t([0, 8, n]), _t(np.zeros(n)), _t(_boxes(np.random.default_rng(1), n)),
+            _t(np.zeros((n, 2)), np.float32), _t([0, 0])]
+    comp = torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV)
+    box = torch.full((n, 4), SENTINEL, dtype=torch.int32, device=DEV)
+    count = torch.full((n,), SENTINEL, dtype=torch.int32, device=DEV)
+    score = torch.full((n,), 12345.0, dtype=torch.float32, device=DEV)
+    _lib.check(lib.gte_page_regions_scored(P(args[0]), P(args[1]), P(args[2]), 2, n, 8, P(args[3]), P(args[4]), P(args[5]), 2, P(args[6]),
+                                           P(comp), P(box), P(count), P(score), _lib.current_stream()), "gte_page_regions_scored")
+    torch.cuda.synchronize()
+    assert comp[:8].tolist() == [0] * 8 and count[0] == 8 and float(score[0]) == 1.0       # the page that fits
+    assert (comp[8:] == -1).all() and not count[8:].any() and not box[8:].any() and not score[1:].any()
+
+
+def test_page_regions_and_extract_regions_carry_the_reference_scores():
+    """6 synthetic pages, random logits, kinds from the arg-max through DEFAULT_CLASS_GROUP: graph.page_regions(..., logits=...)
+    and model_predict.extract_regions(..., logits=...) give the regions of the unscored calls plus the reference's scores."""
+    data = PrebuiltPages.synthetic(6, in_feats=13)
+    src, dst, _, _, _, off = S.concat_pages(data.page_arrays)
+    n = int(off[-1])
+    bbox = np.concatenate([p.bbox for p in data.page_arrays]).astype(np.int32)
+    rng = np.random.default_rng(9)
+    logits = (2.0 * rng.standard_normal((n, 9))).astype(np.float32)
+    pred = logits.argmax(axis=1)
+    table = np.asarray(G.DEFAULT_CLASS_GROUP, dtype=np.int32)
+    group = table[pred]
+    g = G.batch([pg.to(DEV) for pg in data.graphs])
+    plain = G.page_regions(g, _t(group), _t(bbox))
+    reg = G.page_regions(g, _t(group), _t(bbox), logits=_t(logits, np.float32))
+    assert plain.score is None and reg.score.dtype == torch.float32
+    for a, b in zip(plain[:6], reg[:6]):
+        assert torch.equal(a, b)
+    want = bref.region_scores_ref(reg.comp.cpu().numpy(), group, logits, table)
+    roots = reg.root.cpu().numpy()
+    assert len(roots) > 6 and np.abs(reg.score.cpu().numpy().astype(np.float64) - want[roots]).max() <= BOUND
+    all_pred = [pred[off[i]:off[i + 1]] for i in range(6)]
+    plain_list = model_predict.extract_regions(data, all_pred, batch_pages=4)
+    scored = model_predict.extract_regions(data, all_pred, batch_pages=4, logits=logits)
+    assert [[t[:3] for t in page] for page in scored] == plain_list and all(len(t) == 3 for page in plain_list for t in page)
+    flat = [t[3] for page in scored for t in page]
+    assert len(flat) == len(roots)                         # ascending root order, page after page: the order of `roots`
+    assert np.abs(np.asarray(flat) - want[roots]).max() <= BOUND
