@@ -724,6 +724,12 @@ def bbox_features(bbox: torch.Tensor, char_counts: torch.Tensor) -> torch.Tensor
 # table cell) -> 4, the TABLE category that "has no nodes" upstream.
 DEFAULT_CLASS_GROUP = (-1, 1, 2, 3, 5, 6, 4, 4, 4)
 GROUP_NAMES = {1: "text", 2: "title", 3: "list", 4: "table", 5: "figure", 6: "caption"}      # lower-case category names
+# original category value of each of the 9 converted classes, the table classes NOT merged (column header 7, spanning cell 8,
+# table cell 10): the reference's LableModification.revert for to_remove = [4, 9, 11, 12] -- what the block route votes with
+DEFAULT_CLASS_CATEGORY = (0, 1, 2, 3, 5, 6, 7, 8, 10)
+# the thirteen lower-case category names, in category order: the keys of the block document (write_json)
+CATEGORY_NAMES = ("other", "text", "title", "list", "table", "figure", "caption", "table-colh", "table-sp", "table-gcell",
+                  "table-tcell", "table-col", "table-row")
 
 
 class PageRegions(NamedTuple):
@@ -826,6 +832,56 @@ def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, io
         raise ValueError(f"box_match: cell {b} ({int(po[b + 1] - po[b])} predicted x {int(go[b + 1] - go[b])} ground-truth boxes) has more "
                          f"than {lib.gte_box_match_max_candidates()} pairs above IoU {thr[0]} (status {int(status[b])})")
     return tp
+
+
+class BlockVote(NamedTuple):
+    """Result of :func:`block_vote`."""
+    word_block: torch.Tensor  # int32 [n]        global index of the word's block, -1 for a word outside every block
+    votes: torch.Tensor       # int32 [B, n_cat] the blocks' counters
+    label: torch.Tensor       # int32 [B]        the lowest category with the largest count (0 for a block without votes)
+
+
+def block_vote(bbox: torch.Tensor, node_off, word_cat: torch.Tensor, block_box: torch.Tensor, block_off, n_cat: int = 13,
+               double_cat: int = 2) -> BlockVote:
+    """Layout blocks labelled by the vote of their words (gte_block_vote, one launch; the words x blocks loop of the reference's
+    ``get_objects_bboxs``, postprocessing_2.py:240-258).
+
+    ``bbox`` int32 [n, 4] word boxes and ``word_cat`` int32 [n] their categories (the reference's ORIGINAL category values:
+    :data:`DEFAULT_CLASS_CATEGORY` of the predicted class), pages concatenated; ``block_box`` float64 [B, 4] the pages' layout
+    blocks ALREADY divided by the scale factor on the host; ``node_off`` / ``block_off`` host sequences [pages + 1].  A word goes
+    to the first block of its page that its rectangle meets (closed test, corners normalised) and adds 2 to the block's counter
+    of its category if that is ``double_cat`` (TITLE; -1: none), else 1; a category outside ``[0, n_cat)`` casts no vote.
+    Raises ``ValueError`` on shapes, dtypes or offsets that do not fit, ``GteError`` when a page has more than
+    ``gte_block_vote_max_page_blocks()`` blocks.  No synchronisation."""
+    _lib.require_device(bbox, "block_vote")
+    _lib.require_device(word_cat, "block_vote")
+    _lib.require_device(block_box, "block_vote")
+    lib, P = _lib.load(), _lib.ptr
+    dev = bbox.device
+    if bbox.dtype != torch.int32 or word_cat.dtype != torch.int32 or block_box.dtype != torch.float64:
+        raise ValueError(f"block_vote: bbox {bbox.dtype} and word_cat {word_cat.dtype} must be int32, block_box {block_box.dtype} float64")
+    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 or word_cat.dim() != 1 \
+            or word_cat.shape[0] != bbox.shape[0]:
+        raise ValueError(f"block_vote: bbox is {tuple(bbox.shape)}, word_cat {tuple(word_cat.shape)}, block_box {tuple(block_box.shape)}")
+    if word_cat.device != dev or block_box.device != dev:
+        raise ValueError("block_vote: bbox, word_cat and block_box live on different devices")
+    n, nb = bbox.shape[0], block_box.shape[0]
+    no, bo = np.asarray(node_off, dtype=np.int64).reshape(-1), np.asarray(block_off, dtype=np.int64).reshape(-1)
+    if no.size < 1 or no.size != bo.size or no[0] != 0 or bo[0] != 0 or (np.diff(no) < 0).any() or (np.diff(bo) < 0).any() \
+            or no[-1] != n or bo[-1] != nb:
+        raise ValueError(f"block_vote: offsets of {no.size - 1} / {bo.size - 1} pages do not partition {n} words and {nb} blocks")
+    if not 1 <= int(n_cat) <= lib.gte_block_vote_max_categories():
+        raise ValueError(f"block_vote: n_cat = {n_cat} outside 1 .. {lib.gte_block_vote_max_categories()}")
+    pages = no.size - 1
+    bbox, word_cat, block_box = bbox.contiguous(), word_cat.contiguous(), block_box.contiguous()
+    word_block = torch.empty(n, dtype=torch.int32, device=dev)
+    votes = torch.empty((nb, int(n_cat)), dtype=torch.int32, device=dev)
+    label = torch.empty(nb, dtype=torch.int32, device=dev)
+    d_no, d_bo = torch.from_numpy(no.astype(np.int32)).to(dev), torch.from_numpy(bo.astype(np.int32)).to(dev)
+    _lib.check(lib.gte_block_vote(P(bbox), P(d_no), P(word_cat), P(block_box), P(d_bo), pages, n, nb,
+                                  int(np.diff(bo).max()) if pages else 0, int(n_cat), int(double_cat), P(word_block), P(votes),
+                                  P(label), _lib.current_stream()), "gte_block_vote")
+    return BlockVote(word_block, votes, label)
 
 
 def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, max_dist: int = 500, bidirectional: bool = True,

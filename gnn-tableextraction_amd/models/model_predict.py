@@ -171,7 +171,7 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
 def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=64, device=None, logits=None):
     """Regions of every page from the node predictions: connected components of the page graph among words of one predicted
     kind, each with the union of its words' boxes (``graph.page_regions`` -> gte_page_regions; the reference's
-    ``get_subgraph_bbox`` is a stub, its PyMuPDF block voting is out of scope -- DESIGN 10).
+    ``get_subgraph_bbox`` is a stub; its own route, layout blocks labelled by word vote, is ``extract_blocks``).
 
     ``all_pred``: per-page class ids in ``data.graphs`` order (``test()``'s ``'all_pred'``);
     ``class_group[c]`` = region kind of class c, < 0 for none (default ``graph.DEFAULT_CLASS_GROUP``: the reference's category
@@ -333,8 +333,255 @@ def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, devi
     return out
 
 
-def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False):
-    """``regions=True``: the result gains ``'regions'`` (``extract_regions`` of the predictions: per page a list of
+# ---- the reference's own route from word predictions to page objects: layout blocks labelled by word vote, tables assembled ----
+# category values of src/utils/const.py Categories_names that the assembly names
+_TABLE, _FIGURE, _COLH, _SP, _TCELL = 4, 5, 7, 8, 10
+
+
+def _y_mid(b):
+    return (b[3] + b[1]) / 2
+
+
+def _x_mid(b):
+    return (b[2] + b[0]) / 2
+
+
+def _x_meets(interval, b):
+    return interval[0] <= b[2] and interval[1] >= b[0]
+
+
+def _hull(group):
+    return [min([b[0] for b in group]), min([b[1] for b in group]), max([b[2] for b in group]), max([b[3] for b in group])]
+
+
+def _overlaps_strictly(a, b):
+    """``intersect`` of the reference's graphs/utils.py:27-34: normalised corners, both axes strictly."""
+    left, top = max(min(a[0], a[2]), min(b[0], b[2])), max(min(a[1], a[3]), min(b[1], b[3]))
+    right, bottom = min(max(a[0], a[2]), max(b[0], b[2])), min(max(a[1], a[3]), max(b[1], b[3]))
+    return bool(left < right and top < bottom)
+
+
+def assemble_tables(blocks, labels):
+    """Tables from labelled layout blocks: ``get_tables_bbox`` of the reference (postprocessing_2.py:21-195) restated -- its
+    behaviour exactly, including what looks accidental there, and the same operations on Python floats, so the result is bit
+    for bit the reference's (tests/golden/blocks_cases.json decides).  Plain Python on lists: a page has tens of blocks and
+    every rule depends on order.
+
+    ``blocks``: ``[x0, y0, x1, y1]`` per block, ``labels``: their category values.  Neither list is changed.  Returns ``(blocks,
+    labels, headers)``: the page's blocks after the assembly (untouched blocks are the caller's own objects), their categories,
+    and the merged column-header / spanning-cell boxes.
+
+    1. Per class -- column header, spanning cell, table cell, in this order -- the class's blocks form COLUMN GROUPS: a block joins
+       the first group whose x-interval it meets (closed), else opens a group.  A group's interval is the x-range of its FIRST
+       block and never widens (group 0 takes the class's first block's).  Inside a group the blocks stand by y-centre, a newcomer
+       before the first centre ``>=`` its own.
+    2. A group is split where other blocks stand between two of its members: over ALL blocks now in the list (the merged ones
+       appended for an earlier class included) that meet the group's interval, count those whose y-centre lies strictly between
+       two consecutive member centres; the SECOND such block splits the group behind the lower of the two members.  The count never
+       resets: a group is split at most once.
+    3. Every part becomes one block, the hull of its members, appended with the class's label; header and spanning hulls are also
+       the ``headers``.  Only the table-cell groups hand their intervals on.  Then the classes' original blocks leave the list.
+    4. Per handed-on interval: the blocks whose x-centre lies strictly inside, in stable order of y-centre.  Walking the
+       consecutive pairs, a header directly followed by a cell block -- or by a spanning block and then a cell block -- gives a
+       TABLE, the hull of the header and the cell block.  The walk does not skip what it merged.  The merged blocks are deleted
+       by descending index, duplicates kept as in the reference (a block named twice would take its successor along; the
+       handed-on intervals are pairwise disjoint -- a group opens only where no interval is met -- so none is).
+    5. The remaining cell blocks become TABLE.  Every block that is no table and strictly overlaps a table (as the tables stand
+       before this step) is absorbed: the table is replaced by the hull of itself and what it overlaps.
+
+    A class whose first block has inverted x-corners leaves group 0 empty and raises ``ValueError`` (the hull of nothing), as the
+    reference does."""
+    blocks, labels = list(blocks), list(labels)
+    members = {cls: [i for i, l in enumerate(labels) if l == cls] for cls in (_COLH, _SP, _TCELL)}
+    handed_on, headers = [], []
+    for cls, ids in members.items():
+        if not ids:
+            continue
+        first = blocks[ids[0]]
+        groups = [{'x': [first[0], first[2]], 'blocks': [], 'mids': []}]
+        for i in ids:
+            b = blocks[i]
+            for g in groups:
+                if _x_meets(g['x'], b):
+                    mid = _y_mid(b)
+                    at = next((k for k, m in enumerate(g['mids']) if not m < mid), len(g['mids']))
+                    g['blocks'].insert(at, b)
+                    g['mids'].insert(at, mid)
+                    break
+            else:
+                groups.append({'x': [b[0], b[2]], 'blocks': [b], 'mids': [_y_mid(b)]})
+        cuts = []
+        for g in groups:
+            cut, between, mids = None, 0, g['mids']
+            for b in blocks:
+                if not _x_meets(g['x'], b):
+                    continue
+                mid = _y_mid(b)
+                for k in range(len(mids) - 1):
+                    if mid < mids[k]:
+                        break
+                    if mids[k] < mid < mids[k + 1]:
+                        between += 1
+                        if between == 2:
+                            cut = k + 1
+                        break
+            cuts.append(cut)
+        for g, cut in zip(groups, cuts):
+            parts = [g['blocks']] if cut is None else [part for part in (g['blocks'][:cut], g['blocks'][cut:]) if part]
+            for part in parts:
+                box = _hull(part)
+                blocks.append(box)
+                labels.append(cls)
+                if cls != _TCELL:
+                    headers.append(box)
+        if cls == _TCELL:
+            handed_on.extend(g['x'] for g in groups)
+    for i in sorted((i for ids in members.values() for i in ids), reverse=True):
+        del blocks[i], labels[i]
+
+    mids = [_y_mid(b) for b in blocks]
+    by_y = sorted(range(len(blocks)), key=lambda k: mids[k])
+    merged = []
+    for x in handed_on:
+        col = [k for k in by_y if x[0] < _x_mid(blocks[k]) < x[1]]
+        for at in range(len(col) - 1):
+            if labels[col[at]] != _COLH:
+                continue
+            head, nxt = col[at], col[at + 1]
+            if labels[nxt] == _TCELL:
+                took = [head, nxt]
+            elif at + 2 == len(col):
+                break
+            elif labels[nxt] == _SP and labels[col[at + 2]] == _TCELL:
+                took = [head, nxt, col[at + 2]]
+            else:
+                continue
+            a, b = blocks[head], blocks[took[-1]]
+            blocks.append([min(a[0], b[0]), min(a[1], b[1]), max(a[2], b[2]), max(a[3], b[3])])
+            labels.append(_TABLE)
+            merged.extend(took)
+    for i in sorted(merged, reverse=True):
+        del blocks[i], labels[i]
+
+    labels = [_TABLE if l == _TCELL else l for l in labels]
+    tables = [i for i, l in enumerate(labels) if l == _TABLE]
+    absorbed = [[b for k, b in enumerate(blocks) if labels[k] != _TABLE and _overlaps_strictly(blocks[t], b)] for t in tables]
+    gone = {k for k, b in enumerate(blocks) if labels[k] != _TABLE and any(_overlaps_strictly(blocks[t], b) for t in tables)}
+    for t, inside in zip(tables, absorbed):
+        if inside:
+            blocks.append(_hull(inside + [blocks[t]]))
+            labels.append(_TABLE)
+            gone.add(t)
+    for i in sorted(gone, reverse=True):
+        del blocks[i], labels[i]
+    return blocks, labels, headers
+
+
+def extract_blocks(data, all_pred, class_category=None, blocks=None, images=None, scale=0.36, rescale=True, batch_pages=64,
+                   device=None):
+    """Page objects by the reference's own route (``get_objects_bboxs``, postprocessing_2.py:197-309): the layout blocks that a
+    PDF text extractor delivers for every page are labelled by the vote of the words inside them (``graph.block_vote`` ->
+    gte_block_vote: ONE launch per ``batch_pages`` pages, in place of the reference's words x blocks loop in Python), the
+    column-header, spanning-cell and table-cell blocks are assembled into tables (``assemble_tables``, on the host, per page, on
+    the unscaled blocks), and the page's images become FIGURE blocks.
+
+    ``all_pred``: per-page class ids in ``data.graphs`` order (``test()``'s ``'all_pred'``); ``class_category[c]`` = the
+    reference's original category value of class c (default ``graph.DEFAULT_CLASS_CATEGORY``, its ``LableModification.revert``);
+    word boxes from ``data.pages[i]['bboxs']``.  ``blocks``: per page a sequence of ``[x0, y0, x1, y1]`` in PDF points, the text
+    blocks in the extractor's order (default ``data.pages[i]['blocks']``; a page without that key raises ``ValueError``);
+    ``images``: per page a sequence of image boxes, ``[x0, y0, x1, y1]`` or a dict with a ``'bbox'`` (default
+    ``data.pages[i].get('images', ())``): those higher than 10 are kept, every coordinate truncated with ``int()``
+    (postprocessing_2.py:264-270).  A block is compared with the word boxes after division by ``scale`` (the reference's
+    SCALE_FACTOR); ``rescale=True`` divides every output coordinate by ``scale`` (postprocessing_2.py:306), ``rescale=False``
+    gives the output of the reference's postprocessing.py.
+
+    Returns per page a dict: ``'blocks'`` / ``'labels'`` after table assembly and figures; ``'voted_labels'`` per input block;
+    ``'headers'`` (never rescaled, as in the reference); ``'word_block'`` the page-local block index of every word or -1;
+    ``'votes'`` the input blocks' counters [blocks, categories].
+
+    Out of scope: obtaining the blocks from a PDF (the caller's extractor); block confidences (the reference writes 1.0;
+    ``'votes'`` is there for callers who want a share); feeding the float-valued block document to ``evaluate_regions``, which
+    takes integer boxes."""
+    n_pages = len(data.graphs)
+    if len(all_pred) != n_pages:
+        raise ValueError(f"extract_blocks: {len(all_pred)} prediction lists for {n_pages} pages")
+    for what, seq in (("block", blocks), ("image", images)):
+        if seq is not None and len(seq) != n_pages:
+            raise ValueError(f"extract_blocks: {len(seq)} {what} lists for {n_pages} pages")
+    if not float(scale) > 0.0:
+        raise ValueError(f"extract_blocks: scale = {scale}")
+    scale = float(scale)
+    table = np.asarray(G.DEFAULT_CLASS_CATEGORY if class_category is None else class_category, dtype=np.int64).reshape(-1)
+    n_cat = max(len(G.CATEGORY_NAMES), int(table.max()) + 1 if table.size else 0)
+    page_blocks = []
+    for i in range(n_pages):
+        if blocks is not None:
+            pb = blocks[i]
+        elif 'blocks' in data.pages[i]:
+            pb = data.pages[i]['blocks']
+        else:
+            raise ValueError(f"extract_blocks: page {i} ({data.pages[i].get('page')}) carries no 'blocks'")
+        pb = np.asarray(pb, dtype=np.float64)
+        if pb.size == 0:
+            pb = pb.reshape(0, 4)
+        if pb.ndim != 2 or pb.shape[1] != 4:
+            raise ValueError(f"extract_blocks: the blocks of page {i} ({data.pages[i].get('page')}) have shape {pb.shape}")
+        page_blocks.append(pb)
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    out = []
+    bp = max(1, int(batch_pages))
+    for b0 in range(0, n_pages, bp):
+        ids = range(b0, min(b0 + bp, n_pages))
+        pred = [np.asarray(all_pred[i], dtype=np.int64).reshape(-1) for i in ids]
+        boxes = [np.asarray(data.pages[i]['bboxs'], dtype=np.int32).reshape(-1, 4) for i in ids]
+        for i, p, b in zip(ids, pred, boxes):
+            if p.shape[0] != b.shape[0]:
+                raise ValueError(f"extract_blocks: page {i} has {p.shape[0]} predictions and {b.shape[0]} boxes")
+            if p.size and (p.min() < 0 or p.max() >= table.size):
+                raise ValueError(f"extract_blocks: page {i} holds a class outside the {table.size} of class_category")
+        node_off = np.concatenate([[0], np.cumsum([b.shape[0] for b in boxes])]).astype(np.int64)
+        block_off = np.concatenate([[0], np.cumsum([page_blocks[i].shape[0] for i in ids])]).astype(np.int64)
+        cat = table[np.concatenate(pred)].astype(np.int32)
+        scaled = np.concatenate([page_blocks[i] for i in ids]) / scale                     # float64: bit for bit b / sf
+        vote = G.block_vote(torch.from_numpy(np.concatenate(boxes)).to(device), node_off, torch.from_numpy(cat).to(device),
+                            torch.from_numpy(scaled).to(device), block_off, n_cat=n_cat, double_cat=2)
+        word_block, votes, label = vote.word_block.cpu().numpy(), vote.votes.cpu().numpy(), vote.label.cpu().numpy()
+        for k, i in enumerate(ids):
+            n0, n1, k0, k1 = int(node_off[k]), int(node_off[k + 1]), int(block_off[k]), int(block_off[k + 1])
+            voted = [int(v) for v in label[k0:k1]]
+            new_blocks, new_labels, headers = assemble_tables(page_blocks[i].tolist(), voted)
+            for img in (images[i] if images is not None else data.pages[i].get('images', ())):
+                box = img['bbox'] if isinstance(img, dict) else img
+                if box[3] - box[1] > 10:
+                    new_blocks.append([int(v) for v in box])
+                    new_labels.append(_FIGURE)
+            if rescale:
+                new_blocks = [[v / scale for v in b] for b in new_blocks]
+            wb = word_block[n0:n1].astype(np.int64)
+            out.append({'blocks': new_blocks, 'labels': new_labels, 'voted_labels': voted, 'headers': headers,
+                        'word_block': np.where(wb >= 0, wb - k0, -1).tolist(), 'votes': votes[k0:k1].tolist()})
+    return out
+
+
+def blocks_json(data, result):
+    """``{kind_name: {page_name: {'bboxes': [...], 'scores': [1.0, ...]}}}`` of ``extract_blocks``' result: the layout of the
+    reference's ``write_json`` (postprocessing_2.py:328-348, its ``ours_bboxs.json``) -- all thirteen lower-case category names
+    as keys, a page only under the kinds it has, coordinates as floats, every score 1.0."""
+    doc = {name: {} for name in G.CATEGORY_NAMES}
+    for i, page in enumerate(result):
+        name = str(data.pages[i]['page'])
+        for box, label in zip(page['blocks'], page['labels']):
+            entry = doc[G.CATEGORY_NAMES[label]].setdefault(name, {'bboxes': [], 'scores': []})
+            entry['bboxes'].append([float(v) for v in box])
+            entry['scores'].append(1.0)
+    return doc
+
+
+def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False, blocks=False):
+    """``blocks=True``: the result gains ``'blocks'`` = ``extract_blocks(data, all_pred)`` (the pages carry their layout blocks
+    as ``data.pages[i]['blocks']``), and with ``save_predictions`` ``{output}/blocks/{logs}.json`` is written (``blocks_json``).
+
+    ``regions=True``: the result gains ``'regions'`` (``extract_regions`` of the predictions: per page a list of
     ``(group, [x0, y0, x1, y1], n_words)``), and with ``save_predictions`` ``{output}/regions/{logs}.json`` is written
     (``regions_json``) with every score 1.0.
 
@@ -443,4 +690,12 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
             labels = [g.ndata['label'].long().cpu().numpy() for g in data.graphs]
             gt = regions_gt_json(data, extract_regions(data, labels, batch_pages=bs, device=device))
             result['box_eval'] = evaluate_regions(doc, gt, device=device)
+    if blocks:
+        result['blocks'] = extract_blocks(data, all_pred, batch_pages=bs, device=device)
+        if save_predictions:
+            import json
+            blk_dir = os.path.join(out_root, 'blocks')
+            os.makedirs(blk_dir, exist_ok=True)
+            with open(os.path.join(blk_dir, f'{logs}.json'), 'w') as f:
+                json.dump(blocks_json(data, result['blocks']), f)
     return result

@@ -224,6 +224,28 @@ int gte_box_match(const int32_t* pred_box, const int32_t* pred_off, const int32_
                   int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr, int32_t* tp,
                   int32_t* cell_status, void* stream);
 
+/* ---- layout blocks labelled by the vote of their words (postprocessing_2.py:240-258, the words x blocks loop of get_objects_bboxs) -
+ * Inputs: bbox int32 [n_nodes, 4] the word boxes; word_cat int32 [n_nodes] the category of every word (a value < 0 or >= n_cat:
+ * the word is still assigned to a block but casts no vote); block_box double [n_blocks, 4] the layout blocks ALREADY DIVIDED by
+ * the scale factor on the host (numpy float64 `blocks / 0.36`: bit for bit the reference's b / sf); node_off[n_pages + 1] and
+ * block_off[n_pages + 1] the pages' runs (first entry 0, last entry n_nodes / n_blocks; empty pages and pages without blocks are
+ * legal).  Both rectangles are normalised per axis (lo = min, hi = max of the two corners); a word MEETS a block when
+ * max(lo, lo') <= min(hi, hi') on both axes -- closed, touching counts -- evaluated in fp64 (int32 -> double is exact); a block
+ * with a NaN coordinate meets nothing.
+ *   word_block[v]    the global index of the FIRST block (lowest index) of v's page that v meets; -1 where there is none.
+ *   votes[b * n_cat + c]   the sum over the words v with word_block[v] == b and word_cat[v] == c of 2 if c == double_cat (the
+ *                    reference: TITLE), else 1; double_cat = -1: no category counts double.
+ *   block_label[b]   the LOWEST category with the largest count; 0 for a block without votes (l.index(max(l))).
+ * Every row of the three outputs is written.  One launch for the batch, one workgroup per page, the page's blocks and counters in
+ * LDS; max_page_blocks = the largest page's block count (it sizes the launch's LDS; a page above it gets -1 / 0 / 0): above
+ * gte_block_vote_max_page_blocks() or with n_cat > gte_block_vote_max_categories() the call returns GTE_ERR_UNSUPPORTED before any
+ * launch.  Integer work on LDS atomic add: deterministic.  No allocation, no workspace, no synchronisation.  bbox 16-byte aligned. */
+int gte_block_vote_max_page_blocks(void);   /* 512 */
+int gte_block_vote_max_categories(void);    /* 16 */
+int gte_block_vote(const int32_t* bbox, const int32_t* node_off, const int32_t* word_cat, const double* block_box,
+                   const int32_t* block_off, int64_t n_pages, int64_t n_nodes, int64_t n_blocks, int64_t max_page_blocks, int n_cat,
+                   int double_cat, int32_t* word_block, int32_t* votes, int32_t* block_label, void* stream);
+
 /* The whole batch in ONE launch (what the train loop calls every step; gte_batch_csr / gte_batch_rows are its pieces):
  * a page's rows are CONTIGUOUS in the resident arrays and in the batch, so every array of the batch is the concatenation
  * of per-page runs -- features and labels copied, indptr / indices copied with a per-page constant added.  Workgroup

@@ -1,0 +1,207 @@
+"""The block vote on the device (gte_block_vote) against tests/blocks_ref.py and the reference's own answers
+(tests/golden/blocks_cases.json): direct ABI calls on sentinel-prefilled outputs.  Every output is an integer: all comparisons are
+exact."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_tableextraction_amd import _lib
+from tests import blocks_ref as ref
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+SENTINEL = 0x5A5A5A5A
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "blocks_cases.json")
+SF = 0.36
+TEXT, TITLE, LIST = 1, 2, 3
+INVALID_ARGUMENT, UNSUPPORTED = -1, -4                                  # GTE_ERR_* of include/gte.h
+
+
+def _pack(pages):
+    """pages = [(word boxes [n, 4], categories [n], scaled blocks [b, 4])] -> the ABI's five input arrays (numpy)."""
+    bbox = np.concatenate([np.asarray(w, dtype=np.int32).reshape(-1, 4) for w, _, _ in pages])
+    cats = np.concatenate([np.asarray(c, dtype=np.int32).reshape(-1) for _, c, _ in pages])
+    blocks = np.concatenate([np.asarray(b, dtype=np.float64).reshape(-1, 4) for _, _, b in pages])
+    node_off = np.concatenate([[0], np.cumsum([len(w) for w, _, _ in pages])]).astype(np.int32)
+    block_off = np.concatenate([[0], np.cumsum([len(b) for _, _, b in pages])]).astype(np.int32)
+    return bbox, node_off, cats, blocks, block_off
+
+
+def _abi(pages, n_cat=13, double_cat=TITLE, max_page_blocks=None):
+    """One direct call of gte_block_vote on sentinel-prefilled outputs -> (code, word_block, votes, label)."""
+    lib, P = _lib.load(), _lib.ptr
+    bbox, node_off, cats, blocks, block_off = _pack(pages)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    d_bbox, d_no, d_cat, d_blk, d_bo = t(bbox), t(node_off), t(cats), t(blocks), t(block_off)
+    word_block = torch.full((len(bbox),), SENTINEL, dtype=torch.int32, device=DEV)
+    votes = torch.full((len(blocks), n_cat), SENTINEL, dtype=torch.int32, device=DEV)
+    label = torch.full((len(blocks),), SENTINEL, dtype=torch.int32, device=DEV)
+    largest = int(np.diff(block_off).max()) if max_page_blocks is None else max_page_blocks
+    code = lib.gte_block_vote(P(d_bbox), P(d_no), P(d_cat), P(d_blk), P(d_bo), len(pages), len(bbox), len(blocks), largest, n_cat,
+                              double_cat, P(word_block), P(votes), P(label), _lib.current_stream())
+    torch.cuda.synchronize()
+    return code, word_block.cpu().numpy(), votes.cpu().numpy(), label.cpu().numpy()
+
+
+def _assert_equal_ref(pages, n_cat=13, double_cat=TITLE):
+    code, word_block, votes, label = _abi(pages, n_cat, double_cat)
+    assert code == 0
+    want = ref.vote_batch(*_pack(pages), n_cat, double_cat)
+    np.testing.assert_array_equal(word_block, want[0])
+    np.testing.assert_array_equal(votes, want[1])
+    np.testing.assert_array_equal(label, want[2])
+    return want
+
+
+def _words(rng, n, width=1600, height=2200):
+    x0, y0 = rng.integers(0, width, n), rng.integers(0, height, n)
+    return np.stack([x0, y0, x0 + rng.integers(0, 120, n), y0 + rng.integers(0, 30, n)], axis=1).astype(np.int32)
+
+
+def test_every_golden_vote_case_alone_and_all_in_one_batch():
+    with open(GOLDEN) as f:
+        g = json.load(f)
+    assert len(g["votes"]) >= 40
+    pages = [(c["bboxs"], c["cats"], np.asarray(c["blocks"], dtype=np.float64).reshape(-1, 4) / g["scale"]) for c in g["votes"]]
+    code, word_block, votes, label = _abi(pages, g["n_cat"], g["double_cat"])
+    assert code == 0
+    _, node_off, _, _, block_off = _pack(pages)
+    for k, c in enumerate(g["votes"]):
+        want = [block_off[k] + j if j >= 0 else -1 for j in c["ref"]["word_block"]]
+        assert word_block[node_off[k]:node_off[k + 1]].tolist() == want, c["name"]
+        assert votes[block_off[k]:block_off[k + 1]].tolist() == c["ref"]["counters"], c["name"]
+        assert label[block_off[k]:block_off[k + 1]].tolist() == c["ref"]["labels"], c["name"]
+    for k in (0, 2, 4, 7, 8, 11):                                       # single-page launches, the pages without words / blocks among them
+        c = g["votes"][k]
+        code, wb, v, l = _abi([pages[k]], g["n_cat"], g["double_cat"])
+        assert code == 0 and wb.tolist() == c["ref"]["word_block"], c["name"]
+        assert v.tolist() == c["ref"]["counters"] and l.tolist() == c["ref"]["labels"], c["name"]
+
+
+def test_pages_without_words_or_without_blocks():
+    block = [[0.0, 0.0, 100.0, 100.0]]
+    want = _assert_equal_ref([([], [], block)])
+    assert want[1].tolist() == [[0] * 13] and want[2].tolist() == [0]
+    want = _assert_equal_ref([([[1, 2, 3, 4], [5, 6, 7, 8]], [TEXT, TITLE], [])])
+    assert want[0].tolist() == [-1, -1]
+    want = _assert_equal_ref([([], [], []), ([[1, 2, 3, 4]], [TEXT], block), ([], [], [])])
+    assert want[0].tolist() == [0]
+
+
+def test_touching_overlapping_inverted_and_nan_blocks():
+    # one block, one word touching it at a single corner point -- from either side
+    assert _assert_equal_ref([([[200, 200, 300, 300]], [TEXT], [[300.0, 300.0, 400.0, 400.0]])])[0].tolist() == [0]
+    assert _assert_equal_ref([([[400, 400, 500, 500]], [TEXT], [[300.0, 300.0, 400.0, 400.0]])])[0].tolist() == [0]
+    assert _assert_equal_ref([([[200, 200, 299, 300]], [TEXT], [[300.0, 300.0, 400.0, 400.0]])])[0].tolist() == [-1]
+    # a word inside two blocks goes to the lower index, whatever the blocks' sizes
+    two = [[0.0, 0.0, 1000.0, 1000.0], [90.0, 90.0, 130.0, 130.0], [95.0, 95.0, 120.0, 120.0]]
+    assert _assert_equal_ref([([[100, 100, 110, 110]], [TEXT], two)])[0].tolist() == [0]
+    assert _assert_equal_ref([([[100, 100, 110, 110]], [TEXT], two[::-1])])[0].tolist() == [0]
+    assert _assert_equal_ref([([[100, 100, 110, 110]], [TEXT], [[500.0, 500.0, 600.0, 600.0]] + two[1:])])[0].tolist() == [1]
+    # a block whose scaled edge equals a word's edge after / 0.36 -- or misses it by the division's rounding: the float64 decides
+    for points in (36.0, 36.36, 100.08, 7.2, 61.2, 250.92):
+        edge = np.float64(points) / SF
+        near = int(round(float(edge)))
+        blocks = np.asarray([[points, 0.0, points + 50.0, 72.0]], dtype=np.float64) / SF
+        words = [[near - 40, 10, near - 1, 20], [near - 40, 30, near, 40], [near - 40, 50, near + 1, 60]]
+        want = _assert_equal_ref([(words, [TEXT] * 3, blocks)])
+        assert want[0].tolist() == [-1, 0 if near >= edge else -1, 0]
+    # inverted block corners and inverted word corners
+    inverted = [[400.0, 300.0, 100.0, 50.0]]
+    want = _assert_equal_ref([([[150, 100, 160, 110], [410, 100, 420, 110], [160, 110, 150, 100]], [LIST] * 3, inverted)])
+    assert want[0].tolist() == [0, -1, 0] and want[2].tolist() == [LIST]
+    # a NaN block meets nothing; the words go on to the next block
+    nan = float("nan")
+    blocks = [[nan, 0.0, 500.0, 500.0], [0.0, 0.0, 500.0, nan], [0.0, nan, nan, 500.0], [0.0, 0.0, 500.0, 500.0]]
+    want = _assert_equal_ref([([[10, 10, 20, 20], [490, 490, 600, 600], [501, 10, 510, 20]], [TEXT] * 3, blocks)])
+    assert want[0].tolist() == [3, 3, -1] and want[2].tolist() == [0, 0, 0, TEXT]
+
+
+def test_the_title_rule_ties_and_words_that_cast_no_vote():
+    block = [[0.0, 0.0, 1000.0, 1000.0]]
+    w = [[10 * i, 10, 10 * i + 5, 20] for i in range(4)]
+    assert _assert_equal_ref([(w[:3], [TITLE, TEXT, TEXT], block)])[2].tolist() == [TEXT]            # 2 : 2, the lower category
+    assert _assert_equal_ref([(w[:2], [TITLE, TEXT], block)])[2].tolist() == [TITLE]                 # 2 : 1
+    assert _assert_equal_ref([(w[:3], [TITLE, LIST, LIST], block)])[2].tolist() == [TITLE]           # 2 : 2, the lower category
+    assert _assert_equal_ref([(w[:2], [TITLE, LIST], block)], double_cat=-1)[2].tolist() == [TITLE]  # 1 : 1
+    assert _assert_equal_ref([(w[:3], [TITLE, LIST, LIST], block)], double_cat=-1)[2].tolist() == [LIST]
+    assert _assert_equal_ref([(w[:3], [TITLE, LIST, LIST], block)], double_cat=LIST)[1][0].tolist() == [0, 0, 1, 4] + [0] * 9
+    # category -1 and categories >= n_cat: assigned, no vote
+    want = _assert_equal_ref([(w, [-1, 13, 2 ** 31 - 1, 12], block)])
+    assert want[0].tolist() == [0, 0, 0, 0] and want[1][0].tolist() == [0] * 12 + [1] and want[2].tolist() == [12]
+    want = _assert_equal_ref([(w[:2], [-1, -5], block)])
+    assert want[0].tolist() == [0, 0] and not want[1].any() and want[2].tolist() == [0]
+    # other category counts: 1 (every word that votes, votes for 0) and the largest, 16
+    assert _assert_equal_ref([(w, [0, 1, 0, -1], block)], n_cat=1)[1].tolist() == [[2]]
+    want = _assert_equal_ref([(w, [15, 15, 3, 16], block)], n_cat=16)
+    assert want[1][0].tolist() == [0, 0, 0, 1] + [0] * 11 + [2] and want[2].tolist() == [15]
+
+
+def test_a_page_of_3000_words_on_7_blocks():
+    """more words than threads: every thread takes several words, the counters are far above 1"""
+    rng = np.random.default_rng(11)
+    words = _words(rng, 3000)
+    bx, by = rng.integers(0, 1200, 7), rng.integers(0, 1700, 7)
+    blocks = np.stack([bx, by, bx + rng.integers(200, 700, 7), by + rng.integers(200, 900, 7)], axis=1).astype(np.float64)
+    want = _assert_equal_ref([(words, rng.integers(-1, 14, 3000), blocks)])
+    assert (want[0] >= 0).sum() > 1000 and (want[0] < 0).sum() > 100 and want[1].max() > 40 and len(set(want[0].tolist())) >= 6
+
+
+def test_a_page_with_exactly_the_largest_block_count_and_one_block_too_many():
+    lib = _lib.load()
+    limit = lib.gte_block_vote_max_page_blocks()
+    assert limit >= 512 and lib.gte_block_vote_max_categories() == 16
+    rng = np.random.default_rng(12)
+    ix, iy = np.meshgrid(np.arange(32), np.arange((limit + 31) // 32))
+    x0, y0 = ix.reshape(-1)[:limit] * 50.0, iy.reshape(-1)[:limit] * 100.0
+    blocks = np.stack([x0, y0, x0 + 44.0, y0 + 90.0], axis=1)[rng.permutation(limit)]
+    words = _words(rng, 2000, 1600, int(y0.max()) + 100)
+    last = blocks[-1].astype(np.int32)
+    words[-1] = [last[0] + 10, last[1] + 10, last[0] + 12, last[1] + 12]                 # the last block takes at least this word
+    cats = rng.integers(0, 16, 2000)
+    small = (_words(rng, 50), rng.integers(0, 16, 50), blocks[:3])
+    want = _assert_equal_ref([small, (words, cats, blocks), small], n_cat=16)
+    assert len(set(want[0][50:2050].tolist())) > limit // 2 and want[0][50:2050].max() == 3 + limit - 1
+    # one block too many: refused before any launch, the outputs keep their sentinels
+    more = np.concatenate([blocks, [[0.0, 0.0, 1.0, 1.0]]])
+    code, word_block, votes, label = _abi([small, (words, cats, more)], n_cat=16)
+    assert code == UNSUPPORTED
+    assert (word_block == SENTINEL).all() and (votes == SENTINEL).all() and (label == SENTINEL).all()
+    code, word_block, votes, label = _abi([small], n_cat=17)
+    assert code == UNSUPPORTED and (word_block == SENTINEL).all() and (votes == SENTINEL).all() and (label == SENTINEL).all()
+    # the existing bad-argument code for negative sizes
+    code, word_block, _, _ = _abi([small], max_page_blocks=-1)
+    assert code == INVALID_ARGUMENT and (word_block == SENTINEL).all()
+    # a page above the maximum the caller named takes no vote; its neighbours are not affected
+    code, word_block, votes, label = _abi([small, (words[:40], cats[:40], blocks[:9]), small], n_cat=16, max_page_blocks=8)
+    assert code == 0
+    alone = ref.vote_batch(*_pack([small]), 16, TITLE)
+    np.testing.assert_array_equal(word_block[:50], alone[0])
+    np.testing.assert_array_equal(votes[:3], alone[1])
+    assert (word_block[50:90] == -1).all() and not votes[3:12].any() and not label[3:12].any()
+    np.testing.assert_array_equal(word_block[90:], np.where(alone[0] >= 0, alone[0] + 12, -1))
+    np.testing.assert_array_equal(label[12:], alone[2])
+
+
+def test_a_batch_of_20_uneven_pages_with_empty_ones_page_by_page():
+    rng = np.random.default_rng(13)
+    pages = []
+    for k in range(20):
+        n = [0, 1, 7, 255, 256, 257, 600, 0, 33, 1200][k % 10] if k != 19 else 0
+        words = _words(rng, n)
+        blocks = ref.synthetic_blocks(words, rng) if k % 7 != 3 else []
+        pages.append((words, rng.integers(0, 13, n), np.asarray(blocks, dtype=np.float64).reshape(-1, 4) / SF))
+    assert any(len(w) and not len(b) for w, _, b in pages) and max(len(b) for _, _, b in pages) > 50
+    code, word_block, votes, label = _abi(pages)
+    assert code == 0
+    _, node_off, _, _, block_off = _pack(pages)
+    for k, (w, c, b) in enumerate(pages):
+        wb, v, l = ref.vote_page(w, c, b)
+        assert word_block[node_off[k]:node_off[k + 1]].tolist() == [block_off[k] + j if j >= 0 else -1 for j in wb], k
+        assert votes[block_off[k]:block_off[k + 1]].tolist() == v, k
+        assert label[block_off[k]:block_off[k + 1]].tolist() == l, k
+    assert (word_block >= 0).sum() > 0.8 * len(word_block) and (word_block < 0).sum() > 10
