@@ -78,6 +78,10 @@ class _GatAggregate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, a_l, a_r, bias, mean_bias, graph, heads, bf16_gather, elu, mean_heads, emit_bf16):
+        if elu and mean_heads:
+            # the backward forms ELU' from the saved ACTIVATED output [n, heads * dim]; with the mean over the heads only the
+            # [n, dim] mean exists.  GAT never asks for the pair (ELU on hidden layers, the mean on the last one).
+            raise ValueError("GAT aggregation: ELU in the epilogue cannot be combined with the mean over the heads")
         lib, P, st = _lib.load(), _lib.ptr, _lib.current_stream()
         z = ops._row_major(z)
         n, hd = z.shape

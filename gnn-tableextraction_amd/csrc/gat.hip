@@ -329,7 +329,8 @@ gat_fold_kernel(const float* __restrict__ partial, int nblk, int HD, float* __re
 
 #include "gat_rows.h"
 
-// GTE_GAT_ROWS=0 keeps the lane-per-feature kernels (A/B measurements)
+// GTE_GAT_ROWS=0 keeps the lane-per-feature kernels (A/B measurements) -- in the measurement build (-DGTE_MEASURE) only: the
+// shipped library has no such switch and always takes the row layout where gat_rows_vec allows it
 bool gat_rows_enabled() {                   // read per call: tests switch it inside one process
     return !GTE_MEASURE_OFF("GTE_GAT_ROWS");
 }
