@@ -342,3 +342,20 @@ def require_device(t, what: str) -> None:
     if not t.is_cuda:
         raise GteError(f"{what}: tensor is on {t.device}; the HIP path needs device tensors "
                        f"(there is no CPU fallback -- the CPU oracle lives under oracle/ for tests only)")
+
+
+def default_device(device=None):
+    """``device`` as a ``torch.device``; None: the current HIP device."""
+    import torch
+    return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def partition_offsets(off, n: int, what: str, device):
+    """A host offset sequence that must partition ``n`` rows (it starts at 0, never decreases and ends at ``n``; ``ValueError``
+    naming ``what`` otherwise) -> (the int64 host array, its int32 copy on ``device``: what the kernels read)."""
+    import numpy as np
+    import torch
+    off = np.asarray(off, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != n:
+        raise ValueError(f"{what} of {off.size - 1} parts do not partition {n} rows")
+    return off, torch.from_numpy(off.astype(np.int32)).to(device)

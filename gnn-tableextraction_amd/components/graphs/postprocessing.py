@@ -1,0 +1,514 @@
+"""From node predictions to page objects: the reference's ``components/graphs/postprocessing*.py``.
+
+Two routes, each an entry point that is three public stages in a row -- host packing, ONE launch per ``batch_pages`` pages, host
+unpacking -- so that the host stages run (and are tested) without a device, with a CPU oracle in place of the launch:
+  ``extract_regions`` = ``region_batches`` -> ``page_regions`` (gte_page_regions[_scored]) -> ``region_tuples``
+  ``extract_blocks``  = ``pack_blocks`` -> ``block_vote`` (gte_block_vote) -> ``blocks_to_pages`` (with ``assemble_tables``)
+``regions_json`` / ``regions_gt_json`` / ``blocks_json`` lay the results out as the documents the reference's box-level evaluation
+reads (``utils.metrics.evaluate_regions``).
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from ... import _lib
+from ... import graph as G
+
+# group id of each of the 9 converted classes = the reference's ORIGINAL category value (src/utils/const.py Categories_names):
+# other -> no region, text 1, title 2, list 3, figure 5, caption 6, and the three table classes (column header, spanning cell,
+# table cell) -> 4, the TABLE category that "has no nodes" upstream.
+DEFAULT_CLASS_GROUP = (-1, 1, 2, 3, 5, 6, 4, 4, 4)
+GROUP_NAMES = {1: "text", 2: "title", 3: "list", 4: "table", 5: "figure", 6: "caption"}      # lower-case category names
+# original category value of each of the 9 converted classes, the table classes NOT merged (column header 7, spanning cell 8,
+# table cell 10): the reference's LableModification.revert for to_remove = [4, 9, 11, 12] -- what the block route votes with
+DEFAULT_CLASS_CATEGORY = (0, 1, 2, 3, 5, 6, 7, 8, 10)
+# the thirteen lower-case category names, in category order: the keys of the block document (write_json)
+CATEGORY_NAMES = ("other", "text", "title", "list", "table", "figure", "caption", "table-colh", "table-sp", "table-gcell",
+                  "table-tcell", "table-col", "table-row")
+
+
+def _offsets(sizes):
+    return np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+
+def _page_words(data, all_pred, ids, what):
+    """Per page of ``ids``: (predictions int64 [n], word boxes int32 [n, 4] from ``data.pages[i]['bboxs']``), equally long."""
+    pred = [np.asarray(all_pred[i], dtype=np.int64).reshape(-1) for i in ids]
+    boxes = [np.asarray(data.pages[i]['bboxs'], dtype=np.int32).reshape(-1, 4) for i in ids]
+    for i, p, b in zip(ids, pred, boxes):
+        if p.shape[0] != b.shape[0]:
+            raise ValueError(f"{what}: page {i} has {p.shape[0]} predictions and {b.shape[0]} boxes")
+    return pred, boxes
+
+
+# ---- connected regions of one predicted kind ------------------------------------------------------------------------------
+class PageRegions(NamedTuple):
+    """Result of :func:`page_regions`: ``comp`` per node, then the regions in ascending root order."""
+    comp: torch.Tensor        # int32 [n]    smallest node id of the node's region, -1 for nodes outside every region
+    root: torch.Tensor        # int64 [R]    the region's smallest node
+    page: torch.Tensor        # int64 [R]    page of the batch
+    group: torch.Tensor       # int32 [R]    region kind
+    box: torch.Tensor         # int32 [R, 4] union of the words' boxes (x0, y0, x1, y1)
+    n_words: torch.Tensor     # int32 [R]
+    score: Optional[torch.Tensor] = None      # float32 [R]  region confidence (page_regions(..., logits=...) only)
+
+
+def page_regions(g: G.PageGraph, group: torch.Tensor, bbox: torch.Tensor, logits: Optional[torch.Tensor] = None,
+                 class_group=None) -> PageRegions:
+    """Regions of a batched page graph (a :class:`PageGraph` from ``graph.batch`` / ``graph.knn_graph_from_boxes``, or a
+    :class:`ResidentBatch`): the connected components of ``g`` restricted to nodes of one ``group`` (int [n]; < 0: in no region),
+    each with the union of its words' boxes (``bbox`` int [n, 4]) -- one launch of gte_page_regions over ``g.in_csr()`` and the
+    batch's page offsets, then a torch compaction of the root rows (``nonzero`` on the counts: plumbing, one synchronisation).
+
+    With ``logits`` (float [n, C], the model's output for the batch) the same launch (gte_page_regions_scored) also gives every
+    region a confidence, ``score``: the mean over its words of the softmax mass on the classes of the region's kind,
+    ``class_group[c]`` = kind of class c (default :data:`DEFAULT_CLASS_GROUP`; the table ``group`` was derived from)."""
+    _lib.require_device(group, "page_regions")
+    _lib.require_device(bbox, "page_regions")
+    lib, P = _lib.load(), _lib.ptr
+    dev = group.device
+    n = g.num_nodes()
+    group = group.to(torch.int32).contiguous()
+    bbox = bbox.to(torch.int32).contiguous()
+    if group.numel() != n or tuple(bbox.shape) != (n, 4):
+        raise ValueError(f"page_regions: the graph has {n} nodes, group has {group.numel()} entries, bbox is {tuple(bbox.shape)}")
+    off_h, node_off = _lib.partition_offsets(_offsets(g.batch_num_nodes_), n, "page_regions: the batch's page offsets", dev)
+    pages = off_h.size - 1
+    csr = g.in_csr()
+    _lib.require_device(csr.indptr, "page_regions")
+    comp = torch.empty(n, dtype=torch.int32, device=dev)
+    rbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    largest = int(np.diff(off_h).max()) if pages else 0
+    score = None
+    if logits is None:
+        if class_group is not None:
+            raise ValueError("page_regions: class_group without logits")
+        _lib.check(lib.gte_page_regions(P(csr.indptr), P(csr.indices), P(node_off), pages, n, largest,
+                                        P(group), P(bbox), P(comp), P(rbox), P(count), _lib.current_stream()), "gte_page_regions")
+    else:
+        _lib.require_device(logits, "page_regions")
+        logits = logits.to(torch.float32).contiguous()
+        table = torch.as_tensor(DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32).to(dev).contiguous()
+        if logits.dim() != 2 or logits.shape[0] != n or logits.shape[1] < 1 or table.numel() != logits.shape[1]:
+            raise ValueError(f"page_regions: the graph has {n} nodes, logits is {tuple(logits.shape)}, class_group has "
+                             f"{table.numel()} entries")
+        score = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.gte_page_regions_scored(P(csr.indptr), P(csr.indices), P(node_off), pages, n, largest, P(group), P(bbox),
+                                               P(logits), logits.shape[1], P(table), P(comp), P(rbox), P(count), P(score),
+                                               _lib.current_stream()), "gte_page_regions_scored")
+    root = torch.nonzero(count).flatten()
+    page = torch.bucketize(root, node_off[1:].long(), right=True)
+    return PageRegions(comp, root, page, group[root], rbox[root], count[root], None if score is None else score[root])
+
+
+def region_batches(data, all_pred, class_group=None, batch_pages=64, device=None):
+    """Stage one of :func:`extract_regions`, a generator: per ``batch_pages`` pages that hold a node, ``(ids, g, group, bbox)`` on
+    ``device`` -- ``ids`` the batch's range of page indices, ``g`` the pages' structure-only block-diagonal graph (``graph.batch``),
+    ``group`` int32 [n] the kind of every word's predicted class (``class_group``), ``bbox`` int32 [n, 4] the words' boxes."""
+    device = _lib.default_device(device)
+    sizes = [g.num_nodes() for g in data.graphs]
+    if len(all_pred) != len(sizes):
+        raise ValueError(f"extract_regions: {len(all_pred)} prediction lists for {len(sizes)} pages")
+    table = torch.as_tensor(DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32, device=device)
+    bp = max(1, int(batch_pages))
+    for b0 in range(0, len(sizes), bp):
+        ids = range(b0, min(b0 + bp, len(sizes)))
+        if sum(sizes[i] for i in ids) == 0:
+            continue
+        parts = []
+        for i in ids:
+            h = data.graphs[i].local_var()                # the structure alone: no feature rows travel for this
+            h.ndata.clear()
+            h.edata.clear()
+            parts.append(h.to(device))
+        bg = G.batch(parts)
+        pred, boxes = (np.concatenate(a) for a in _page_words(data, all_pred, ids, "extract_regions"))
+        if pred.shape[0] != bg.num_nodes():
+            raise ValueError(f"extract_regions: pages {ids.start}..{ids.stop - 1} have {bg.num_nodes()} nodes, {pred.shape[0]} "
+                             f"predictions and boxes")
+        yield ids, bg, table[torch.from_numpy(pred).to(device)], torch.from_numpy(boxes).to(device)      # class -> kind: a gather
+
+
+def region_tuples(reg: PageRegions, n_pages, min_words=1):
+    """Stage three of :func:`extract_regions`: the regions of one batch of ``n_pages`` pages as per-page lists of ``(group,
+    [x0, y0, x1, y1], n_words)`` -- ``(..., score)`` when ``reg`` carries scores -- in ascending order of the region's first word,
+    without the regions of fewer than ``min_words`` words."""
+    keep = reg.n_words >= int(min_words)
+    rows = [reg.page[keep].tolist(), reg.group[keep].tolist(), reg.box[keep].tolist(), reg.n_words[keep].tolist()]
+    if reg.score is not None:
+        rows.append(reg.score[keep].tolist())
+    out = [[] for _ in range(n_pages)]
+    for p, *rest in zip(*rows):
+        out[p].append(tuple(rest))
+    return out
+
+
+def extract_regions(data, all_pred, class_group=None, min_words=1, batch_pages=64, device=None, logits=None):
+    """Regions of every page from the node predictions: connected components of the page graph among words of one predicted
+    kind, each with the union of its words' boxes (``page_regions`` -> gte_page_regions; the reference's ``get_subgraph_bbox`` is
+    a stub; its own route, layout blocks labelled by word vote, is ``extract_blocks``).
+
+    ``all_pred``: per-page class ids in ``data.graphs`` order (``test()``'s ``'all_pred'``);
+    ``class_group[c]`` = region kind of class c, < 0 for none (default ``DEFAULT_CLASS_GROUP``: the reference's category
+    values, the three table classes merged into TABLE = 4); boxes from ``data.pages[i]['bboxs']``.  ``batch_pages`` pages go
+    through one launch.  Returns, per page, a list of ``(group, [x0, y0, x1, y1], n_words)`` in ascending order of the region's
+    first word; regions of fewer than ``min_words`` words are dropped after the compaction.
+
+    ``logits`` (float [all nodes, n_classes], the pages concatenated in ``data.graphs`` order; a tensor on any device or an array):
+    the tuples become ``(group, box, n_words, score)``, score = the region's confidence from the same launch
+    (gte_page_regions_scored: the mean over the region's words of the softmax mass on the classes of its kind)."""
+    device = _lib.default_device(device)
+    table = torch.as_tensor(DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32, device=device)
+    node_off = _offsets([g.num_nodes() for g in data.graphs])
+    if logits is not None:
+        logits = torch.as_tensor(logits)
+        if logits.dim() != 2 or logits.shape[0] != int(node_off[-1]):
+            raise ValueError(f"extract_regions: logits of shape {tuple(logits.shape)} for {int(node_off[-1])} nodes")
+    out = [[] for _ in data.graphs]
+    for ids, bg, group, bbox in region_batches(data, all_pred, table, batch_pages, device):
+        rows = None if logits is None else logits[int(node_off[ids.start]):int(node_off[ids.stop])].to(device)
+        reg = page_regions(bg, group, bbox, logits=rows, class_group=None if rows is None else table)
+        out[ids.start:ids.stop] = region_tuples(reg, len(ids), min_words)
+    return out
+
+
+def regions_json(data, regions):
+    """``{kind_name: {page_name: {'bboxes': [...], 'scores': [...]}}}``: the layout the reference's box-level evaluation reads
+    (postprocessing.py:326-345 write_json -> utils/metrics.py), kind names = the lower-case category names; the score of a
+    region is its confidence where its tuple carries one (``extract_regions(..., logits=...)``) and 1.0, as in the reference's
+    own writer, otherwise."""
+    doc = {name: {} for name in GROUP_NAMES.values()}
+    for i, page in enumerate(regions):
+        name = str(data.pages[i]['page'])
+        for kind, box, *rest in page:
+            entry = doc.setdefault(GROUP_NAMES.get(kind, str(kind)), {}).setdefault(name, {'bboxes': [], 'scores': []})
+            entry['bboxes'].append([int(v) for v in box])
+            entry['scores'].append(float(rest[1]) if len(rest) > 1 else 1.0)
+    return doc
+
+
+def regions_gt_json(data, regions):
+    """``{kind_name: {page_name: [box, ...]}}``: regions as the GROUND-TRUTH document of the box-level evaluation
+    (``utils.metrics.evaluate_regions``; the layout of the reference's ground-truth JSON, utils/metrics.py ``gt_boxes``)."""
+    return {kind: {name: entry['bboxes'] for name, entry in pages.items()} for kind, pages in regions_json(data, regions).items()}
+
+
+# ---- the reference's own route from word predictions to page objects: layout blocks labelled by word vote, tables assembled ----
+# category values of src/utils/const.py Categories_names that the assembly names
+_TABLE, _FIGURE, _COLH, _SP, _TCELL = 4, 5, 7, 8, 10
+
+
+def _y_mid(b):
+    return (b[3] + b[1]) / 2
+
+
+def _x_mid(b):
+    return (b[2] + b[0]) / 2
+
+
+def _x_meets(interval, b):
+    return interval[0] <= b[2] and interval[1] >= b[0]
+
+
+def _hull(group):
+    return [min([b[0] for b in group]), min([b[1] for b in group]), max([b[2] for b in group]), max([b[3] for b in group])]
+
+
+def _overlaps_strictly(a, b):
+    """``intersect`` of the reference's graphs/utils.py:27-34: normalised corners, both axes strictly."""
+    left, top = max(min(a[0], a[2]), min(b[0], b[2])), max(min(a[1], a[3]), min(b[1], b[3]))
+    right, bottom = min(max(a[0], a[2]), max(b[0], b[2])), min(max(a[1], a[3]), max(b[1], b[3]))
+    return bool(left < right and top < bottom)
+
+
+def assemble_tables(blocks, labels):
+    """Tables from labelled layout blocks: ``get_tables_bbox`` of the reference (postprocessing_2.py:21-195) restated -- its
+    behaviour exactly, including what looks accidental there, and the same operations on Python floats, so the result is bit
+    for bit the reference's (tests/golden/blocks_cases.json decides).  Plain Python on lists: a page has tens of blocks and
+    every rule depends on order.
+
+    ``blocks``: ``[x0, y0, x1, y1]`` per block, ``labels``: their category values.  Neither list is changed.  Returns ``(blocks,
+    labels, headers)``: the page's blocks after the assembly (untouched blocks are the caller's own objects), their categories,
+    and the merged column-header / spanning-cell boxes.
+
+    1. Per class -- column header, spanning cell, table cell, in this order -- the class's blocks form COLUMN GROUPS: a block joins
+       the first group whose x-interval it meets (closed), else opens a group.  A group's interval is the x-range of its FIRST
+       block and never widens (group 0 takes the class's first block's).  Inside a group the blocks stand by y-centre, a newcomer
+       before the first centre ``>=`` its own.
+    2. A group is split where other blocks stand between two of its members: over ALL blocks now in the list (the merged ones
+       appended for an earlier class included) that meet the group's interval, count those whose y-centre lies strictly between
+       two consecutive member centres; the SECOND such block splits the group behind the lower of the two members.  The count never
+       resets: a group is split at most once.
+    3. Every part becomes one block, the hull of its members, appended with the class's label; header and spanning hulls are also
+       the ``headers``.  Only the table-cell groups hand their intervals on.  Then the classes' original blocks leave the list.
+    4. Per handed-on interval: the blocks whose x-centre lies strictly inside, in stable order of y-centre.  Walking the
+       consecutive pairs, a header directly followed by a cell block -- or by a spanning block and then a cell block -- gives a
+       TABLE, the hull of the header and the cell block.  The walk does not skip what it merged.  The merged blocks are deleted
+       by descending index, duplicates kept as in the reference (a block named twice would take its successor along; the
+       handed-on intervals are pairwise disjoint -- a group opens only where no interval is met -- so none is).
+    5. The remaining cell blocks become TABLE.  Every block that is no table and strictly overlaps a table (as the tables stand
+       before this step) is absorbed: the table is replaced by the hull of itself and what it overlaps.
+
+    A class whose first block has inverted x-corners leaves group 0 empty and raises ``ValueError`` (the hull of nothing), as the
+    reference does."""
+    blocks, labels = list(blocks), list(labels)
+    members = {cls: [i for i, l in enumerate(labels) if l == cls] for cls in (_COLH, _SP, _TCELL)}
+    handed_on, headers = [], []
+    for cls, ids in members.items():
+        if not ids:
+            continue
+        first = blocks[ids[0]]
+        groups = [{'x': [first[0], first[2]], 'blocks': [], 'mids': []}]
+        for i in ids:
+            b = blocks[i]
+            for g in groups:
+                if _x_meets(g['x'], b):
+                    mid = _y_mid(b)
+                    at = next((k for k, m in enumerate(g['mids']) if not m < mid), len(g['mids']))
+                    g['blocks'].insert(at, b)
+                    g['mids'].insert(at, mid)
+                    break
+            else:
+                groups.append({'x': [b[0], b[2]], 'blocks': [b], 'mids': [_y_mid(b)]})
+        cuts = []
+        for g in groups:
+            cut, between, mids = None, 0, g['mids']
+            for b in blocks:
+                if not _x_meets(g['x'], b):
+                    continue
+                mid = _y_mid(b)
+                for k in range(len(mids) - 1):
+                    if mid < mids[k]:
+                        break
+                    if mids[k] < mid < mids[k + 1]:
+                        between += 1
+                        if between == 2:
+                            cut = k + 1
+                        break
+            cuts.append(cut)
+        for g, cut in zip(groups, cuts):
+            parts = [g['blocks']] if cut is None else [part for part in (g['blocks'][:cut], g['blocks'][cut:]) if part]
+            for part in parts:
+                box = _hull(part)
+                blocks.append(box)
+                labels.append(cls)
+                if cls != _TCELL:
+                    headers.append(box)
+        if cls == _TCELL:
+            handed_on.extend(g['x'] for g in groups)
+    for i in sorted((i for ids in members.values() for i in ids), reverse=True):
+        del blocks[i], labels[i]
+
+    mids = [_y_mid(b) for b in blocks]
+    by_y = sorted(range(len(blocks)), key=lambda k: mids[k])
+    merged = []
+    for x in handed_on:
+        col = [k for k in by_y if x[0] < _x_mid(blocks[k]) < x[1]]
+        for at in range(len(col) - 1):
+            if labels[col[at]] != _COLH:
+                continue
+            head, nxt = col[at], col[at + 1]
+            if labels[nxt] == _TCELL:
+                took = [head, nxt]
+            elif at + 2 == len(col):
+                break
+            elif labels[nxt] == _SP and labels[col[at + 2]] == _TCELL:
+                took = [head, nxt, col[at + 2]]
+            else:
+                continue
+            a, b = blocks[head], blocks[took[-1]]
+            blocks.append([min(a[0], b[0]), min(a[1], b[1]), max(a[2], b[2]), max(a[3], b[3])])
+            labels.append(_TABLE)
+            merged.extend(took)
+    for i in sorted(merged, reverse=True):
+        del blocks[i], labels[i]
+
+    labels = [_TABLE if l == _TCELL else l for l in labels]
+    tables = [i for i, l in enumerate(labels) if l == _TABLE]
+    absorbed = [[b for k, b in enumerate(blocks) if labels[k] != _TABLE and _overlaps_strictly(blocks[t], b)] for t in tables]
+    gone = {k for k, b in enumerate(blocks) if labels[k] != _TABLE and any(_overlaps_strictly(blocks[t], b) for t in tables)}
+    for t, inside in zip(tables, absorbed):
+        if inside:
+            blocks.append(_hull(inside + [blocks[t]]))
+            labels.append(_TABLE)
+            gone.add(t)
+    for i in sorted(gone, reverse=True):
+        del blocks[i], labels[i]
+    return blocks, labels, headers
+
+
+class BlockVote(NamedTuple):
+    """Result of :func:`block_vote`."""
+    word_block: torch.Tensor  # int32 [n]        global index of the word's block, -1 for a word outside every block
+    votes: torch.Tensor       # int32 [B, n_cat] the blocks' counters
+    label: torch.Tensor       # int32 [B]        the lowest category with the largest count (0 for a block without votes)
+
+
+def block_vote(bbox: torch.Tensor, node_off, word_cat: torch.Tensor, block_box: torch.Tensor, block_off, n_cat: int = 13,
+               double_cat: int = 2) -> BlockVote:
+    """Layout blocks labelled by the vote of their words (gte_block_vote, one launch; the words x blocks loop of the reference's
+    ``get_objects_bboxs``, postprocessing_2.py:240-258).
+
+    ``bbox`` int32 [n, 4] word boxes and ``word_cat`` int32 [n] their categories (the reference's ORIGINAL category values:
+    :data:`DEFAULT_CLASS_CATEGORY` of the predicted class), pages concatenated; ``block_box`` float64 [B, 4] the pages' layout
+    blocks ALREADY divided by the scale factor on the host; ``node_off`` / ``block_off`` host sequences [pages + 1].  A word goes
+    to the first block of its page that its rectangle meets (closed test, corners normalised) and adds 2 to the block's counter
+    of its category if that is ``double_cat`` (TITLE; -1: none), else 1; a category outside ``[0, n_cat)`` casts no vote.
+    Raises ``ValueError`` on shapes, dtypes or offsets that do not fit, ``GteError`` when a page has more than
+    ``gte_block_vote_max_page_blocks()`` blocks.  No synchronisation."""
+    _lib.require_device(bbox, "block_vote")
+    _lib.require_device(word_cat, "block_vote")
+    _lib.require_device(block_box, "block_vote")
+    lib, P = _lib.load(), _lib.ptr
+    dev = bbox.device
+    if bbox.dtype != torch.int32 or word_cat.dtype != torch.int32 or block_box.dtype != torch.float64:
+        raise ValueError(f"block_vote: bbox {bbox.dtype} and word_cat {word_cat.dtype} must be int32, block_box {block_box.dtype} float64")
+    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 or word_cat.dim() != 1 \
+            or word_cat.shape[0] != bbox.shape[0]:
+        raise ValueError(f"block_vote: bbox is {tuple(bbox.shape)}, word_cat {tuple(word_cat.shape)}, block_box {tuple(block_box.shape)}")
+    if word_cat.device != dev or block_box.device != dev:
+        raise ValueError("block_vote: bbox, word_cat and block_box live on different devices")
+    n, nb = bbox.shape[0], block_box.shape[0]
+    no, d_no = _lib.partition_offsets(node_off, n, "block_vote: the word offsets", dev)
+    bo, d_bo = _lib.partition_offsets(block_off, nb, "block_vote: the block offsets", dev)
+    if no.size != bo.size:
+        raise ValueError(f"block_vote: offsets of {no.size - 1} / {bo.size - 1} pages do not partition the words and the blocks")
+    if not 1 <= int(n_cat) <= lib.gte_block_vote_max_categories():
+        raise ValueError(f"block_vote: n_cat = {n_cat} outside 1 .. {lib.gte_block_vote_max_categories()}")
+    pages = no.size - 1
+    bbox, word_cat, block_box = bbox.contiguous(), word_cat.contiguous(), block_box.contiguous()
+    word_block = torch.empty(n, dtype=torch.int32, device=dev)
+    votes = torch.empty((nb, int(n_cat)), dtype=torch.int32, device=dev)
+    label = torch.empty(nb, dtype=torch.int32, device=dev)
+    _lib.check(lib.gte_block_vote(P(bbox), P(d_no), P(word_cat), P(block_box), P(d_bo), pages, n, nb,
+                                  int(np.diff(bo).max()) if pages else 0, int(n_cat), int(double_cat), P(word_block), P(votes),
+                                  P(label), _lib.current_stream()), "gte_block_vote")
+    return BlockVote(word_block, votes, label)
+
+
+class BlockBatch(NamedTuple):
+    """One launch's worth of :func:`pack_blocks`: host arrays, the pages of ``ids`` concatenated."""
+    ids: range                # the batch's page indices
+    bbox: np.ndarray          # int32 [n, 4]   word boxes
+    node_off: np.ndarray      # int64 [pages + 1]
+    word_cat: np.ndarray      # int32 [n]      the reference's category of every word's predicted class
+    block_box: np.ndarray     # float64 [B, 4] layout blocks divided by the scale (bit for bit the reference's b / sf)
+    block_off: np.ndarray     # int64 [pages + 1]
+    page_blocks: list         # per page float64 [blocks, 4]: the blocks as delivered (what the assembly works on)
+    n_cat: int                # categories to count: the thirteen, or more where ``class_category`` names a higher value
+
+
+def pack_blocks(data, all_pred, class_category=None, blocks=None, images=None, scale=0.36, batch_pages=64):
+    """Stage one of :func:`extract_blocks`: every argument check (``ValueError``; no device is touched) and the packing, a
+    :class:`BlockBatch` per ``batch_pages`` pages.  ``images`` is only checked for its length."""
+    n_pages = len(data.graphs)
+    if len(all_pred) != n_pages:
+        raise ValueError(f"extract_blocks: {len(all_pred)} prediction lists for {n_pages} pages")
+    for what, seq in (("block", blocks), ("image", images)):
+        if seq is not None and len(seq) != n_pages:
+            raise ValueError(f"extract_blocks: {len(seq)} {what} lists for {n_pages} pages")
+    if not float(scale) > 0.0:
+        raise ValueError(f"extract_blocks: scale = {scale}")
+    table = np.asarray(DEFAULT_CLASS_CATEGORY if class_category is None else class_category, dtype=np.int64).reshape(-1)
+    n_cat = max(len(CATEGORY_NAMES), int(table.max()) + 1 if table.size else 0)
+    page_blocks = []
+    for i in range(n_pages):
+        if blocks is not None:
+            pb = blocks[i]
+        elif 'blocks' in data.pages[i]:
+            pb = data.pages[i]['blocks']
+        else:
+            raise ValueError(f"extract_blocks: page {i} ({data.pages[i].get('page')}) carries no 'blocks'")
+        pb = np.asarray(pb, dtype=np.float64)
+        if pb.size == 0:
+            pb = pb.reshape(0, 4)
+        if pb.ndim != 2 or pb.shape[1] != 4:
+            raise ValueError(f"extract_blocks: the blocks of page {i} ({data.pages[i].get('page')}) have shape {pb.shape}")
+        page_blocks.append(pb)
+    out = []
+    bp = max(1, int(batch_pages))
+    for b0 in range(0, n_pages, bp):
+        ids = range(b0, min(b0 + bp, n_pages))
+        pred, boxes = _page_words(data, all_pred, ids, "extract_blocks")
+        for i, p in zip(ids, pred):
+            if p.size and (p.min() < 0 or p.max() >= table.size):
+                raise ValueError(f"extract_blocks: page {i} holds a class outside the {table.size} of class_category")
+        mine = [page_blocks[i] for i in ids]
+        out.append(BlockBatch(ids, np.concatenate(boxes), _offsets([b.shape[0] for b in boxes]), table[np.concatenate(pred)].astype(np.int32),
+                              np.concatenate(mine) / float(scale), _offsets([b.shape[0] for b in mine]), mine, n_cat))
+    return out
+
+
+def blocks_to_pages(data, batch: BlockBatch, word_block, votes, label, images=None, scale=0.36, rescale=True):
+    """Stage three of :func:`extract_blocks`: a batch's vote (host arrays as :class:`BlockVote` names them: ``word_block`` [n]
+    global or -1, ``votes`` [B, n_cat], ``label`` [B]) -> the batch's per-page dicts: ``assemble_tables`` on the unscaled blocks
+    and their voted labels, the figure rule on the page's images, the rescale, the page-local word index."""
+    out, scale = [], float(scale)
+    for k, i in enumerate(batch.ids):
+        n0, n1, k0, k1 = int(batch.node_off[k]), int(batch.node_off[k + 1]), int(batch.block_off[k]), int(batch.block_off[k + 1])
+        voted = [int(v) for v in label[k0:k1]]
+        new_blocks, new_labels, headers = assemble_tables(batch.page_blocks[k].tolist(), voted)
+        for img in (images[i] if images is not None else data.pages[i].get('images', ())):
+            box = img['bbox'] if isinstance(img, dict) else img
+            if box[3] - box[1] > 10:
+                new_blocks.append([int(v) for v in box])
+                new_labels.append(_FIGURE)
+        if rescale:
+            new_blocks = [[v / scale for v in b] for b in new_blocks]
+        wb = np.asarray(word_block[n0:n1], dtype=np.int64)
+        out.append({'blocks': new_blocks, 'labels': new_labels, 'voted_labels': voted, 'headers': headers,
+                    'word_block': np.where(wb >= 0, wb - k0, -1).tolist(), 'votes': np.asarray(votes[k0:k1]).tolist()})
+    return out
+
+
+def extract_blocks(data, all_pred, class_category=None, blocks=None, images=None, scale=0.36, rescale=True, batch_pages=64,
+                   device=None):
+    """Page objects by the reference's own route (``get_objects_bboxs``, postprocessing_2.py:197-309): the layout blocks that a
+    PDF text extractor delivers for every page are labelled by the vote of the words inside them (``block_vote`` ->
+    gte_block_vote: ONE launch per ``batch_pages`` pages, in place of the reference's words x blocks loop in Python), the
+    column-header, spanning-cell and table-cell blocks are assembled into tables (``assemble_tables``, on the host, per page, on
+    the unscaled blocks), and the page's images become FIGURE blocks.
+
+    ``all_pred``: per-page class ids in ``data.graphs`` order (``test()``'s ``'all_pred'``); ``class_category[c]`` = the
+    reference's original category value of class c (default ``DEFAULT_CLASS_CATEGORY``, its ``LableModification.revert``);
+    word boxes from ``data.pages[i]['bboxs']``.  ``blocks``: per page a sequence of ``[x0, y0, x1, y1]`` in PDF points, the text
+    blocks in the extractor's order (default ``data.pages[i]['blocks']``; a page without that key raises ``ValueError``);
+    ``images``: per page a sequence of image boxes, ``[x0, y0, x1, y1]`` or a dict with a ``'bbox'`` (default
+    ``data.pages[i].get('images', ())``): those higher than 10 are kept, every coordinate truncated with ``int()``
+    (postprocessing_2.py:264-270).  A block is compared with the word boxes after division by ``scale`` (the reference's
+    SCALE_FACTOR); ``rescale=True`` divides every output coordinate by ``scale`` (postprocessing_2.py:306), ``rescale=False``
+    gives the output of the reference's postprocessing.py.
+
+    Returns per page a dict: ``'blocks'`` / ``'labels'`` after table assembly and figures; ``'voted_labels'`` per input block;
+    ``'headers'`` (never rescaled, as in the reference); ``'word_block'`` the page-local block index of every word or -1;
+    ``'votes'`` the input blocks' counters [blocks, categories].
+
+    Out of scope: obtaining the blocks from a PDF (the caller's extractor); block confidences (the reference writes 1.0;
+    ``'votes'`` is there for callers who want a share); feeding the float-valued block document to ``evaluate_regions``, which
+    takes integer boxes."""
+    batches = pack_blocks(data, all_pred, class_category, blocks, images, scale, batch_pages)
+    device = _lib.default_device(device)
+    out = []
+    for b in batches:
+        vote = block_vote(torch.from_numpy(b.bbox).to(device), b.node_off, torch.from_numpy(b.word_cat).to(device),
+                          torch.from_numpy(b.block_box).to(device), b.block_off, n_cat=b.n_cat, double_cat=2)
+        out += blocks_to_pages(data, b, *(t.cpu().numpy() for t in vote), images=images, scale=scale, rescale=rescale)
+    return out
+
+
+def blocks_json(data, result):
+    """``{kind_name: {page_name: {'bboxes': [...], 'scores': [1.0, ...]}}}`` of ``extract_blocks``' result: the layout of the
+    reference's ``write_json`` (postprocessing_2.py:328-348, its ``ours_bboxs.json``) -- all thirteen lower-case category names
+    as keys, a page only under the kinds it has, coordinates as floats, every score 1.0."""
+    doc = {name: {} for name in CATEGORY_NAMES}
+    for i, page in enumerate(result):
+        name = str(data.pages[i]['page'])
+        for box, label in zip(page['blocks'], page['labels']):
+            entry = doc[CATEGORY_NAMES[label]].setdefault(name, {'bboxes': [], 'scores': []})
+            entry['bboxes'].append([float(v) for v in box])
+            entry['scores'].append(1.0)
+    return doc

@@ -18,9 +18,8 @@ the user set it; the CSR-ordered copies are cached per tensor version.
 from __future__ import annotations
 
 import os
-from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -716,172 +715,6 @@ def bbox_features(bbox: torch.Tensor, char_counts: torch.Tensor) -> torch.Tensor
     _lib.check(_lib.load().gte_bbox_features(_lib.ptr(bbox), _lib.ptr(counts), _lib.ptr(out), 13, bbox.shape[0],
                                              _lib.current_stream()), "gte_bbox_features")
     return out
-
-
-# ---- page regions from node predictions ------------------------------------------------------------------
-# group id of each of the 9 converted classes = the reference's ORIGINAL category value (src/utils/const.py Categories_names):
-# other -> no region, text 1, title 2, list 3, figure 5, caption 6, and the three table classes (column header, spanning cell,
-# table cell) -> 4, the TABLE category that "has no nodes" upstream.
-DEFAULT_CLASS_GROUP = (-1, 1, 2, 3, 5, 6, 4, 4, 4)
-GROUP_NAMES = {1: "text", 2: "title", 3: "list", 4: "table", 5: "figure", 6: "caption"}      # lower-case category names
-# original category value of each of the 9 converted classes, the table classes NOT merged (column header 7, spanning cell 8,
-# table cell 10): the reference's LableModification.revert for to_remove = [4, 9, 11, 12] -- what the block route votes with
-DEFAULT_CLASS_CATEGORY = (0, 1, 2, 3, 5, 6, 7, 8, 10)
-# the thirteen lower-case category names, in category order: the keys of the block document (write_json)
-CATEGORY_NAMES = ("other", "text", "title", "list", "table", "figure", "caption", "table-colh", "table-sp", "table-gcell",
-                  "table-tcell", "table-col", "table-row")
-
-
-class PageRegions(NamedTuple):
-    """Result of :func:`page_regions`: ``comp`` per node, then the regions in ascending root order."""
-    comp: torch.Tensor        # int32 [n]    smallest node id of the node's region, -1 for nodes outside every region
-    root: torch.Tensor        # int64 [R]    the region's smallest node
-    page: torch.Tensor        # int64 [R]    page of the batch
-    group: torch.Tensor       # int32 [R]    region kind
-    box: torch.Tensor         # int32 [R, 4] union of the words' boxes (x0, y0, x1, y1)
-    n_words: torch.Tensor     # int32 [R]
-    score: Optional[torch.Tensor] = None      # float32 [R]  region confidence (page_regions(..., logits=...) only)
-
-
-def page_regions(g: PageGraph, group: torch.Tensor, bbox: torch.Tensor, logits: Optional[torch.Tensor] = None,
-                 class_group=None) -> PageRegions:
-    """Regions of a batched page graph (a :class:`PageGraph` from :func:`batch` / :func:`knn_graph_from_boxes`, or a
-    :class:`ResidentBatch`): the connected components of ``g`` restricted to nodes of one ``group`` (int [n]; < 0: in no region),
-    each with the union of its words' boxes (``bbox`` int [n, 4]) -- one launch of gte_page_regions over ``g.in_csr()`` and the
-    batch's page offsets, then a torch compaction of the root rows (``nonzero`` on the counts: plumbing, one synchronisation).
-
-    With ``logits`` (float [n, C], the model's output for the batch) the same launch (gte_page_regions_scored) also gives every
-    region a confidence, ``score``: the mean over its words of the softmax mass on the classes of the region's kind,
-    ``class_group[c]`` = kind of class c (default :data:`DEFAULT_CLASS_GROUP`; the table ``group`` was derived from)."""
-    _lib.require_device(group, "page_regions")
-    _lib.require_device(bbox, "page_regions")
-    lib, P = _lib.load(), _lib.ptr
-    dev = group.device
-    n = g.num_nodes()
-    group = group.to(torch.int32).contiguous()
-    bbox = bbox.to(torch.int32).contiguous()
-    if group.numel() != n or tuple(bbox.shape) != (n, 4):
-        raise ValueError(f"page_regions: the graph has {n} nodes, group has {group.numel()} entries, bbox is {tuple(bbox.shape)}")
-    sizes = torch.as_tensor(g.batch_num_nodes_, dtype=torch.int64)
-    if int(sizes.sum()) != n:
-        raise ValueError(f"page_regions: the pages of the batch hold {int(sizes.sum())} nodes, the graph {n}")
-    node_off_h = torch.zeros(sizes.numel() + 1, dtype=torch.int64)
-    node_off_h[1:] = torch.cumsum(sizes, 0)
-    node_off = node_off_h.to(torch.int32).to(dev)
-    csr = g.in_csr()
-    _lib.require_device(csr.indptr, "page_regions")
-    comp = torch.empty(n, dtype=torch.int32, device=dev)
-    rbox = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    count = torch.empty(n, dtype=torch.int32, device=dev)
-    largest = int(sizes.max()) if sizes.numel() else 0
-    score = None
-    if logits is None:
-        if class_group is not None:
-            raise ValueError("page_regions: class_group without logits")
-        _lib.check(lib.gte_page_regions(P(csr.indptr), P(csr.indices), P(node_off), sizes.numel(), n, largest,
-                                        P(group), P(bbox), P(comp), P(rbox), P(count), _lib.current_stream()), "gte_page_regions")
-    else:
-        _lib.require_device(logits, "page_regions")
-        logits = logits.to(torch.float32).contiguous()
-        table = torch.as_tensor(DEFAULT_CLASS_GROUP if class_group is None else class_group, dtype=torch.int32).to(dev).contiguous()
-        if logits.dim() != 2 or logits.shape[0] != n or logits.shape[1] < 1 or table.numel() != logits.shape[1]:
-            raise ValueError(f"page_regions: the graph has {n} nodes, logits is {tuple(logits.shape)}, class_group has "
-                             f"{table.numel()} entries")
-        score = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(lib.gte_page_regions_scored(P(csr.indptr), P(csr.indices), P(node_off), sizes.numel(), n, largest, P(group), P(bbox),
-                                               P(logits), logits.shape[1], P(table), P(comp), P(rbox), P(count), P(score),
-                                               _lib.current_stream()), "gte_page_regions_scored")
-    root = torch.nonzero(count).flatten()
-    page = torch.bucketize(root, node_off[1:].long(), right=True)
-    return PageRegions(comp, root, page, group[root], rbox[root], count[root], None if score is None else score[root])
-
-
-def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, iou_thr) -> torch.Tensor:
-    """Match counts of the box-level evaluation (gte_box_match, one launch): ``tp`` int32 [n_thr, R] on the device.
-
-    Cell b (one page and kind) holds the predictions ``pred_box[pred_off[b]:pred_off[b + 1]]`` (int [R, 4], inside a cell ASCENDING
-    by score) and the ground truths ``gt_box[gt_off[b]:gt_off[b + 1]]``; the offsets are host sequences.
-    ``tp[j, pred_off[b] + k]`` = greedy matches (descending IoU, ``iou > iou_thr[j]`` strictly, +1 pixel convention; include/gte.h)
-    between the cell's ground truths and its predictions ``k ..``, i.e. after pruning its k lowest-scored boxes.  ``iou_thr``:
-    1 .. 16 ascending thresholds.  Raises ``ValueError`` naming the first cell whose candidate pairs exceed
-    ``gte_box_match_max_candidates()``; ``GteError`` when a cell has more than ``gte_box_match_max_boxes()`` boxes on a side.
-    One synchronisation (the cells' status words are read before the result is handed out)."""
-    import ctypes
-    _lib.require_device(pred_box, "box_match")
-    _lib.require_device(gt_box, "box_match")
-    lib, P = _lib.load(), _lib.ptr
-    dev = pred_box.device
-    pred_box = pred_box.to(torch.int32).reshape(-1, 4).contiguous()
-    gt_box = gt_box.to(dev).to(torch.int32).reshape(-1, 4).contiguous()
-    po, go = np.asarray(pred_off, dtype=np.int64).reshape(-1), np.asarray(gt_off, dtype=np.int64).reshape(-1)
-    if po.size < 1 or po.size != go.size or po[0] != 0 or go[0] != 0 or (np.diff(po) < 0).any() or (np.diff(go) < 0).any() \
-            or po[-1] != pred_box.shape[0] or go[-1] != gt_box.shape[0]:
-        raise ValueError(f"box_match: offsets of {po.size - 1} / {go.size - 1} cells do not partition {pred_box.shape[0]} predicted and "
-                         f"{gt_box.shape[0]} ground-truth boxes")
-    cells = po.size - 1
-    thr = np.ascontiguousarray(np.asarray(iou_thr, dtype=np.float64).reshape(-1))
-    tp = torch.empty((thr.size, pred_box.shape[0]), dtype=torch.int32, device=dev)
-    status = torch.empty(cells, dtype=torch.int32, device=dev)
-    d_po, d_go = torch.from_numpy(po.astype(np.int32)).to(dev), torch.from_numpy(go.astype(np.int32)).to(dev)
-    _lib.check(lib.gte_box_match(P(pred_box), P(d_po), P(gt_box), P(d_go), cells, int(np.diff(po).max()) if cells else 0,
-                                 int(np.diff(go).max()) if cells else 0, thr.ctypes.data_as(ctypes.c_void_p), thr.size, P(tp),
-                                 P(status), _lib.current_stream()), "gte_box_match")
-    bad = torch.nonzero(status).flatten()
-    if bad.numel():
-        b = int(bad[0])
-        raise ValueError(f"box_match: cell {b} ({int(po[b + 1] - po[b])} predicted x {int(go[b + 1] - go[b])} ground-truth boxes) has more "
-                         f"than {lib.gte_box_match_max_candidates()} pairs above IoU {thr[0]} (status {int(status[b])})")
-    return tp
-
-
-class BlockVote(NamedTuple):
-    """Result of :func:`block_vote`."""
-    word_block: torch.Tensor  # int32 [n]        global index of the word's block, -1 for a word outside every block
-    votes: torch.Tensor       # int32 [B, n_cat] the blocks' counters
-    label: torch.Tensor       # int32 [B]        the lowest category with the largest count (0 for a block without votes)
-
-
-def block_vote(bbox: torch.Tensor, node_off, word_cat: torch.Tensor, block_box: torch.Tensor, block_off, n_cat: int = 13,
-               double_cat: int = 2) -> BlockVote:
-    """Layout blocks labelled by the vote of their words (gte_block_vote, one launch; the words x blocks loop of the reference's
-    ``get_objects_bboxs``, postprocessing_2.py:240-258).
-
-    ``bbox`` int32 [n, 4] word boxes and ``word_cat`` int32 [n] their categories (the reference's ORIGINAL category values:
-    :data:`DEFAULT_CLASS_CATEGORY` of the predicted class), pages concatenated; ``block_box`` float64 [B, 4] the pages' layout
-    blocks ALREADY divided by the scale factor on the host; ``node_off`` / ``block_off`` host sequences [pages + 1].  A word goes
-    to the first block of its page that its rectangle meets (closed test, corners normalised) and adds 2 to the block's counter
-    of its category if that is ``double_cat`` (TITLE; -1: none), else 1; a category outside ``[0, n_cat)`` casts no vote.
-    Raises ``ValueError`` on shapes, dtypes or offsets that do not fit, ``GteError`` when a page has more than
-    ``gte_block_vote_max_page_blocks()`` blocks.  No synchronisation."""
-    _lib.require_device(bbox, "block_vote")
-    _lib.require_device(word_cat, "block_vote")
-    _lib.require_device(block_box, "block_vote")
-    lib, P = _lib.load(), _lib.ptr
-    dev = bbox.device
-    if bbox.dtype != torch.int32 or word_cat.dtype != torch.int32 or block_box.dtype != torch.float64:
-        raise ValueError(f"block_vote: bbox {bbox.dtype} and word_cat {word_cat.dtype} must be int32, block_box {block_box.dtype} float64")
-    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 or word_cat.dim() != 1 \
-            or word_cat.shape[0] != bbox.shape[0]:
-        raise ValueError(f"block_vote: bbox is {tuple(bbox.shape)}, word_cat {tuple(word_cat.shape)}, block_box {tuple(block_box.shape)}")
-    if word_cat.device != dev or block_box.device != dev:
-        raise ValueError("block_vote: bbox, word_cat and block_box live on different devices")
-    n, nb = bbox.shape[0], block_box.shape[0]
-    no, bo = np.asarray(node_off, dtype=np.int64).reshape(-1), np.asarray(block_off, dtype=np.int64).reshape(-1)
-    if no.size < 1 or no.size != bo.size or no[0] != 0 or bo[0] != 0 or (np.diff(no) < 0).any() or (np.diff(bo) < 0).any() \
-            or no[-1] != n or bo[-1] != nb:
-        raise ValueError(f"block_vote: offsets of {no.size - 1} / {bo.size - 1} pages do not partition {n} words and {nb} blocks")
-    if not 1 <= int(n_cat) <= lib.gte_block_vote_max_categories():
-        raise ValueError(f"block_vote: n_cat = {n_cat} outside 1 .. {lib.gte_block_vote_max_categories()}")
-    pages = no.size - 1
-    bbox, word_cat, block_box = bbox.contiguous(), word_cat.contiguous(), block_box.contiguous()
-    word_block = torch.empty(n, dtype=torch.int32, device=dev)
-    votes = torch.empty((nb, int(n_cat)), dtype=torch.int32, device=dev)
-    label = torch.empty(nb, dtype=torch.int32, device=dev)
-    d_no, d_bo = torch.from_numpy(no.astype(np.int32)).to(dev), torch.from_numpy(bo.astype(np.int32)).to(dev)
-    _lib.check(lib.gte_block_vote(P(bbox), P(d_no), P(word_cat), P(block_box), P(d_bo), pages, n, nb,
-                                  int(np.diff(bo).max()) if pages else 0, int(n_cat), int(double_cat), P(word_block), P(votes),
-                                  P(label), _lib.current_stream()), "gte_block_vote")
-    return BlockVote(word_block, votes, label)
 
 
 def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, max_dist: int = 500, bidirectional: bool = True,

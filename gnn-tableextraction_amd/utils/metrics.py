@@ -1,0 +1,177 @@
+"""Evaluation (the reference's ``utils/metrics.py`` and ``models/evaluate.py``): per-class precision / recall / F1 of node
+predictions, and the box-level AP of predicted regions.
+
+``evaluate_regions`` is three public stages in a row -- ``region_cells`` (host) -> ``box_match`` (gte_box_match, ONE launch) ->
+``average_precisions`` (host, numpy) -- so that the host stages run (and are tested) without a device, with a CPU oracle in place
+of the launch.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+
+def per_class_prf(y_true: np.ndarray, y_pred: np.ndarray, n_classes: int):
+    conf = np.zeros((n_classes, n_classes), dtype=np.float64)
+    np.add.at(conf, (y_true, y_pred), 1.0)
+    tp = np.diag(conf)
+    pred_n, true_n = conf.sum(0), conf.sum(1)
+    p = np.where(pred_n > 0, tp / np.maximum(pred_n, 1), 0.0)
+    r = np.where(true_n > 0, tp / np.maximum(true_n, 1), 0.0)
+    f1 = np.where(p + r > 0, 2 * p * r / np.maximum(p + r, 1e-30), 0.0)
+    return p, r, f1, conf
+
+
+class RegionCells(NamedTuple):
+    """Result of :func:`region_cells`: one cell per (kind, page) that counts, in the order of ``kinds`` and of the pages."""
+    kinds: list               # the kinds of gt_doc, then those only pred_doc knows
+    thresholds: dict          # kind -> float64 [T]: the distinct scores of ALL the kind's predictions, ascending
+    kind: list                # per cell: its kind
+    scores: list              # per cell: float64 [r] the page's scores in stable ascending order
+    pred_box: np.ndarray      # int32 [R, 4]  the cells' predictions concatenated, inside a cell in the order of ``scores``
+    pred_off: list            # [cells + 1]
+    gt_box: np.ndarray        # int32 [G, 4]  the cells' ground truths concatenated
+    gt_off: list              # [cells + 1]
+
+
+def region_cells(pred_doc, gt_doc, count_unpaired=False) -> RegionCells:
+    """Stage one of :func:`evaluate_regions`: the documents (layouts there) as cells -- the paired pages of every kind (all pages
+    with ``count_unpaired``), each page's predictions in stable ascending score order, the boxes concatenated with offsets: the
+    arguments of :func:`box_match`.  ``ValueError`` on unequal box / score counts and on a malformed box; no device is touched."""
+    kinds = list(gt_doc) + [k for k in pred_doc if k not in gt_doc]
+    kind_of, scores, pbox, gbox, po, go = [], [], [], [], [0], [0]
+    for kind in kinds:
+        preds, gts = pred_doc.get(kind, {}), gt_doc.get(kind, {})
+        pages = [pg for pg in gts if pg in preds or count_unpaired] + [pg for pg in preds if pg not in gts and count_unpaired]
+        for pg in pages:
+            sc = np.asarray(preds[pg]['scores'], dtype=np.float64).reshape(-1) if pg in preds else np.zeros(0)
+            bx = np.asarray(preds[pg]['bboxes'], dtype=np.int64).reshape(-1, 4) if pg in preds else np.zeros((0, 4), dtype=np.int64)
+            gb = np.asarray(gts.get(pg, []), dtype=np.int64).reshape(-1, 4)
+            if sc.shape[0] != bx.shape[0]:
+                raise ValueError(f"evaluate_regions: {kind} / {pg}: {bx.shape[0]} boxes, {sc.shape[0]} scores")
+            for what, a in (("predicted", bx), ("ground-truth", gb)):
+                if a.size and ((a[:, 0] > a[:, 2]).any() or (a[:, 1] > a[:, 3]).any() or np.abs(a).max() >= 1 << 24):
+                    raise ValueError(f"evaluate_regions: {kind} / {pg}: a {what} box is malformed (metrics.py:35-40) or outside +-2^24")
+            order = np.argsort(sc, kind='stable')
+            kind_of.append(kind)
+            scores.append(sc[order])
+            pbox.append(bx[order])
+            gbox.append(gb)
+            po.append(po[-1] + bx.shape[0])
+            go.append(go[-1] + gb.shape[0])
+    thresholds = {kind: np.unique(np.asarray([s for e in pred_doc.get(kind, {}).values() for s in e['scores']], dtype=np.float64))
+                  for kind in kinds}
+    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros((0, 4), dtype=np.int32)
+    return RegionCells(kinds, thresholds, kind_of, scores, cat(pbox), po, cat(gbox), go)
+
+
+def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, iou_thr) -> torch.Tensor:
+    """Match counts of the box-level evaluation (gte_box_match, one launch): ``tp`` int32 [n_thr, R] on the device.
+
+    Cell b (one page and kind) holds the predictions ``pred_box[pred_off[b]:pred_off[b + 1]]`` (int [R, 4], inside a cell ASCENDING
+    by score) and the ground truths ``gt_box[gt_off[b]:gt_off[b + 1]]``; the offsets are host sequences.
+    ``tp[j, pred_off[b] + k]`` = greedy matches (descending IoU, ``iou > iou_thr[j]`` strictly, +1 pixel convention; include/gte.h)
+    between the cell's ground truths and its predictions ``k ..``, i.e. after pruning its k lowest-scored boxes.  ``iou_thr``:
+    1 .. 16 ascending thresholds.  Raises ``ValueError`` naming the first cell whose candidate pairs exceed
+    ``gte_box_match_max_candidates()``; ``GteError`` when a cell has more than ``gte_box_match_max_boxes()`` boxes on a side.
+    One synchronisation (the cells' status words are read before the result is handed out)."""
+    _lib.require_device(pred_box, "box_match")
+    _lib.require_device(gt_box, "box_match")
+    lib, P = _lib.load(), _lib.ptr
+    dev = pred_box.device
+    pred_box = pred_box.to(torch.int32).reshape(-1, 4).contiguous()
+    gt_box = gt_box.to(dev).to(torch.int32).reshape(-1, 4).contiguous()
+    po, d_po = _lib.partition_offsets(pred_off, pred_box.shape[0], "box_match: the prediction offsets", dev)
+    go, d_go = _lib.partition_offsets(gt_off, gt_box.shape[0], "box_match: the ground-truth offsets", dev)
+    if po.size != go.size:
+        raise ValueError(f"box_match: offsets of {po.size - 1} / {go.size - 1} cells do not partition the predicted and the ground-truth boxes")
+    cells = po.size - 1
+    thr = np.ascontiguousarray(np.asarray(iou_thr, dtype=np.float64).reshape(-1))
+    tp = torch.empty((thr.size, pred_box.shape[0]), dtype=torch.int32, device=dev)
+    status = torch.empty(cells, dtype=torch.int32, device=dev)
+    _lib.check(lib.gte_box_match(P(pred_box), P(d_po), P(gt_box), P(d_go), cells, int(np.diff(po).max()) if cells else 0,
+                                 int(np.diff(go).max()) if cells else 0, thr.ctypes.data_as(ctypes.c_void_p), thr.size, P(tp),
+                                 P(status), _lib.current_stream()), "gte_box_match")
+    bad = torch.nonzero(status).flatten()
+    if bad.numel():
+        b = int(bad[0])
+        raise ValueError(f"box_match: cell {b} ({int(po[b + 1] - po[b])} predicted x {int(go[b + 1] - go[b])} ground-truth boxes) has more "
+                         f"than {lib.gte_box_match_max_candidates()} pairs above IoU {thr[0]} (status {int(status[b])})")
+    return tp
+
+
+def average_precisions(cells: RegionCells, tp):
+    """Stage three of :func:`evaluate_regions`: the cells and their match counts (``tp`` integer array [n_iou, R], the host copy of
+    :func:`box_match`'s result) -> the result of :func:`evaluate_regions`.  The sweep of a kind is one cumulative sum: a page's
+    counts change only at its own scores, so every cell adds per-event deltas at the positions of its scores among the kind's
+    thresholds.  Pure numpy."""
+    tp = np.asarray(tp, dtype=np.int64)
+    n_iou, po, go = tp.shape[0], cells.pred_off, cells.gt_off
+    out = {}
+    for kind in cells.kinds:
+        thr = cells.thresholds[kind]
+        d_tp, d_fp, d_fn = (np.zeros((n_iou, thr.size), dtype=np.int64) for _ in range(3))
+        for b, (ck, sc) in enumerate(zip(cells.kind, cells.scores)):
+            if ck != kind or thr.size == 0:
+                continue
+            r, g = sc.shape[0], go[b + 1] - go[b]
+            own = np.unique(sc)                                              # the page's own scores, ascending
+            k = np.concatenate([[0], np.searchsorted(sc, own[1:], side='left')]).astype(np.int64) if r else np.zeros(1, dtype=np.int64)
+            at = np.concatenate([[0], np.searchsorted(thr, own[1:])]).astype(np.int64) if r else np.zeros(1, dtype=np.int64)
+            t = tp[:, po[b] + k] if r else np.zeros((n_iou, 1), dtype=np.int64)              # [n_iou, events]
+            for acc, val in ((d_tp, t), (d_fp, (r - k)[None, :] - t), (d_fn, g - t)):
+                val = np.diff(val, axis=1, prepend=0)                        # the first event carries the whole state k = 0
+                acc[:, at] += val                                             # (own scores are distinct: so are the columns)
+        s_tp, s_fp, s_fn = (np.cumsum(d, axis=1) for d in (d_tp, d_fp, d_fn))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            prec = np.where(s_tp + s_fp > 0, s_tp / (s_tp + s_fp), 0.0)
+            rec = np.where(s_tp + s_fn > 0, s_tp / (s_tp + s_fn), 0.0)
+        ap = []
+        for j in range(n_iou):
+            levels = [prec[j][rec[j] >= lv] for lv in np.linspace(0.0, 1.0, 11)]
+            ap.append(float(np.mean([a.max() if a.size else 0.0 for a in levels])))
+        out[kind] = {'ap': ap, 'map': float(np.mean(ap)), 'precisions': prec.tolist(), 'recalls': rec.tolist(),
+                     'thresholds': thr.tolist()}
+    out['map'] = float(np.mean([out[k]['map'] for k in cells.kinds])) if cells.kinds else 0.0
+    return out
+
+
+def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, device=None):
+    """Box-level evaluation of predicted regions: the reference's AP at IoU thresholds (``get_avg_precision_at_iou`` of
+    src/utils/metrics.py:162-244 per kind and threshold, their mean as in evaluate.py:116-129), with the box matching of all
+    pages, kinds and thresholds in ONE launch (``box_match`` -> gte_box_match) and the curve from its integer counts.
+
+    ``pred_doc[kind][page] = {'bboxes': [[x0, y0, x1, y1], ...], 'scores': [...]}`` (``postprocessing.regions_json``),
+    ``gt_doc[kind][page] = [[x0, y0, x1, y1], ...]`` (``postprocessing.regions_gt_json``); ``iou_thrs``: 1 .. 16 ascending
+    thresholds (default ``np.linspace(0.5, 0.95, 10)``).  What the reference computes is NOT the textbook sweep, and this restates
+    it exactly:
+
+    * only PAIRED pages count: a page enters a kind's sums when it is a key of both ``pred_doc[kind]`` and ``gt_doc[kind]``.  The
+      boxes of a page that only one of the two knows are ignored (metrics.py:202-206) -- unless ``count_unpaired=True``, which
+      is NOT the reference: it counts the ground truths of such a page as false negatives and its predictions (those that the
+      page's state below keeps) as false positives;
+    * the score thresholds are the distinct scores of all the kind's predictions, ascending (unpaired pages included);
+    * a page's state LAGS: at threshold t it keeps its predictions with score >= c, c = the largest of the page's OWN scores
+      <= t (all of them below its first own score) -- a page is re-pruned only when the sweep reaches one of its own scores, so
+      a lower-scored box survives until the page's next own score;
+    * per page: IoU with the +1 pixel convention, candidates ``iou > thr`` strictly, greedy matching in descending IoU (among
+      equal IoUs the larger ``pred_index * n_gt + gt_index`` first; predictions in stable ascending score order); tp = matches,
+      fp = kept predictions - tp, fn = ground truths - tp;
+    * precision = sum tp / (sum tp + sum fp), recall with fn, 0.0 on a zero denominator; AP = the mean over the recall levels
+      ``linspace(0, 1, 11)`` of the largest precision at ``recall >= level`` (0.0 where there is none).
+
+    Returns ``{kind: {'ap': [per IoU threshold], 'map': mean, 'precisions': [[...] per IoU threshold], 'recalls': [[...]],
+    'thresholds': [score thresholds]}, ..., 'map': mean of the kinds' 'map'}`` over the kinds of ``gt_doc`` and ``pred_doc``."""
+    iou_thrs = np.linspace(0.5, 0.95, 10) if iou_thrs is None else np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
+    cells = region_cells(pred_doc, gt_doc, count_unpaired)
+    tp = np.zeros((iou_thrs.size, 0), dtype=np.int64)
+    if cells.kind:
+        device = _lib.default_device(device)
+        tp = box_match(torch.from_numpy(cells.pred_box).to(device), cells.pred_off, torch.from_numpy(cells.gt_box).to(device),
+                       cells.gt_off, iou_thrs).cpu().numpy()
+    return average_precisions(cells, tp)

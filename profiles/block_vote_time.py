@@ -2,7 +2,7 @@
 synthetic_blocks, categories from random predictions): microseconds per launch of gte_block_vote -- 20 warm-up launches, then the
 MEDIAN of 200 launches each between its own event pair -- beside a plain torch formulation of the same vote on the same tensors
 (pages padded to [pages, words, blocks], the closed test as one boolean tensor, first hit by argmax, counters by scatter_add:
-what one would write without the kernel), timed the same way.  Host wall time of model_predict.extract_blocks on these pages
+what one would write without the kernel), timed the same way.  Host wall time of postprocessing.extract_blocks on these pages
 against the same pages through the pure-Python loop of tests/blocks_ref.py (+ the same assemble_tables) beside it.
 usage: python profiles/block_vote_time.py"""
 import json
@@ -14,9 +14,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np                                                     # noqa: E402
 import torch                                                           # noqa: E402
-from gnn_tableextraction_amd import _lib, graph as G                   # noqa: E402
+from gnn_tableextraction_amd import _lib                               # noqa: E402
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP      # noqa: E402
 from gnn_tableextraction_amd.components.graphs.loader import PrebuiltPages      # noqa: E402
-from gnn_tableextraction_amd.models import model_predict               # noqa: E402
 from tests import blocks_ref                                           # noqa: E402
 
 WARMUP, LAUNCHES, SF, N_CAT = 20, 200, 0.36, 13
@@ -33,7 +33,7 @@ node_off_h = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
 block_off_h = np.concatenate([[0], np.cumsum(n_blocks)]).astype(np.int32)
 n, nb = int(node_off_h[-1]), int(block_off_h[-1])
 bbox_h = np.concatenate([np.asarray(p["bboxs"], dtype=np.int32).reshape(-1, 4) for p in data.pages])
-cat_h = np.asarray(G.DEFAULT_CLASS_CATEGORY, dtype=np.int32)[np.concatenate(pred)]
+cat_h = np.asarray(PP.DEFAULT_CLASS_CATEGORY, dtype=np.int32)[np.concatenate(pred)]
 blocks_h = np.concatenate([np.asarray(p["blocks"], dtype=np.float64).reshape(-1, 4) for p in data.pages]) / SF
 t = lambda a: torch.from_numpy(a).to(dev)
 bbox, cat, blocks, node_off, block_off = t(bbox_h), t(cat_h), t(blocks_h), t(node_off_h), t(block_off_h)
@@ -95,22 +95,22 @@ first, counters, _ = plain_torch()
 torch.cuda.synchronize()
 out["plain_torch_equal_counters"] = bool((counters[page_of_block, slot_of_block] == votes).all())
 
-model_predict.extract_blocks(data, pred, batch_pages=100)
+PP.extract_blocks(data, pred, batch_pages=100)
 t0 = time.perf_counter()
 for _ in range(5):
-    got = model_predict.extract_blocks(data, pred, batch_pages=100)
+    got = PP.extract_blocks(data, pred, batch_pages=100)
 out["extract_blocks_ms_host"] = round(1e3 * (time.perf_counter() - t0) / 5, 2)
 t0 = time.perf_counter()
 want = []
 for page, p in zip(data.pages, pred):
-    cats = [G.DEFAULT_CLASS_CATEGORY[int(c)] for c in p]
+    cats = [PP.DEFAULT_CLASS_CATEGORY[int(c)] for c in p]
     wb, v, voted = blocks_ref.vote_page(page["bboxs"], cats, np.asarray(page["blocks"], dtype=np.float64).reshape(-1, 4) / SF)
-    new_blocks, new_labels, _ = model_predict.assemble_tables([[float(x) for x in b] for b in page["blocks"]], voted)
+    new_blocks, new_labels, _ = PP.assemble_tables([[float(x) for x in b] for b in page["blocks"]], voted)
     want.append(([[x / SF for x in b] for b in new_blocks], new_labels, wb))
 out["python_loop_ms_host"] = round(1e3 * (time.perf_counter() - t0), 1)
 t0 = time.perf_counter()
 for page, r in zip(data.pages, got):
-    model_predict.assemble_tables([[float(x) for x in b] for b in page["blocks"]], r["voted_labels"])
+    PP.assemble_tables([[float(x) for x in b] for b in page["blocks"]], r["voted_labels"])
 out["assemble_tables_ms_host"] = round(1e3 * (time.perf_counter() - t0), 2)
 out["equal_to_ref"] = all(r["blocks"] == w[0] and r["labels"] == w[1] and r["word_block"] == w[2] for r, w in zip(got, want))
 print(json.dumps(out), flush=True)

@@ -1,7 +1,7 @@
 """gte_page_regions on ONE cfg2-sized synthetic batch (100 pages, their k-NN edges and boxes): microseconds per launch, kinds from
 DEFAULT_CLASS_GROUP over predictions equal to the labels / uniform over the 9 classes / all one kind (every page ONE region: the
 most rounds and the most contended accumulators) -- per case 20 warm-up launches, then 200 launches between one event pair.
-The torch compaction behind graph.page_regions (nonzero + gathers, one synchronisation) is timed beside it from the host.
+The torch compaction behind postprocessing.page_regions (nonzero + gathers, one synchronisation) is timed beside it from the host.
 usage: python profiles/regions_time.py"""
 import json
 import os
@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np                                                     # noqa: E402
 import torch                                                           # noqa: E402
 from gnn_tableextraction_amd import _lib, graph as G                   # noqa: E402
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP      # noqa: E402
 from gnn_tableextraction_amd.data import synthetic as S                # noqa: E402
 
 WARMUP, LAUNCHES = 20, 200
@@ -25,7 +26,7 @@ g.batch_num_nodes_ = [p.num_nodes for p in pages]
 csr = g.in_csr()
 bbox = torch.from_numpy(np.concatenate([p.bbox for p in pages]).astype(np.int32)).to(dev)
 node_off = torch.from_numpy(off.astype(np.int32)).to(dev)
-table = torch.tensor(G.DEFAULT_CLASS_GROUP, dtype=torch.int32, device=dev)
+table = torch.tensor(PP.DEFAULT_CLASS_GROUP, dtype=torch.int32, device=dev)
 groups = {"labels": table[torch.from_numpy(label).to(dev)],
           "uniform": table[torch.from_numpy(np.random.default_rng(7).integers(0, 9, n)).to(dev)],
           "one_kind": torch.ones(n, dtype=torch.int32, device=dev)}
@@ -53,11 +54,11 @@ for name, group in groups.items():
     e1.record()
     torch.cuda.synchronize()
     for _ in range(3):
-        G.page_regions(g, group, bbox)
+        PP.page_regions(g, group, bbox)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(20):
-        reg = G.page_regions(g, group, bbox)
+        reg = PP.page_regions(g, group, bbox)
     torch.cuda.synchronize()
     out[name] = {"kernel_us": round(1000.0 * e0.elapsed_time(e1) / LAUNCHES, 2), "regions": int(reg.root.numel()),
                  "largest_region_words": int(reg.n_words.max()) if reg.root.numel() else 0,

@@ -1,4 +1,4 @@
-"""CPU reference of the block vote (gte_block_vote of include/gte.h, graph.block_vote), written from its definition; plain Python /
+"""CPU reference of the block vote (gte_block_vote of include/gte.h, postprocessing.block_vote), written from its definition; plain Python /
 numpy (it also runs where the GPU tests run), and a maker of layout blocks for synthetic pages.
 
 The rule restates the words x blocks loop of the reference's get_objects_bboxs (postprocessing_2.py:240-258);

@@ -1,4 +1,4 @@
-"""CPU reference of the box-level evaluation (gte_box_match of include/gte.h, model_predict.evaluate_regions) and of the region
+"""CPU reference of the box-level evaluation (gte_box_match of include/gte.h, metrics.evaluate_regions) and of the region
 confidence (gte_page_regions_scored), written from their definitions; pure Python / numpy (it also runs where the GPU tests run).
 
 The evaluation restates what the reference's get_avg_precision_at_iou (src/utils/metrics.py:162-244) computes, which is not the
@@ -131,7 +131,7 @@ def avg_precision_at_iou(gt_boxes, pred_boxes, iou_thr, count_unpaired=False):
 
 
 def evaluate_doc_ref(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False):
-    """The result of model_predict.evaluate_regions, from avg_precision_at_iou."""
+    """The result of metrics.evaluate_regions, from avg_precision_at_iou."""
     iou_thrs = np.linspace(0.5, 0.95, 10) if iou_thrs is None else iou_thrs
     kinds = list(gt_doc) + [k for k in pred_doc if k not in gt_doc]
     out = {}

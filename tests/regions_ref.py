@@ -58,7 +58,7 @@ def in_csr(src, dst, n):
 
 
 def regions_list(comp, box, count, node_off, group, min_words=1):
-    """The compacted per-page form of model_predict.extract_regions: per page [(group, [x0, y0, x1, y1], n_words)] in ascending
+    """The compacted per-page form of postprocessing.extract_regions: per page [(group, [x0, y0, x1, y1], n_words)] in ascending
     root order."""
     node_off = np.asarray(node_off, dtype=np.int64)
     out = [[] for _ in range(len(node_off) - 1)]

@@ -111,7 +111,7 @@ def test_lr_schedule_mirror_follows_reduce_on_plateau():
 
 def test_per_class_f1_equals_sklearn():
     from sklearn.metrics import precision_recall_fscore_support
-    from gnn_tableextraction_amd.models.model_predict import per_class_prf
+    from gnn_tableextraction_amd.utils.metrics import per_class_prf
     rng = np.random.default_rng(0)
     for trial in range(5):
         n_classes = 9

@@ -1,4 +1,4 @@
-"""The host side of the block route (model_predict.assemble_tables, blocks_json, extract_blocks' argument checks) against the
+"""The host side of the block route (postprocessing.assemble_tables, blocks_json, extract_blocks' argument checks) against the
 reference's own get_tables_bbox on the pages of tests/golden/blocks_cases.json (tools/make_blocks_golden.py).  No GPU."""
 import copy
 import json
@@ -7,8 +7,7 @@ from types import SimpleNamespace
 
 import pytest
 
-from gnn_tableextraction_amd import graph as G
-from gnn_tableextraction_amd.models import model_predict
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "blocks_cases.json")
 TABLE, COLH, SP, TCELL = 4, 7, 8, 10
@@ -25,7 +24,7 @@ def test_assemble_tables_equals_the_reference_on_every_golden_page_and_leaves_it
     tables = headers = 0
     for i, c in enumerate(golden["assembly"]):
         blocks, labels = copy.deepcopy(c["blocks"]), list(c["labels"])
-        got_blocks, got_labels, got_headers = model_predict.assemble_tables(blocks, labels)
+        got_blocks, got_labels, got_headers = PP.assemble_tables(blocks, labels)
         assert got_blocks == c["ref"]["blocks"], i
         assert got_labels == c["ref"]["labels"], i
         assert got_headers == c["ref"]["headers"], i
@@ -38,20 +37,20 @@ def test_assemble_tables_equals_the_reference_on_every_golden_page_and_leaves_it
 
 def test_assemble_tables_takes_tuples_and_pages_without_table_blocks():
     blocks = ((10.0, 10.0, 200.0, 40.0), (10.0, 50.0, 200.0, 90.0))
-    assert model_predict.assemble_tables(blocks, (1, 2)) == ([blocks[0], blocks[1]], [1, 2], [])
-    assert model_predict.assemble_tables([], []) == ([], [], [])
+    assert PP.assemble_tables(blocks, (1, 2)) == ([blocks[0], blocks[1]], [1, 2], [])
+    assert PP.assemble_tables([], []) == ([], [], [])
     # one header above one cell block in one column: a table, the hull of the two; the paragraph it overlaps is absorbed
     page = [[10.0, 10.0, 100.0, 20.0], [12.0, 24.0, 98.0, 34.0], [50.0, 30.0, 300.0, 60.0], [10.0, 200.0, 300.0, 260.0]]
-    got = model_predict.assemble_tables(page, [COLH, TCELL, 1, 1])
+    got = PP.assemble_tables(page, [COLH, TCELL, 1, 1])
     assert got == ([[10.0, 200.0, 300.0, 260.0], [10.0, 10.0, 300.0, 60.0]], [1, TABLE], [[10.0, 10.0, 100.0, 20.0]])
 
 
 def test_default_class_category_is_the_references_revert_map(golden):
     assert golden["label_revert"]["to_remove"] == [4, 9, 11, 12]
-    assert list(G.DEFAULT_CLASS_CATEGORY) == golden["label_revert"]["revert"]
-    assert len(G.CATEGORY_NAMES) == golden["n_cat"] == 13 and len(set(G.CATEGORY_NAMES)) == 13
-    assert [G.CATEGORY_NAMES[k] for k in G.GROUP_NAMES] == list(G.GROUP_NAMES.values())
-    assert G.CATEGORY_NAMES[0] == "other" and G.CATEGORY_NAMES[TCELL] == "table-tcell" and G.CATEGORY_NAMES[12] == "table-row"
+    assert list(PP.DEFAULT_CLASS_CATEGORY) == golden["label_revert"]["revert"]
+    assert len(PP.CATEGORY_NAMES) == golden["n_cat"] == 13 and len(set(PP.CATEGORY_NAMES)) == 13
+    assert [PP.CATEGORY_NAMES[k] for k in PP.GROUP_NAMES] == list(PP.GROUP_NAMES.values())
+    assert PP.CATEGORY_NAMES[0] == "other" and PP.CATEGORY_NAMES[TCELL] == "table-tcell" and PP.CATEGORY_NAMES[12] == "table-row"
 
 
 def _data(n, blocks=True):
@@ -67,8 +66,8 @@ def test_blocks_json_has_the_thirteen_kinds_float_coordinates_and_unit_scores():
     result = [{"blocks": [[1, 2, 3, 4], [5.5, 6.0, 7.25, 8.0], [9.0, 9.0, 10.0, 10.0]], "labels": [1, 4, 1]},
               {"blocks": [], "labels": []},
               {"blocks": [[0.0, 0.0, 2.0, 2.0]], "labels": [5]}]
-    doc = model_predict.blocks_json(data, result)
-    assert list(doc) == list(G.CATEGORY_NAMES) and len(doc) == 13
+    doc = PP.blocks_json(data, result)
+    assert list(doc) == list(PP.CATEGORY_NAMES) and len(doc) == 13
     assert doc["text"] == {"doc_0.pdf": {"bboxes": [[1.0, 2.0, 3.0, 4.0], [9.0, 9.0, 10.0, 10.0]], "scores": [1.0, 1.0]}}
     assert doc["table"] == {"doc_0.pdf": {"bboxes": [[5.5, 6.0, 7.25, 8.0]], "scores": [1.0]}}
     assert doc["figure"] == {"doc_2.pdf": {"bboxes": [[0.0, 0.0, 2.0, 2.0]], "scores": [1.0]}}
@@ -81,20 +80,20 @@ def test_extract_blocks_refuses_arguments_that_do_not_fit():
     data = _data(2)
     pred = [[1], [1]]
     with pytest.raises(ValueError, match="1 prediction lists for 2 pages"):
-        model_predict.extract_blocks(data, pred[:1])
+        PP.extract_blocks(data, pred[:1])
     with pytest.raises(ValueError, match="3 block lists for 2 pages"):
-        model_predict.extract_blocks(data, pred, blocks=[[], [], []])
+        PP.extract_blocks(data, pred, blocks=[[], [], []])
     with pytest.raises(ValueError, match="1 image lists for 2 pages"):
-        model_predict.extract_blocks(data, pred, images=[[]])
+        PP.extract_blocks(data, pred, images=[[]])
     with pytest.raises(ValueError, match="scale"):
-        model_predict.extract_blocks(data, pred, scale=0.0)
+        PP.extract_blocks(data, pred, scale=0.0)
     with pytest.raises(ValueError, match=r"page 1 .*shape \(1, 3\)"):
-        model_predict.extract_blocks(data, pred, blocks=[[], [[1.0, 2.0, 3.0]]])
+        PP.extract_blocks(data, pred, blocks=[[], [[1.0, 2.0, 3.0]]])
     missing = _data(2)
     del missing.pages[1]["blocks"]
     with pytest.raises(ValueError, match=r"page 1 \(doc_1.pdf\) carries no 'blocks'"):
-        model_predict.extract_blocks(missing, pred)
+        PP.extract_blocks(missing, pred)
     with pytest.raises(ValueError, match="page 0 has 2 predictions and 1 boxes"):
-        model_predict.extract_blocks(data, [[1, 1], [1]], device="cpu")
+        PP.extract_blocks(data, [[1, 1], [1]], device="cpu")
     with pytest.raises(ValueError, match="page 1 holds a class outside"):
-        model_predict.extract_blocks(data, [[1], [9]], device="cpu")
+        PP.extract_blocks(data, [[1], [9]], device="cpu")

@@ -1,4 +1,4 @@
-"""CPU-only: tests/boxeval_ref.py (the oracle of gte_box_match and model_predict.evaluate_regions) against the reference's own
+"""CPU-only: tests/boxeval_ref.py (the oracle of gte_box_match and metrics.evaluate_regions) against the reference's own
 answers in tests/golden/boxeval_cases.json (tools/make_boxeval_golden.py: get_avg_precision_at_iou of the reference on generated
 documents without order-dependent ties), and hand cases of the rules the fixtures cannot isolate."""
 import json

@@ -1,19 +1,17 @@
-"""The box-level evaluation end to end (model_predict.evaluate_regions, test(..., region_scores / box_eval)) against the reference's
+"""The box-level evaluation end to end (metrics.evaluate_regions, test(..., region_scores / box_eval)) against the reference's
 own answers (tests/golden/boxeval_cases.json) and tests/boxeval_ref.py."""
 import json
 import os
 
 import numpy as np
 import pytest
-import torch
 
-from gnn_tableextraction_amd import GcnSAGE
-from gnn_tableextraction_amd import graph as G
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP
 from gnn_tableextraction_amd.components.graphs.loader import PrebuiltPages
 from gnn_tableextraction_amd.models import model_predict
-from gnn_tableextraction_amd.parsers.graphs import parse_args_ModelTrain
-from gnn_tableextraction_amd.utils.config import logs_from_config
+from gnn_tableextraction_amd.utils import metrics
 from tests import boxeval_ref as ref
+from tests.predict_setup import config_and_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -35,7 +33,7 @@ def test_evaluate_regions_reproduces_the_references_curves_on_every_fixture():
         golden = json.load(f)
     assert len(golden["cases"]) >= 30
     for i, c in enumerate(golden["cases"]):
-        out = model_predict.evaluate_regions(c["pred"], c["gt"], golden["iou_thrs"])
+        out = metrics.evaluate_regions(c["pred"], c["gt"], golden["iou_thrs"])
         for kind in golden["kinds"]:
             assert out[kind]["precisions"] == c["ref"][kind]["precisions"], (i, kind)
             assert out[kind]["recalls"] == c["ref"][kind]["recalls"], (i, kind)
@@ -44,7 +42,7 @@ def test_evaluate_regions_reproduces_the_references_curves_on_every_fixture():
         assert out["map"] == float(np.mean([out[k]["map"] for k in golden["kinds"]]))
     # the pages that only one side knows, counted (not the reference: tests/boxeval_ref.py states the rule)
     c = golden["cases"][0]
-    _assert_same_evaluation(model_predict.evaluate_regions(c["pred"], c["gt"], golden["iou_thrs"], count_unpaired=True),
+    _assert_same_evaluation(metrics.evaluate_regions(c["pred"], c["gt"], golden["iou_thrs"], count_unpaired=True),
                             ref.evaluate_doc_ref(c["pred"], c["gt"], golden["iou_thrs"], count_unpaired=True), golden["kinds"])
 
 
@@ -52,34 +50,28 @@ def test_test_entry_point_scores_evaluates_and_keeps_the_plain_regions(tmp_path)
     """test(data, config, box_eval=True) on 6 synthetic pages: the regions carry the device's scores, the JSON carries them,
     result['box_eval'] is tests/boxeval_ref.py applied to those regions and the label regions; predictions equal to the labels
     evaluate to AP 1.0; regions=True alone still returns 3-tuples and writes 1.0 scores."""
-    torch.manual_seed(3)
     data = PrebuiltPages.synthetic(6, in_feats=13)
-    cfg = parse_args_ModelTrain(argv=["--mode=knn", "--features", "BBOX", "--n_layers=3", "--mode_params=fixed", "--h_layer_dim=64",
-                                      "--batch_size=4", "--n_epochs=1", "--output_dir", str(tmp_path)])
-    model = GcnSAGE(13, 64, 9, 3, torch.nn.functional.relu, 0)
-    logs = logs_from_config(cfg)
-    os.makedirs(tmp_path / "weights", exist_ok=True)
-    torch.save(model.state_dict(), tmp_path / "weights" / f"{logs}.pt")
+    cfg, _, logs = config_and_weights(tmp_path)
 
     out = model_predict.test(data, cfg, box_eval=True)
     assert all(len(t) == 4 and isinstance(t[3], float) and 0.0 < t[3] <= 1.0 for page in out["regions"] for t in page)
     assert sum(len(page) for page in out["regions"]) > 0
     # the scores are the reference's on the device's own logits-free inputs: kinds, boxes and counts are the unscored regions
-    plain_regions = model_predict.extract_regions(data, out["all_pred"], batch_pages=4)
+    plain_regions = PP.extract_regions(data, out["all_pred"], batch_pages=4)
     assert [[t[:3] for t in page] for page in out["regions"]] == plain_regions
     doc = json.load(open(tmp_path / "regions" / f"{logs}.json"))
-    assert doc == model_predict.regions_json(data, out["regions"])
+    assert doc == PP.regions_json(data, out["regions"])
     assert sorted(s for kind in doc.values() for e in kind.values() for s in e["scores"]) == \
         sorted(t[3] for page in out["regions"] for t in page)
     labels = [p.label for p in data.page_arrays]
-    gt_doc = model_predict.regions_gt_json(data, model_predict.extract_regions(data, labels, batch_pages=4))
-    kinds = list(G.GROUP_NAMES.values())
+    gt_doc = PP.regions_gt_json(data, PP.extract_regions(data, labels, batch_pages=4))
+    kinds = list(PP.GROUP_NAMES.values())
     assert set(out["box_eval"]) == set(kinds) | {"map"}
     _assert_same_evaluation(out["box_eval"], ref.evaluate_doc_ref(doc, gt_doc), kinds)
 
     # predictions equal to the labels: every kind that has a region is found completely at every threshold
-    label_doc = model_predict.regions_json(data, model_predict.extract_regions(data, labels, batch_pages=4))
-    perfect = model_predict.evaluate_regions(label_doc, gt_doc)
+    label_doc = PP.regions_json(data, PP.extract_regions(data, labels, batch_pages=4))
+    perfect = metrics.evaluate_regions(label_doc, gt_doc)
     present = [k for k in kinds if gt_doc[k]]
     assert len(present) >= 2
     for kind in present:

@@ -1,4 +1,4 @@
-"""Box matching on the device (gte_box_match, graph.box_match) against tests/boxeval_ref.py.  Every output is an integer: all
+"""Box matching on the device (gte_box_match, metrics.box_match) against tests/boxeval_ref.py.  Every output is an integer: all
 comparisons are exact."""
 import math
 
@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from gnn_tableextraction_amd import _lib
-from gnn_tableextraction_amd import graph as G
+from gnn_tableextraction_amd.utils import metrics
 from tests import boxeval_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -66,7 +66,7 @@ def test_hand_cells_touching_threshold_equality_and_a_shared_tie():
     assert want[:, 0].tolist() == [1, 0, 0, 0] and not want[:, 1].any()
     assert want[:, 2].tolist() == [1, 1, 1, 0]                                            # iou == thr is not a match
     assert want[:, 3].tolist() == [1, 1, 1, 0] and want[:, 4].tolist() == [1, 1, 0, 0]    # the tie takes ground truth 1
-    tp = G.box_match(torch.from_numpy(_pack(cells)[0]).to(DEV), _pack(cells)[1], torch.from_numpy(_pack(cells)[2]).to(DEV),
+    tp = metrics.box_match(torch.from_numpy(_pack(cells)[0]).to(DEV), _pack(cells)[1], torch.from_numpy(_pack(cells)[2]).to(DEV),
                      _pack(cells)[3], thr)
     assert tp.dtype == torch.int32 and tp.is_cuda
     np.testing.assert_array_equal(tp.cpu().numpy(), want)
@@ -163,4 +163,4 @@ def test_a_cell_above_the_candidate_cap_reports_itself_and_leaves_its_neighbours
     np.testing.assert_array_equal(tp[:, 9 + m + 3:], np.tile((m - 1) - np.arange(m - 1), (2, 1)))
     pb, po, gb, go = _pack(cells)
     with pytest.raises(ValueError, match="cell 1 "):
-        G.box_match(torch.from_numpy(pb).to(DEV), po, torch.from_numpy(gb).to(DEV), go, [0.5, 0.75])
+        metrics.box_match(torch.from_numpy(pb).to(DEV), po, torch.from_numpy(gb).to(DEV), go, [0.5, 0.75])

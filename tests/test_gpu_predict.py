@@ -1,5 +1,4 @@
 """Inference entry point: ``test(data, config)`` against the CPU oracle and sklearn."""
-import os
 import pickle
 
 import numpy as np
@@ -10,16 +9,10 @@ from gnn_tableextraction_amd import GcnSAGE
 from gnn_tableextraction_amd import graph as G
 from gnn_tableextraction_amd.components.graphs.loader import PrebuiltPages
 from gnn_tableextraction_amd.models import model_predict
-from gnn_tableextraction_amd.parsers.graphs import parse_args_ModelTrain
-from gnn_tableextraction_amd.utils.config import logs_from_config
 from oracle import gcnsage_cpu as oc
+from tests.predict_setup import config_and_weights
 
 pytestmark = pytest.mark.gpu
-
-
-def _cfg(tmp_path, bs):
-    return parse_args_ModelTrain(argv=["--mode=knn", "--features", "BBOX", "--n_layers=3", "--mode_params=fixed", "--h_layer_dim=64",
-                                      f"--batch_size={bs}", "--n_epochs=1", "--output_dir", str(tmp_path)])
 
 
 def _oracle_logits(state, page):
@@ -33,14 +26,9 @@ def test_predictions_equal_the_oracle_argmax_and_the_metrics_equal_sklearn(tmp_p
     logits are closer than 1e-4 are excluded and must be rare); accuracy / precision / recall / F1 against sklearn on those
     predictions; the flat pickle at {output}/all_pred/{logs} is what post-processing reads (model_predict.py:151,172-174)."""
     from sklearn.metrics import precision_recall_fscore_support
-    torch.manual_seed(3)
     data = PrebuiltPages.synthetic(24, in_feats=13)
     # BBOX features are raw pixels / areas up to ~1e5: un-normalised, as the reference feeds them (SURVEY 7.3)
-    cfg = _cfg(tmp_path, bs)
-    model = GcnSAGE(13, 64, 9, 3, torch.nn.functional.relu, 0)
-    logs = logs_from_config(cfg)
-    os.makedirs(tmp_path / "weights", exist_ok=True)
-    torch.save(model.state_dict(), tmp_path / "weights" / f"{logs}.pt")
+    cfg, model, logs = config_and_weights(tmp_path, batch_size=bs)
     out = model_predict.test(data, cfg)
     state = {k: v.detach().clone() for k, v in model.state_dict().items()}
     n_tie = n_all = 0

@@ -1,4 +1,4 @@
-"""Region confidences on the device (gte_page_regions_scored, graph.page_regions(..., logits=...), extract_regions(..., logits=...))
+"""Region confidences on the device (gte_page_regions_scored, postprocessing.page_regions(..., logits=...), extract_regions(..., logits=...))
 against gte_page_regions (bit for bit) and the float64 score reference of tests/boxeval_ref.py.
 
 The score bound is derived, not measured: a word's q is p * 2^19 rounded (<= 2^-20), p comes from an fp32 max-subtracted softmax
@@ -12,7 +12,7 @@ from gnn_tableextraction_amd import _lib
 from gnn_tableextraction_amd import graph as G
 from gnn_tableextraction_amd.components.graphs.loader import PrebuiltPages
 from gnn_tableextraction_amd.data import synthetic as S
-from gnn_tableextraction_amd.models import model_predict
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP
 from tests import boxeval_ref as bref
 from tests import regions_ref as ref
 
@@ -153,8 +153,8 @@ def test_a_page_above_max_page_nodes_writes_no_regions_and_score_zero():
 
 
 def test_page_regions_and_extract_regions_carry_the_reference_scores():
-    """6 synthetic pages, random logits, kinds from the arg-max through DEFAULT_CLASS_GROUP: graph.page_regions(..., logits=...)
-    and model_predict.extract_regions(..., logits=...) give the regions of the unscored calls plus the reference's scores."""
+    """6 synthetic pages, random logits, kinds from the arg-max through DEFAULT_CLASS_GROUP: postprocessing.page_regions(..., logits=...)
+    and PP.extract_regions(..., logits=...) give the regions of the unscored calls plus the reference's scores."""
     data = PrebuiltPages.synthetic(6, in_feats=13)
     src, dst, _, _, _, off = S.concat_pages(data.page_arrays)
     n = int(off[-1])
@@ -162,11 +162,11 @@ def test_page_regions_and_extract_regions_carry_the_reference_scores():
     rng = np.random.default_rng(9)
     logits = (2.0 * rng.standard_normal((n, 9))).astype(np.float32)
     pred = logits.argmax(axis=1)
-    table = np.asarray(G.DEFAULT_CLASS_GROUP, dtype=np.int32)
+    table = np.asarray(PP.DEFAULT_CLASS_GROUP, dtype=np.int32)
     group = table[pred]
     g = G.batch([pg.to(DEV) for pg in data.graphs])
-    plain = G.page_regions(g, _t(group), _t(bbox))
-    reg = G.page_regions(g, _t(group), _t(bbox), logits=_t(logits, np.float32))
+    plain = PP.page_regions(g, _t(group), _t(bbox))
+    reg = PP.page_regions(g, _t(group), _t(bbox), logits=_t(logits, np.float32))
     assert plain.score is None and reg.score.dtype == torch.float32
     for a, b in zip(plain[:6], reg[:6]):
         assert torch.equal(a, b)
@@ -174,8 +174,8 @@ def test_page_regions_and_extract_regions_carry_the_reference_scores():
     roots = reg.root.cpu().numpy()
     assert len(roots) > 6 and np.abs(reg.score.cpu().numpy().astype(np.float64) - want[roots]).max() <= BOUND
     all_pred = [pred[off[i]:off[i + 1]] for i in range(6)]
-    plain_list = model_predict.extract_regions(data, all_pred, batch_pages=4)
-    scored = model_predict.extract_regions(data, all_pred, batch_pages=4, logits=logits)
+    plain_list = PP.extract_regions(data, all_pred, batch_pages=4)
+    scored = PP.extract_regions(data, all_pred, batch_pages=4, logits=logits)
     assert [[t[:3] for t in page] for page in scored] == plain_list and all(len(t) == 3 for page in plain_list for t in page)
     flat = [t[3] for page in scored for t in page]
     assert len(flat) == len(roots)                         # ascending root order, page after page: the order of `roots`

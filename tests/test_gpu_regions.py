@@ -1,20 +1,19 @@
-"""Page regions on the device (gte_page_regions, graph.page_regions, model_predict.extract_regions / test(regions=True)) against
+"""Page regions on the device (gte_page_regions, postprocessing.page_regions / extract_regions, test(regions=True)) against
 the CPU union-find of tests/regions_ref.py.  Every output is an integer: all comparisons are exact."""
 import json
-import os
 
 import numpy as np
 import pytest
 import torch
 
-from gnn_tableextraction_amd import GcnSAGE, _lib
+from gnn_tableextraction_amd import _lib
 from gnn_tableextraction_amd import graph as G
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP
 from gnn_tableextraction_amd.components.graphs.loader import PrebuiltPages
 from gnn_tableextraction_amd.data import synthetic as S
 from gnn_tableextraction_amd.models import model_predict
-from gnn_tableextraction_amd.parsers.graphs import parse_args_ModelTrain
-from gnn_tableextraction_amd.utils.config import logs_from_config
 from tests import regions_ref as ref
+from tests.predict_setup import config_and_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +45,7 @@ def _assert_equal_ref(got, indptr, indices, node_off, group, bbox):
 
 
 def _full_from_compact(reg, n):
-    """(comp, box [n, 4], count [n]) rebuilt from the compacted result of graph.page_regions."""
+    """(comp, box [n, 4], count [n]) rebuilt from the compacted result of postprocessing.page_regions."""
     box, count = np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.int32)
     root = reg.root.cpu().numpy()
     assert (np.diff(root) > 0).all()                      # ascending root order
@@ -65,7 +64,7 @@ def test_hand_cases_through_page_regions():
     group = np.array([4, 4, -1, 4, 1, 1], dtype=np.int32)
     bbox = _boxes(np.random.default_rng(0), 6)
     g = G.PageGraph(src, dst, 6, device=DEV)
-    reg = G.page_regions(g, torch.from_numpy(group).to(DEV), torch.from_numpy(bbox).to(DEV))
+    reg = PP.page_regions(g, torch.from_numpy(group).to(DEV), torch.from_numpy(bbox).to(DEV))
     indptr, indices = ref.in_csr(src, dst, 6)
     _assert_equal_ref(_full_from_compact(reg, 6), indptr, indices, [0, 6], group, bbox)
     assert reg.comp.tolist() == [0, 0, -1, 3, 4, 4] and reg.root.tolist() == [0, 3, 4]
@@ -73,7 +72,7 @@ def test_hand_cases_through_page_regions():
     # a directed-only entry 2 -> 0 joins its endpoints; node 1 (no edge at all) is a region of one word; two pages
     g2 = G.batch([G.PageGraph([2], [0], 4, device=DEV), G.PageGraph([0], [1], 2, device=DEV)])
     group2 = np.array([3, 3, 3, -1, 0, 0], dtype=np.int32)
-    reg2 = G.page_regions(g2, torch.from_numpy(group2).to(DEV), torch.from_numpy(bbox).to(DEV))
+    reg2 = PP.page_regions(g2, torch.from_numpy(group2).to(DEV), torch.from_numpy(bbox).to(DEV))
     indptr2, indices2 = ref.in_csr([2, 4], [0, 5], 6)
     _assert_equal_ref(_full_from_compact(reg2, 6), indptr2, indices2, [0, 4, 6], group2, bbox)
     assert reg2.comp.tolist() == [0, 1, 0, -1, 4, 4] and reg2.root.tolist() == [0, 1, 4] and reg2.page.tolist() == [0, 0, 1]
@@ -158,7 +157,7 @@ def realistic():
     bbox = np.concatenate([p.bbox for p in data.page_arrays]).astype(np.int32)
     indptr, indices = ref.in_csr(src, dst, n)
     preds = {"random": np.random.default_rng(7).integers(0, 9, n), "labels": label.astype(np.int64)}
-    table = np.asarray(G.DEFAULT_CLASS_GROUP, dtype=np.int32)
+    table = np.asarray(PP.DEFAULT_CLASS_GROUP, dtype=np.int32)
     want = {k: ref.page_regions_ref(indptr, indices, off, table[p], bbox) for k, p in preds.items()}
     return data, off, bbox, preds, want
 
@@ -174,9 +173,9 @@ def test_synthetic_pages_with_their_knn_edges(realistic, which, through):
         g = G.batch([pg.to(DEV) for pg in data.graphs])
     else:
         g = G.ResidentPages(data.graphs, DEV).batch(list(range(len(data.graphs))))
-    table = torch.tensor(G.DEFAULT_CLASS_GROUP, dtype=torch.int32, device=DEV)
+    table = torch.tensor(PP.DEFAULT_CLASS_GROUP, dtype=torch.int32, device=DEV)
     group = table[torch.from_numpy(preds[which]).to(DEV)]
-    reg = G.page_regions(g, group, torch.from_numpy(bbox).to(DEV))
+    reg = PP.page_regions(g, group, torch.from_numpy(bbox).to(DEV))
     for name, a, b in zip(("comp", "region_box", "region_count"), _full_from_compact(reg, n), want[which]):
         np.testing.assert_array_equal(a, b, err_msg=name)
     roots = reg.root.cpu().numpy()
@@ -188,26 +187,20 @@ def test_synthetic_pages_with_their_knn_edges(realistic, which, through):
 def test_test_entry_point_returns_and_writes_the_regions(tmp_path):
     """test(data, config, regions=True) on 6 synthetic pages: result['regions'] is the CPU reference applied to result['all_pred'],
     the JSON file parses back to the same boxes, and regions=False returns exactly the keys it returned before."""
-    torch.manual_seed(3)
     data = PrebuiltPages.synthetic(6, in_feats=13)
-    cfg = parse_args_ModelTrain(argv=["--mode=knn", "--features", "BBOX", "--n_layers=3", "--mode_params=fixed", "--h_layer_dim=64",
-                                      "--batch_size=4", "--n_epochs=1", "--output_dir", str(tmp_path)])
-    model = GcnSAGE(13, 64, 9, 3, torch.nn.functional.relu, 0)
-    logs = logs_from_config(cfg)
-    os.makedirs(tmp_path / "weights", exist_ok=True)
-    torch.save(model.state_dict(), tmp_path / "weights" / f"{logs}.pt")
+    cfg, _, logs = config_and_weights(tmp_path)
     out = model_predict.test(data, cfg, regions=True)
     src, dst, _, _, _, off = S.concat_pages(data.page_arrays)
     n = int(off[-1])
     bbox = np.concatenate([p.bbox for p in data.page_arrays]).astype(np.int32)
     indptr, indices = ref.in_csr(src, dst, n)
-    group = np.asarray(G.DEFAULT_CLASS_GROUP, dtype=np.int32)[np.concatenate(out["all_pred"])]
+    group = np.asarray(PP.DEFAULT_CLASS_GROUP, dtype=np.int32)[np.concatenate(out["all_pred"])]
     comp, box, count = ref.page_regions_ref(indptr, indices, off, group, bbox)
     want = ref.regions_list(comp, box, count, off, group)
     assert out["regions"] == want
     # a model that has not been trained may put every word into 'other': the same pages with their labels as predictions
-    by_label = model_predict.extract_regions(data, [p.label for p in data.page_arrays], min_words=2, batch_pages=4)
-    lgroup = np.asarray(G.DEFAULT_CLASS_GROUP, dtype=np.int32)[np.concatenate([p.label for p in data.page_arrays])]
+    by_label = PP.extract_regions(data, [p.label for p in data.page_arrays], min_words=2, batch_pages=4)
+    lgroup = np.asarray(PP.DEFAULT_CLASS_GROUP, dtype=np.int32)[np.concatenate([p.label for p in data.page_arrays])]
     lwant = ref.regions_list(*ref.page_regions_ref(indptr, indices, off, lgroup, bbox), off, lgroup, min_words=2)
     assert by_label == lwant and sum(len(p) for p in lwant) > 6
     doc = json.load(open(tmp_path / "regions" / f"{logs}.json"))

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from gnn_tableextraction_amd import _lib, graph as G
+from gnn_tableextraction_amd.components.graphs import postprocessing as PP
 
 _P = 0x10000          # a dummy 16-byte aligned address: never dereferenced, no call below reaches a launch
 
@@ -43,7 +44,7 @@ def test_bad_arguments_return_error_codes_without_launching():
 
 def test_default_class_group_merges_the_table_classes_and_drops_other():
     from gnn_tableextraction_amd.components.graphs.loader import ORIGIN_TO_CONV
-    table = G.DEFAULT_CLASS_GROUP
+    table = PP.DEFAULT_CLASS_GROUP
     assert len(table) == 9 and table[0] == -1
     conv_to_origin = {v: k for k, v in ORIGIN_TO_CONV.items() if v is not None}
     for conv, kind in enumerate(table):
@@ -54,10 +55,10 @@ def test_default_class_group_merges_the_table_classes_and_drops_other():
             assert kind < 0
         else:
             assert kind == origin                         # text 1, title 2, list 3, figure 5, caption 6
-    assert {G.GROUP_NAMES[k] for k in table if k >= 0} == {"text", "title", "list", "table", "figure", "caption"}
+    assert {PP.GROUP_NAMES[k] for k in table if k >= 0} == {"text", "title", "list", "table", "figure", "caption"}
 
 
 def test_page_regions_refuses_host_tensors():
     g = G.PageGraph([0, 1], [1, 0], 2)
     with pytest.raises(_lib.GteError):
-        G.page_regions(g, torch.zeros(2, dtype=torch.int32), torch.zeros((2, 4), dtype=torch.int32))
+        PP.page_regions(g, torch.zeros(2, dtype=torch.int32), torch.zeros((2, 4), dtype=torch.int32))
