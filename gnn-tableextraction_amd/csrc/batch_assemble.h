@@ -18,24 +18,21 @@ __device__ __forceinline__ int seg_of(const int32_t* __restrict__ off, int nb, i
 }
 
 // ---- the whole batch in one launch -----------------------------------------------------------------------------
-// One run = n consecutive dwords src -> dst (+ an integer constant for index arrays).  The workgroups of a page split
-// every run in 16-byte pieces aligned on the DESTINATION (head / tail dwords by single lanes); four pieces per lane are
-// requested before the first store.
+// One run = n consecutive dwords src -> dst (+ an integer constant for index arrays).  ONE workgroup moves a run in
+// 16-byte pieces aligned on the DESTINATION (head / tail dwords by single lanes); four pieces per lane are requested
+// before the first store.
 struct __attribute__((packed, aligned(4))) u4 { uint32_t x, y, z, w; };
 
 template <bool ADD>
-__device__ __forceinline__ void copy_run(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int64_t n, uint32_t add,
-                                         int worker, int workers) {
+__device__ __forceinline__ void copy_run(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int64_t n, uint32_t add) {
     if (n <= 0) return;
     int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) >> 2;
     if (head > n) head = n;
     const int64_t body = (n - head) >> 2, tail0 = head + 4 * body;
-    const int t = worker * 256 + (int)threadIdx.x, stride = workers * 256;
-    if (worker == 0) {
-        if ((int64_t)threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x] + (ADD ? add : 0u);
-        const int64_t j = tail0 + (threadIdx.x - 64);
-        if (threadIdx.x >= 64 && j < n) dst[j] = src[j] + (ADD ? add : 0u);
-    }
+    const int t = (int)threadIdx.x, stride = 256;
+    if ((int64_t)threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x] + (ADD ? add : 0u);
+    const int64_t j = tail0 + (threadIdx.x - 64);
+    if (threadIdx.x >= 64 && j < n) dst[j] = src[j] + (ADD ? add : 0u);
     const u4* s4 = reinterpret_cast<const u4*>(src + head);        // 4-byte aligned source: gfx950 unaligned access mode
     uint4* d4 = reinterpret_cast<uint4*>(dst + head);
     int64_t c = t;
@@ -86,7 +83,7 @@ __device__ __forceinline__ void assemble_block(const AssembleArgs& a, const int 
             if (hi <= lo) continue;                                  // empty page
             const int64_t src_row = (int64_t)a.node_off[a.pages[i]] + (lo - pb);
             copy_run<false>(reinterpret_cast<const uint32_t*>(a.feat + src_row * a.n_cols),
-                            reinterpret_cast<uint32_t*>(a.feat_out + (int64_t)lo * a.n_cols), (int64_t)(hi - lo) * a.n_cols, 0u, 0, 1);
+                            reinterpret_cast<uint32_t*>(a.feat_out + (int64_t)lo * a.n_cols), (int64_t)(hi - lo) * a.n_cols, 0u);
         }
         return;
     }
@@ -97,7 +94,7 @@ __device__ __forceinline__ void assemble_block(const AssembleArgs& a, const int 
     const int64_t o0 = a.b_node_off[i];
     if (job == 0) {
         if (a.label)
-            copy_run<false>(reinterpret_cast<const uint32_t*>(a.label + r0), reinterpret_cast<uint32_t*>(a.label_out + o0), n_i, 0u, 0, 1);
+            copy_run<false>(reinterpret_cast<const uint32_t*>(a.label + r0), reinterpret_cast<uint32_t*>(a.label_out + o0), n_i, 0u);
         if (a.row_map) {
             // batch row o0 + r  <-  resident row r0 + r: the planes GEMMs read the resident feature image through this map
             // instead of a per-batch copy of the rows; the entries past the batch name a row past the resident image
@@ -114,14 +111,13 @@ __device__ __forceinline__ void assemble_block(const AssembleArgs& a, const int 
     const int what = (job - 1) % 3;
     if (what == 0)
         copy_run<true>(reinterpret_cast<const uint32_t*>(g.indptr_loc + r0 + p), reinterpret_cast<uint32_t*>(g.indptr_out + o0),
-                       n_i + (i == a.nb - 1 ? 1 : 0), (uint32_t)eo, 0, 1);
+                       n_i + (i == a.nb - 1 ? 1 : 0), (uint32_t)eo);
     else if (what == 1)
         copy_run<true>(reinterpret_cast<const uint32_t*>(g.indices_loc + e0), reinterpret_cast<uint32_t*>(g.indices_out + eo), e_i,
-                       (uint32_t)o0, 0, 1);
+                       (uint32_t)o0);
     else if (g.weight_out) {
         if (g.weight)
-            copy_run<false>(reinterpret_cast<const uint32_t*>(g.weight + e0), reinterpret_cast<uint32_t*>(g.weight_out + eo), e_i, 0u,
-                            0, 1);
+            copy_run<false>(reinterpret_cast<const uint32_t*>(g.weight + e0), reinterpret_cast<uint32_t*>(g.weight_out + eo), e_i, 0u);
         else
             for (int64_t j = threadIdx.x; j < e_i; j += 256) g.weight_out[eo + j] = 1.0f;
     }

@@ -131,7 +131,8 @@ static int batch_assemble_impl(const int32_t* pages, int64_t n_batch, const int3
         if (!g.edge_off || !g.indptr_loc || !g.b_edge_off || !g.indptr_out)
             return gte::fail(GTE_ERR_INVALID_ARGUMENT, "batch_assemble: null CSR pointer");
     }
-    if (n_out == 0) return GTE_OK;
+    // n_out == 0 (every chosen page empty) launches too: no feature workgroup, and the last page's jobs write indptr_out[0] = 0
+    // and the row map's padding entries
     // ~32 KB of feature rows per workgroup (at least one row): ~2 500 workgroups for a 100-page batch of 831-wide rows
     int64_t rows_per_wg = feat ? 32768 / (n_cols * 4) : 1;
     if (rows_per_wg < 1) rows_per_wg = 1;

@@ -424,7 +424,7 @@ class ResidentPages:
 
     Replaces the reference's per-step ``dgl.batch(train_batch).to(device)`` (model_train.py:297): features,
     labels, both CSRs and the CSR-ordered edge weights live in HBM for the whole run; ``batch(page_ids)``
-    writes the block-diagonal union of the chosen pages with ``gte_batch_csr`` / ``gte_batch_rows``.
+    writes the block-diagonal union of the chosen pages with one ``gte_batch_assemble`` / ``gte_batch_assemble_rows`` launch.
     288 GB of HBM hold ~80 M nodes of 831 fp32 features.
     """
 

@@ -248,11 +248,20 @@ int gte_block_vote(const int32_t* bbox, const int32_t* node_off, const int32_t* 
 
 /* The whole batch in ONE launch (what the train loop calls every step; gte_batch_csr / gte_batch_rows are its pieces):
  * a page's rows are CONTIGUOUS in the resident arrays and in the batch, so every array of the batch is the concatenation
- * of per-page runs -- features and labels copied, indptr / indices copied with a per-page constant added.  Workgroup
- * (page i, worker w) moves its share of each of page i's runs with 16-byte accesses (rows need only 4-byte alignment);
- * no per-element search, no allocation, no synchronisation.  HBM-bound: 2 * n_out * n_cols * 4 bytes dominate.
- * `in` / `out`: the two CSR directions (in-edge, out-edge); any weight pointer may be NULL (then the pair is skipped);
- * label / label_out may be NULL.  feat_out has leading dimension n_cols (packed). */
+ * of per-page runs -- features and labels copied, indptr / indices copied with a per-page constant added.
+ * Workgroups: the batch's feature rows are split EVENLY, rows_per_wg = max(1, 32 KB / row bytes) consecutive batch rows per
+ * workgroup whatever the page sizes (a workgroup may cover many small pages, a large page many workgroups; one binary search
+ * over b_node_off per workgroup finds the first page it overlaps).  Behind them come 7 workgroups per chosen page, one small run
+ * each: the labels (and the row map of gte_batch_assemble_rows), and per direction indptr / indices / weights.  The last chosen
+ * page's indptr run is one entry longer (indptr_out[n_out] = e_out).  Runs move with 16-byte stores aligned on the destination
+ * (single dwords in front and behind; sources need only 4-byte alignment); no per-element search, no allocation, no
+ * synchronisation.  HBM-bound: 2 * n_out * n_cols * 4 bytes dominate.
+ * `in_edges` / `out_edges`: the two CSR directions; either may be NULL (nothing of that direction is written); in a given one
+ * edge_off, indptr_loc, b_edge_off and indptr_out are required.  weight_out NULL: no weights are written; weight_out set and
+ * weight NULL (an unweighted set): weight_out is filled with 1.0f.  label / label_out: both or neither.  feat_out has leading
+ * dimension n_cols (packed), and so must feat (ld_feat == n_cols, else GTE_ERR_UNSUPPORTED).  1 <= n_batch <= 65535.
+ * n_out == 0 (every chosen page is empty) is a launch like any other: it writes indptr_out[0] = 0 in every given direction (and
+ * the padding entries of a row map) and nothing else.  A chosen page may be empty, and may be chosen more than once. */
 typedef struct gte_batch_arrays {
     const int32_t* edge_off;      /* [P+1]  resident: first CSR entry of every page                                  */
     const int32_t* indptr_loc;    /* packed per-page indptr (see gte_batch_csr)                                        */
