@@ -910,6 +910,9 @@ constexpr int LN_CACHE = 16;      // elements per lane kept in registers -> rows
 
 __device__ __forceinline__ float wave_sum(float v) { return gte_group_sum<64>(v); }
 
+// pre = xhat gamma + beta.  The backward's ReLU mask is DEFINED on the stored stats: pre from xhat = (z - stats.mean) * stats.rstd,
+// gradient where pre > 0.  The gen forward below forms z - mean as fma(-1 / n, sum, z) instead, about |mean| / std * 2^-24 away, so
+// its y > 0 can disagree with that mask where |pre| is that close to zero (counted, and bounded, by tests/test_gpu_layernorm.py).
 __device__ __forceinline__ float ln_affine(float xhat, float g, float b) { return fmaf(xhat, g, b); }
 
 __global__ void __launch_bounds__(256)

@@ -833,7 +833,10 @@ int gte_sage_narrow_bwd_ln_p3_pad(const float* dl, int64_t lddl, const float* q,
 
 /* LayerNorm + ReLU alone (row-wise over n_out):  y = relu?(gamma * (z - mean) * rstd + beta).
  * replaces models.py:64-66 when the caller ran the linear part separately.  In place (y == z) is
- * allowed.  stats (nullable): f32[2*M] = mean, rstd. */
+ * allowed.  stats (nullable): f32[2*M] = mean, rstd.
+ * Pinned by tests/test_gpu_layernorm.py for this entry point and every fused forward form: two-pass statistics (the mean, then the
+ * sum of (z - mean)^2), the BIASED variance over the n_out true columns (never a padded width), rstd = 1 / sqrt(var + eps) with eps
+ * inside the square root, y = max(pre, 0) on pre = xhat gamma + beta.  An all-zero row is exact: mean 0, y = relu?(beta). */
 int gte_ln_relu_fwd(const float* z, int64_t ldz, const float* gamma, const float* beta, float eps, int relu,
                     float* y, int64_t ldy, float* stats, int64_t M, int64_t n_out, void* stream);
 
@@ -847,6 +850,10 @@ int gte_ln_relu_fwd_p3(const float* z, int64_t ldz, const float* gamma, const fl
  *   dz[M,n_out], and WRITES the column sums dgamma, dbeta, dbias (f32[n_out], nullable; no zero-init needed).
  * With gamma == NULL it is the backward of (relu?)(z) only.  dz may alias dy unless gamma != NULL and
  * n_out > 1024 (wide rows are re-read).
+ * The ReLU mask is DEFINED on the stored stats: xhat = (z - stats.mean) * stats.rstd, pre = fma(xhat, gamma, beta), gradient where
+ * pre > 0 and 0 at pre == 0 (torch.relu).  A forward form that subtracts the mean as fma(-1 / n, sum, z) (gte_ln_relu_fwd_p3,
+ * gte_gemm_p3_nt_ln_fwd) can round an element whose |pre| is within about |mean| / std * 2^-24 * |gamma| of zero to the other side;
+ * tests/test_gpu_layernorm.py counts those elements and holds every other one to the float64 reference.
  * workspace: gte_ln_relu_bwd_workspace_bytes(M, n_out). */
 int64_t gte_ln_relu_bwd_workspace_bytes(int64_t M, int64_t n_out);
 int gte_ln_relu_bwd(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* stats,
