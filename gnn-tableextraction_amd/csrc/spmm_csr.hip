@@ -169,12 +169,20 @@ spmm_csr_kernel(const int32_t* __restrict__ indptr, const int32_t* __restrict__ 
                     my_u = indices[my_e];
                     my_w = ew ? ew[my_e] : 1.0f;
                 }
+                if constexpr (G == 4 && EU == 4) {
+                    // one quad per row, whose four (source, weight) pairs are broadcast on DPP below whatever the row's length: a
+                    // lane past the row end takes the source of the quad's FIRST lane -- always an edge of this row (eb < hi) -- at
+                    // weight 0.  No lane group ever loads a row its destination does not name: 0 x Inf of some other node would be
+                    // a NaN in this one (the convention of include/gte.h).  The other forms clamp to the row's last edge instead.
+                    const int u_first = gte_quad_bcast<0>(my_u);
+                    if (my_e >= hi) my_u = u_first;
+                }
                 const int cnt = min(G, hi - eb);
                 for (int t = 0; t < cnt; t += EU) {
                     int u[EU];
                     float w[EU];
                     if constexpr (G == 4 && EU == 4) {
-                        // one quad per row: DPP quad broadcasts (lanes past the row end hold source 0 / weight 0)
+                        // DPP quad broadcasts (lanes past the row end hold the row's first source of this trip / weight 0)
                         u[0] = gte_quad_bcast<0>(my_u); u[1] = gte_quad_bcast<1>(my_u);
                         u[2] = gte_quad_bcast<2>(my_u); u[3] = gte_quad_bcast<3>(my_u);
                         w[0] = gte_quad_bcast<0>(my_w); w[1] = gte_quad_bcast<1>(my_w);

@@ -57,6 +57,11 @@ int gte_device_info(int* compute_units, int* wave_size, int* lds_bytes, char* ar
  * The same entry point run on the out-edge CSR is the backward of A6 (A7, DGL GSpMM.backward).
  * indptr: int32[n_rows+1]; indices: int32[nnz] (row ids of x); eweight: f32[nnz] or NULL (=1.0).
  * dtype GTE_BF16: x/out are bf16 (uint16 storage), accumulation in f32.
+ * Non-finite inputs (gte_spmm_csr, _accumulate, _accumulate_ln(_p3), _p3, _edge, _tiled): row v reads the rows of x its edges
+ * name and no others -- where a kernel pads a row's edge list to its unroll it re-uses a source of THAT row at weight 0 -- so an
+ * Inf or NaN in x[u, c] reaches out[v, c] of the out-neighbours v of u only (there it is Inf or NaN; 0 * Inf from the padding
+ * may turn an Inf into a NaN), and every other element is bit for bit what it is with x[u, c] = 0.  A zero WEIGHT on a non-finite
+ * source is a NaN, as in the reference.
  * ---------------------------------------------------------------------------------------- */
 int gte_spmm_csr(const int32_t* indptr, const int32_t* indices, const float* eweight,
                  const void* x, int64_t ldx, void* out, int64_t ldo,
