@@ -23,6 +23,7 @@
 //   four k rows a transposing read (ds_read_b64_tr_b16) touches fall on disjoint banks.
 #include "gte_common.h"
 #include "gemm_p3_host.h"
+#include "layernorm.h"
 #include "p3.h"
 #include "smallk_step.h"
 
@@ -556,7 +557,7 @@ __device__ __forceinline__ void lw_epilogue(const f32x16 (&acc)[TM][TN], char* l
                            p.accumulate, lane, p.wide_c);
     } else if constexpr (LNB == 4) {
         // ---- LayerNorm(+ReLU) FORWARD of the tile's rows: z = product + bias goes to LDS row-major per slice of TM * 32 rows, then
-        // every wave takes rows of the slice in the layout and with the arithmetic of ln_relu_fwd_gen_kernel<1, .> (lane l = columns
+        // every wave takes rows of the slice in the layout and with the arithmetic of ln_relu_fwd_vec_kernel<1, ., MSK> of layernorm.hip (lane l = columns
         // 4 l .. 4 l + 3, two-pass statistics over the n true columns): z, stats, y and the image are bit for bit what
         // gte_gemm_p3_nt + gte_ln_relu_fwd_p3 write ----
         asm volatile("s_barrier" ::: "memory");
@@ -615,7 +616,7 @@ __device__ __forceinline__ void lw_epilogue(const f32x16 (&acc)[TM][TN], char* l
 #pragma unroll
                     for (int e = 0; e < 4; ++e) s += c[e];
                     const float wsum = gte_group_sum<64>(s);           // (z - mean as one fused multiply-add of the row sum, as
-                    const float mean = wsum * inv_n;                   // ln_relu_fwd_gen_kernel writes it)
+                    const float mean = wsum * inv_n;                   // ln_relu_fwd_vec_kernel writes it)
                     float q = 0.f, dv[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { dv[e] = j4 + e < n ? fmaf(-inv_n, wsum, c[e]) : 0.f; q = fmaf(dv[e], dv[e], q); }
@@ -662,7 +663,7 @@ __device__ __forceinline__ void lw_epilogue(const f32x16 (&acc)[TM][TN], char* l
         // landed: they wait for them and join this barrier before they leave) ----
         asm volatile("s_barrier" ::: "memory");
         // Per slice of TM * 32 rows: the waves that own them put their accumulators into LDS row-major, then every wave takes
-        // rows of the slice in the layout of ln_relu_bwd_vec_kernel (lane l = columns 4 l .. 4 l + 3, two rows in flight) with
+        // rows of the slice in the layout of ln_relu_bwd_vec_kernel of layernorm.hip (lane l = columns 4 l .. 4 l + 3, two rows in flight) with
         // ITS arithmetic: dz is bit for bit what the separate launch computes from the stored product.
         static_assert(BN == 256, "whole rows per workgroup");
         constexpr int SR = TM * 32, LDT = 256;                        // slice rows; floats per LDS row

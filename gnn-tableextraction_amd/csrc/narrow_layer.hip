@@ -23,6 +23,7 @@
 // order (no atomics: deterministic).
 #include "gte_common.h"
 #include "ce_fold.h"
+#include "layernorm.h"
 #include "p3.h"
 
 #include <stdlib.h>
@@ -220,7 +221,7 @@ __device__ __forceinline__ void stage_w_image(float* __restrict__ img, int FP, c
 }
 
 // LNF: the input is the PRE-LayerNorm z of the layer below; the kernel normalises its rows in registers (statistics and
-// affine arithmetic of ln_relu_fwd_vec_kernel; a row's two halves sit in lanes i and i + 32), writes y = relu?(LN(z)) and the
+// affine arithmetic of ln_relu_fwd_vec_kernel, layernorm.hip; a row's two halves sit in lanes i and i + 32), writes y = relu?(LN(z)) and the
 // row statistics for the backward, and feeds the products from the normalised registers: the layer below needs no
 // LayerNorm launch (gte_sage_narrow_fwd_ln).
 struct LnForward { const float* gamma; const float* beta; float eps; int relu; float* y; int64_t ldy; float* stats; };
@@ -426,13 +427,13 @@ struct LnBackward {
 };
 
 // LNB: 0 plain; 2 the dh tile goes through LDS and every wave takes whole rows of it in the layout and with the arithmetic of
-// ln_relu_bwd_vec_kernel (16-byte accesses, dz as fp32 + P3 image: bit for bit gte_sage_narrow_bwd + gte_ln_relu_bwd_p3).
+// ln_relu_bwd_vec_kernel of layernorm.hip (16-byte accesses, dz as fp32 + P3 image: bit for bit gte_sage_narrow_bwd + gte_ln_relu_bwd_p3).
 // (Round 2's form 1 -- the LayerNorm backward in the accumulator layout, row sums across the four waves -- measured slower than
 // two launches, 41.6 against 39 us at 24 k x 256, and is gone; so is form 2's option of gathering q = A_w^T (norm dl) from the
 // out-edge CSR inside the kernel: 18 us of dependent loads for the 6 us launch it saved.  profiles/r03/gemm_p3.md keeps the numbers.)
 // MSK (with Ft < F): the rows are PADDED -- Ft true columns, zeros up to F (a multiple of 16): W is [C][2 Ft], the dW / LayerNorm
 // partials are written compact ([.][Ft]), the LayerNorm backward runs over the Ft true columns with per-element validity (the
-// arithmetic of ln_relu_bwd_gen_kernel) and writes zeros into the padding of dz and of its image
+// arithmetic of ln_relu_bwd_gen_kernel, layernorm.hip: gte_ln_bwd_pre4m / _post4m of layernorm.h) and writes zeros into the padding of dz and of its image
 #ifndef NB_ABL
 #define NB_ABL 0          // measurement builds (profiles/debug/build_variant.sh): 1 no dW products, 2 no LayerNorm phase, 4 no dh products,
 #endif                    // 8 no dz stores, 16 no z loads, 32 no CE fold / alpha

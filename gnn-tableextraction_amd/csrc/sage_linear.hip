@@ -1,15 +1,22 @@
-// Per-node transform of GcnSAGELayer on gfx950: fp32 MFMA GEMMs + LayerNorm/ReLU.
+// Per-node transform of GcnSAGELayer on gfx950: the fp32 MFMA GEMMs and the one-pass short-K input layer.
 //
 // replaces (reference src/components/graphs/models.py):
 //   :69-72  torch.cat((h, ah*norm), 1)      -> never materialised: the A operand is read from two
 //                                              buffers (K segments [0,k1) and [k1,k1+k2))
 //   :63     nn.Linear(2F, out)              -> v_mfma_f32_32x32x2_f32 GEMM, bias in the epilogue
-//   :64-66  nn.LayerNorm(out) + activation  -> row-wise kernel (one wave per node row)
-// and their autograd: dX = dZ W (NN), dW = dZ^T X (TN, split over the node dimension with a
-// deterministic slab reduction), LayerNorm/ReLU backward with column sums for dgamma/dbeta/dbias.
+//   :64-66  nn.LayerNorm(out) + activation  -> gte_ln_relu_fwd (layernorm.hip) after the GEMM; inside the kernel for the short-K layer
+// and the GEMM half of their autograd: dX = dZ W (NN), dW = dZ^T X (TN, split over the node dimension with a deterministic slab
+// reduction; gemm_split.h), with skinny forms for class-count-sized operands, and the transform-then-aggregate ("q-form") products.
+//
+// What this file holds:
+//   gemm_f32_mfma_kernel with its launch plan, the skinny NN / TN kernels and the split-K reduction: gte_gemm_f32,
+//     gte_sage_linear_fwd, gte_sage_linear_dw, gte_sage_transform_fwd, gte_sage_qform_dw, gte_sage_qform_dx;
+//   sage_smallk_fwd_kernel, linear + bias + LayerNorm + ReLU of a layer with k1 + k2 <= 64 inputs in ONE pass:
+//     gte_sage_linear_fwd(_p3) where gte_sage_linear_fwd_fuses_ln says so (LayerNorm arithmetic: layernorm.h; backward: smallk_bwd.hip).
+// The stand-alone LayerNorm(+ReLU) kernels and their entry points are in layernorm.hip.
 //
 // Roofline: MFMA (fp32 matrix peak 157.3 TFLOP/s; v_mfma_f32_32x32x2_f32 is bit-exact fp32 FMA
-// chains, no TF32-like shortcut exists on gfx950).  LayerNorm passes are HBM-bound.
+// chains, no TF32-like shortcut exists on gfx950).  The short-K layer is HBM-bound.
 //
 // GEMM structure (one workgroup = 4 waves, wave64):
 //   block tile BM x BN (128x128, 64x128, 128x32 or 32x128), BK = 32; every wave owns a (BM/WM)x(BN/WN) patch
@@ -22,6 +29,7 @@
 //   Row-contiguous operands ([K][rows]) keep [BK][rows+4] images read with conflict-free ds_read_b32.
 //   blockIdx is remapped so that the tiles sharing an A row-panel run on one XCD (its L2 keeps it).
 #include "gte_common.h"
+#include "layernorm.h"
 #include "p3.h"
 
 #include <stdlib.h>
@@ -45,7 +53,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 }
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };
+using namespace gte_ln;           // f4u, wave_sum, ln_affine (layernorm.h)
 
 constexpr int BK = 32;
 constexpr int KPAD = BK + 4;      // row stride (floats) of a K-contiguous LDS image
@@ -903,613 +911,6 @@ int64_t gemm_workspace(int64_t M, int64_t N, int64_t K1, int64_t K2, int64_t Nse
     return pl.splits_bound > 1 ? gte::round_up((int64_t)pl.splits_bound * M * N * 4, 256) : 256;
 }
 
-// ------------------------------- LayerNorm + ReLU, forward ----------------------------------------
-// y = relu?( gamma * (z - mean) * rstd + beta ); one wave per row, two-pass mean/variance (biased
-// variance, eps inside the sqrt: torch.nn.LayerNorm).  In place (y == z) is allowed.
-constexpr int LN_CACHE = 16;      // elements per lane kept in registers -> rows up to 1024 wide
-
-__device__ __forceinline__ float wave_sum(float v) { return gte_group_sum<64>(v); }
-
-// pre = xhat gamma + beta.  The backward's ReLU mask is DEFINED on the stored stats: pre from xhat = (z - stats.mean) * stats.rstd,
-// gradient where pre > 0.  The gen forward below forms z - mean as fma(-1 / n, sum, z) instead, about |mean| / std * 2^-24 away, so
-// its y > 0 can disagree with that mask where |pre| is that close to zero (counted, and bounded, by tests/test_gpu_layernorm.py).
-__device__ __forceinline__ float ln_affine(float xhat, float g, float b) { return fmaf(xhat, g, b); }
-
-__global__ void __launch_bounds__(256)
-ln_relu_fwd_kernel(const float* __restrict__ z, int64_t ldz, const float* __restrict__ gamma,
-                   const float* __restrict__ beta, float eps, int relu, float* __restrict__ y, int64_t ldy,
-                   float* __restrict__ stats, int M, int n) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    const float* zr = z + (int64_t)row * ldz;
-    float* yr = y + (int64_t)row * ldy;
-    float c[LN_CACHE];
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < LN_CACHE; ++t) {
-        const int j = lane + 64 * t;
-        c[t] = j < n ? zr[j] : 0.f;
-        s += c[t];
-    }
-    for (int j = lane + 64 * LN_CACHE; j < n; j += 64) s += zr[j];
-    const float mean = wave_sum(s) / (float)n;
-    float q = 0.f;
-#pragma unroll
-    for (int t = 0; t < LN_CACHE; ++t) {
-        const int j = lane + 64 * t;
-        const float d = j < n ? c[t] - mean : 0.f;
-        q = fmaf(d, d, q);
-    }
-    for (int j = lane + 64 * LN_CACHE; j < n; j += 64) { const float d = zr[j] - mean; q = fmaf(d, d, q); }
-    const float rstd = rsqrtf(wave_sum(q) / (float)n + eps);
-    if (stats && lane == 0) { stats[row] = mean; stats[M + row] = rstd; }
-#pragma unroll
-    for (int t = 0; t < LN_CACHE; ++t) {
-        const int j = lane + 64 * t;
-        if (j < n) {
-            float v = ln_affine((c[t] - mean) * rstd, gamma[j], beta[j]);
-            if (relu) v = fmaxf(v, 0.f);
-            yr[j] = v;
-        }
-    }
-    for (int j = lane + 64 * LN_CACHE; j < n; j += 64) {
-        float v = ln_affine((zr[j] - mean) * rstd, gamma[j], beta[j]);
-        if (relu) v = fmaxf(v, 0.f);
-        yr[j] = v;
-    }
-}
-
-// 16-byte accesses, two rows in flight per wave: lane l owns columns 4 (l + 64 v) .. + 3 (n % 4 == 0, n <= 256 NV).
-// Same two-pass statistics.  (The scalar version above moves 4 bytes per lane per instruction: 13.9 us for 50 MB, a plain
-// device copy of the same bytes takes 8.3 us on this chip.)
-template <int NV>
-__global__ void __launch_bounds__(256)
-ln_relu_fwd_vec_kernel(const float* __restrict__ z, int64_t ldz, const float* __restrict__ gamma,
-                       const float* __restrict__ beta, float eps, int relu, float* __restrict__ y, int64_t ldy,
-                       float* __restrict__ stats, int M, int n) {
-    const int lane = threadIdx.x & 63;
-    const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2;
-    if (row0 >= M) return;
-    float g[NV][4], b[NV][4];
-    bool okv[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int j = 4 * (lane + 64 * v);
-        okv[v] = j < n;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { g[v][e] = okv[v] ? gamma[j + e] : 0.f; b[v][e] = okv[v] ? beta[j + e] : 0.f; }
-    }
-    float c[2][NV][4];
-    bool rok[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        rok[u] = row0 + u < M;
-        const int r = rok[u] ? row0 + u : row0;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            f4u t{0.f, 0.f, 0.f, 0.f};
-            if (okv[v]) t = *reinterpret_cast<const f4u*>(z + (int64_t)r * ldz + 4 * (lane + 64 * v));
-            c[u][v][0] = t.x; c[u][v][1] = t.y; c[u][v][2] = t.z; c[u][v][3] = t.w;
-        }
-    }
-    const float inv_n = 1.0f / (float)n;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        if (!rok[u]) continue;                             // wave-uniform
-        const int r = row0 + u;
-        float s = 0.f;
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s += c[u][v][e];
-        const float mean = wave_sum(s) * inv_n;
-        float q = 0.f;
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = okv[v] ? c[u][v][e] - mean : 0.f; q = fmaf(d, d, q); }
-        const float rstd = rsqrtf(wave_sum(q) * inv_n + eps);
-        if (stats && lane == 0) { stats[r] = mean; stats[M + r] = rstd; }
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            if (okv[v]) {
-                float o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    o[e] = ln_affine((c[u][v][e] - mean) * rstd, g[v][e], b[v][e]);
-                    if (relu) o[e] = fmaxf(o[e], 0.f);
-                }
-                f4u t; t.x = o[0]; t.y = o[1]; t.z = o[2]; t.w = o[3];
-                *reinterpret_cast<f4u*>(y + (int64_t)r * ldy + 4 * (lane + 64 * v)) = t;
-            }
-        }
-    }
-}
-
-// ------------------------------- LayerNorm + ReLU, backward ---------------------------------------
-// Per row: g = relu ? (pre > 0 ? dy : 0) : dy ; dxhat = g*gamma ;
-//          dz = rstd * (dxhat - mean(dxhat) - xhat * mean(dxhat*xhat))
-// Column sums (dgamma = sum g*xhat, dbeta = sum g, dbias = sum dz) never touch atomics: every wave
-// keeps its partial sums for its columns (lane + 64 t) in registers over the rows it owns, the four
-// waves of a block are folded through LDS, the block writes partial[block][3][n], and a second kernel
-// folds the (<= LNB_MAX_BLOCKS) block partials in a fixed order.  HBM-bound: reads dy and z once,
-// writes dz once.
-constexpr int LNB_MAX_BLOCKS = 512;
-
-template <int NCH>                 // row width n <= 64 * NCH, whole row in registers
-__global__ void __launch_bounds__(256)
-ln_relu_bwd_kernel(const float* __restrict__ dy, int64_t lddy, const float* __restrict__ z, int64_t ldz,
-                   const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-                   int relu, float* __restrict__ dz, int64_t lddz, float* __restrict__ partial, int M, int n) {
-    extern __shared__ __attribute__((aligned(16))) float red[];      // [4 waves][3][NCH*64]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool has_ln = gamma != nullptr;
-    float gam[NCH], bet[NCH], s_dg[NCH], s_db[NCH], s_dbias[NCH];
-#pragma unroll
-    for (int t = 0; t < NCH; ++t) {
-        const int j = lane + 64 * t;
-        gam[t] = (has_ln && j < n) ? gamma[j] : 1.f;
-        bet[t] = (has_ln && j < n) ? beta[j] : 0.f;
-        s_dg[t] = s_db[t] = s_dbias[t] = 0.f;
-    }
-    const float inv_n = 1.0f / (float)n;
-    for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
-        const float* dyr = dy + (int64_t)row * lddy;
-        const float* zr = z + (int64_t)row * ldz;
-        float* dzr = dz + (int64_t)row * lddz;
-        float g[NCH], xh[NCH];
-        if (has_ln) {
-            const float mean = stats[row], rstd = stats[M + row];
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int t = 0; t < NCH; ++t) {
-                const int j = lane + 64 * t;
-                const bool ok = j < n;
-                xh[t] = ok ? (zr[j] - mean) * rstd : 0.f;
-                float gv = ok ? dyr[j] : 0.f;
-                if (relu && ln_affine(xh[t], gam[t], bet[t]) <= 0.f) gv = 0.f;
-                g[t] = gv;
-                const float dxh = gv * gam[t];
-                a += dxh;
-                b = fmaf(dxh, xh[t], b);
-            }
-            const float c1 = wave_sum(a) * inv_n, c2 = wave_sum(b) * inv_n;
-#pragma unroll
-            for (int t = 0; t < NCH; ++t) {
-                const int j = lane + 64 * t;
-                if (j < n) {
-                    const float d = rstd * (g[t] * gam[t] - c1 - xh[t] * c2);
-                    s_dg[t] = fmaf(g[t], xh[t], s_dg[t]);
-                    s_db[t] += g[t];
-                    s_dbias[t] += d;
-                    dzr[j] = d;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < NCH; ++t) {
-                const int j = lane + 64 * t;
-                if (j < n) {
-                    float gv = dyr[j];
-                    if (relu && zr[j] <= 0.f) gv = 0.f;
-                    s_dbias[t] += gv;
-                    dzr[j] = gv;
-                }
-            }
-        }
-    }
-    constexpr int W = NCH * 64;
-#pragma unroll
-    for (int t = 0; t < NCH; ++t) {
-        red[(wave * 3 + 0) * W + lane + 64 * t] = s_dg[t];
-        red[(wave * 3 + 1) * W + lane + 64 * t] = s_db[t];
-        red[(wave * 3 + 2) * W + lane + 64 * t] = s_dbias[t];
-    }
-    __syncthreads();
-    float* pp = partial + (int64_t)blockIdx.x * 3 * n;
-    for (int i = threadIdx.x; i < 3 * W; i += 256) {
-        const int q = i / W, j = i - q * W;
-        if (j < n) pp[q * n + j] = red[(0 * 3 + q) * W + j] + red[(1 * 3 + q) * W + j] + red[(2 * 3 + q) * W + j] +
-                                   red[(3 * 3 + q) * W + j];
-    }
-}
-
-// Same maths with 16-byte accesses: lane l owns columns 4 (l + 64 v) .. + 3, v < NV (n % 4 == 0, n <= 256 NV).  The scalar
-// version above moves 4 bytes per lane per instruction (12 memory instructions per 256-wide row): 30 us for the 75 MB
-// of a 24 k x 256 layer, 2.5 TB/s; two rows are in flight per wave here.
-template <int NV>
-__global__ void __launch_bounds__(256)
-ln_relu_bwd_vec_kernel(const float* __restrict__ dy, int64_t lddy, const float* __restrict__ z, int64_t ldz,
-                       const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-                       int relu, float* __restrict__ dz, int64_t lddz, float* __restrict__ partial, int M, int n,
-                       char* __restrict__ dzp3 = nullptr, int64_t ldp3 = 0) {
-    extern __shared__ __attribute__((aligned(16))) float red[];      // [4 waves][3][NV*256]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool has_ln = gamma != nullptr;
-    float gam[NV][4], bet[NV][4], s_dg[NV][4], s_db[NV][4], s_dbias[NV][4];
-    bool okv[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int j = 4 * (lane + 64 * v);
-        okv[v] = j < n;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            gam[v][e] = (has_ln && okv[v]) ? gamma[j + e] : 1.f;
-            bet[v][e] = (has_ln && okv[v]) ? beta[j + e] : 0.f;
-            s_dg[v][e] = s_db[v][e] = s_dbias[v][e] = 0.f;
-        }
-    }
-    const float inv_n = 1.0f / (float)n;
-    const int stride = gridDim.x * 4;
-    for (int row = blockIdx.x * 4 + wave; row < M; row += 2 * stride) {
-        // two rows per trip: all four 16-byte loads are issued before the first reduction
-        float gy[2][NV][4], zz[2][NV][4];
-        float mean[2] = {0.f, 0.f}, rstd[2] = {1.f, 1.f};
-        bool rok[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int r = row + u * stride;
-            rok[u] = r < M;
-            const int rc = rok[u] ? r : row;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int j = 4 * (lane + 64 * v);
-                f4u a{0.f, 0.f, 0.f, 0.f}, b{0.f, 0.f, 0.f, 0.f};
-                if (okv[v]) {
-                    a = *reinterpret_cast<const f4u*>(dy + (int64_t)rc * lddy + j);
-                    b = *reinterpret_cast<const f4u*>(z + (int64_t)rc * ldz + j);
-                }
-                gy[u][v][0] = a.x; gy[u][v][1] = a.y; gy[u][v][2] = a.z; gy[u][v][3] = a.w;
-                zz[u][v][0] = b.x; zz[u][v][1] = b.y; zz[u][v][2] = b.z; zz[u][v][3] = b.w;
-            }
-            if (has_ln) { mean[u] = stats[rc]; rstd[u] = stats[M + rc]; }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            if (!rok[u]) continue;                       // wave-uniform
-            float* dzr = dz + (int64_t)(row + u * stride) * lddz;
-            if (has_ln) {
-                float xh[NV][4], g[NV][4];
-                float a = 0.f, b = 0.f;
-#pragma unroll
-                for (int v = 0; v < NV; ++v)                 // (gte_common.h: the arithmetic shared with the GEMM epilogue form)
-                    gte_ln_bwd_pre4(gy[u][v], zz[u][v], mean[u], rstd[u], gam[v], bet[v], okv[v], relu, xh[v], g[v], a, b);
-                const float c1 = wave_sum(a) * inv_n, c2 = wave_sum(b) * inv_n;
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    float d[4];
-                    gte_ln_bwd_post4(g[v], xh[v], gam[v], rstd[u], c1, c2, okv[v], d, s_dg[v], s_db[v], s_dbias[v]);
-                    if (okv[v]) {
-                        f4u o; o.x = d[0]; o.y = d[1]; o.z = d[2]; o.w = d[3];
-                        *reinterpret_cast<f4u*>(dzr + 4 * (lane + 64 * v)) = o;
-                        // ... and as a P3 image: dz is the A operand of the dX and dW planes GEMMs
-                        if (dzp3) p3::store4(dzp3 + (int64_t)(row + u * stride) * ldp3, 4 * (lane + 64 * v), d[0], d[1], d[2], d[3]);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    float d[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        d[e] = (relu && zz[u][v][e] <= 0.f) ? 0.f : gy[u][v][e];
-                        s_dbias[v][e] += d[e];
-                    }
-                    if (okv[v]) {
-                        f4u o; o.x = d[0]; o.y = d[1]; o.z = d[2]; o.w = d[3];
-                        *reinterpret_cast<f4u*>(dzr + 4 * (lane + 64 * v)) = o;
-                        if (dzp3) p3::store4(dzp3 + (int64_t)(row + u * stride) * ldp3, 4 * (lane + 64 * v), d[0], d[1], d[2], d[3]);
-                    }
-                }
-            }
-        }
-    }
-    constexpr int W = NV * 256;
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int j = 4 * (lane + 64 * v) + e;
-            red[(wave * 3 + 0) * W + j] = s_dg[v][e];
-            red[(wave * 3 + 1) * W + j] = s_db[v][e];
-            red[(wave * 3 + 2) * W + j] = s_dbias[v][e];
-        }
-    __syncthreads();
-    float* pp = partial + (int64_t)blockIdx.x * 3 * n;
-    for (int i = threadIdx.x; i < 3 * W; i += 256) {
-        const int q = i / W, j = i - q * W;
-        if (j < n) pp[q * n + j] = red[(0 * 3 + q) * W + j] + red[(1 * 3 + q) * W + j] + red[(2 * 3 + q) * W + j] +
-                                   red[(3 * 3 + q) * W + j];
-    }
-}
-
-// ---- any width up to 1024 (the reference's own run shapes: hidden 1000, or int(calculate_hidden) = 96 ... 218) ----------------
-// Rows PADDED to a multiple of 4 floats (ld >= n rounded up to 4): lane l owns columns 4 (l + 64 v) .. + 3, v < NV; per-element
-// masks instead of the per-chunk mask of the vec kernels; columns n .. up to the next multiple of 4 of the fp32 outputs and up to
-// the next multiple of 16 of the P3 images are written as zeros.  Same two-pass statistics / the same backward arithmetic.
-template <int NV, int RF>
-__global__ void __launch_bounds__(256)
-ln_relu_fwd_gen_kernel(const float* __restrict__ z, int64_t ldz, const float* __restrict__ gamma, const float* __restrict__ beta,
-                       float eps, int relu, float* __restrict__ y, int64_t ldy, char* __restrict__ yp3, int64_t ldyp3,
-                       float* __restrict__ stats, int M, int n) {
-    const int lane = threadIdx.x & 63;
-    const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RF;
-    if (row0 >= M) return;
-    const int n16 = (n + 15) & ~15;
-    float g[NV][4], b[NV][4];
-    bool okv[NV], imv[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int j = 4 * (lane + 64 * v);
-        okv[v] = j < n;
-        imv[v] = j < n16;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { g[v][e] = j + e < n ? gamma[j + e] : 0.f; b[v][e] = j + e < n ? beta[j + e] : 0.f; }
-    }
-    float c[RF][NV][4];
-    bool rok[RF];
-#pragma unroll
-    for (int u = 0; u < RF; ++u) {
-        rok[u] = row0 + u < M;
-        const int r = rok[u] ? row0 + u : row0;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const int j = 4 * (lane + 64 * v);
-            f4u t{0.f, 0.f, 0.f, 0.f};
-            if (okv[v]) t = *reinterpret_cast<const f4u*>(z + (int64_t)r * ldz + j);
-            c[u][v][0] = t.x; c[u][v][1] = j + 1 < n ? t.y : 0.f; c[u][v][2] = j + 2 < n ? t.z : 0.f; c[u][v][3] = j + 3 < n ? t.w : 0.f;
-        }
-    }
-    const float inv_n = 1.0f / (float)n;
-#pragma unroll
-    for (int u = 0; u < RF; ++u) {
-        if (!rok[u]) continue;                             // wave-uniform
-        const int r = row0 + u;
-        float s = 0.f;
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s += c[u][v][e];
-        // (z - mean as ONE fused multiply-add of the row sum, written out: hipcc contracts `c - wave_sum(s) * inv_n` this way, and
-        // the LayerNorm-forward epilogue of the planes GEMM -- gemm_p3.hip, LNB == 4 -- is held bit for bit to this kernel)
-        const float wsum = wave_sum(s);
-        const float mean = wsum * inv_n;
-        float q = 0.f;
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = 4 * (lane + 64 * v) + e < n ? fmaf(-inv_n, wsum, c[u][v][e]) : 0.f; q = fmaf(d, d, q); }
-        const float rstd = rsqrtf(wave_sum(q) * inv_n + eps);
-        if (stats && lane == 0) { stats[r] = mean; stats[M + r] = rstd; }
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            if (!imv[v]) continue;
-            const int j = 4 * (lane + 64 * v);
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                o[e] = ln_affine(fmaf(-inv_n, wsum, c[u][v][e]) * rstd, g[v][e], b[v][e]);
-                if (relu) o[e] = fmaxf(o[e], 0.f);
-                if (j + e >= n) o[e] = 0.f;
-            }
-            if (y && okv[v]) {
-                f4u t; t.x = o[0]; t.y = o[1]; t.z = o[2]; t.w = o[3];
-                *reinterpret_cast<f4u*>(y + (int64_t)r * ldy + j) = t;
-            }
-            if (yp3) p3::store4(yp3 + (int64_t)r * ldyp3, j, o[0], o[1], o[2], o[3]);
-        }
-    }
-}
-
-template <int NV, int RF>
-__global__ void __launch_bounds__(256)
-ln_relu_bwd_gen_kernel(const float* __restrict__ dy, int64_t lddy, const float* __restrict__ z, int64_t ldz,
-                       const float* __restrict__ stats, const float* __restrict__ gamma, const float* __restrict__ beta,
-                       int relu, float* __restrict__ dz, int64_t lddz, float* __restrict__ partial, int M, int n,
-                       char* __restrict__ dzp3, int64_t ldp3) {
-    extern __shared__ __attribute__((aligned(16))) float red[];      // [4 waves][3][NV*256]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n16 = (n + 15) & ~15;
-    float gam[NV][4], bet[NV][4], s_dg[NV][4], s_db[NV][4], s_dbias[NV][4];
-    bool okv[NV], imv[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int j = 4 * (lane + 64 * v);
-        okv[v] = j < n;
-        imv[v] = j < n16;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            gam[v][e] = j + e < n ? gamma[j + e] : 1.f;
-            bet[v][e] = j + e < n ? beta[j + e] : 0.f;
-            s_dg[v][e] = s_db[v][e] = s_dbias[v][e] = 0.f;
-        }
-    }
-    const float inv_n = 1.0f / (float)n;
-    const int stride = gridDim.x * 4;
-    for (int row = blockIdx.x * 4 + wave; row < M; row += RF * stride) {
-        float gy[RF][NV][4], zz[RF][NV][4];
-        float mean[RF], rstd[RF];
-        bool rok[RF];
-#pragma unroll
-        for (int u = 0; u < RF; ++u) {
-            const int r = row + u * stride;
-            rok[u] = r < M;
-            const int rc = rok[u] ? r : row;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const int j = 4 * (lane + 64 * v);
-                f4u a{0.f, 0.f, 0.f, 0.f}, b{0.f, 0.f, 0.f, 0.f};
-                if (okv[v]) {
-                    a = *reinterpret_cast<const f4u*>(dy + (int64_t)rc * lddy + j);
-                    b = *reinterpret_cast<const f4u*>(z + (int64_t)rc * ldz + j);
-                }
-                gy[u][v][0] = a.x; gy[u][v][1] = a.y; gy[u][v][2] = a.z; gy[u][v][3] = a.w;
-                zz[u][v][0] = b.x; zz[u][v][1] = b.y; zz[u][v][2] = b.z; zz[u][v][3] = b.w;
-            }
-            mean[u] = stats[rc]; rstd[u] = stats[M + rc];
-        }
-#pragma unroll
-        for (int u = 0; u < RF; ++u) {
-            if (!rok[u]) continue;                       // wave-uniform
-            const int64_t r = row + u * stride;
-            float xh[NV][4], g[NV][4];
-            float a = 0.f, b = 0.f;
-            {
-#pragma clang fp contract(off)
-#pragma unroll
-                for (int v = 0; v < NV; ++v)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const bool ok = 4 * (lane + 64 * v) + e < n;
-                        xh[v][e] = ok ? (zz[u][v][e] - mean[u]) * rstd[u] : 0.f;
-                        float gv = ok ? gy[u][v][e] : 0.f;
-                        if (relu && fmaf(xh[v][e], gam[v][e], bet[v][e]) <= 0.f) gv = 0.f;
-                        g[v][e] = gv;
-                        const float dxh = gv * gam[v][e];
-                        a = a + dxh;
-                        b = fmaf(dxh, xh[v][e], b);
-                    }
-            }
-            const float c1 = wave_sum(a) * inv_n, c2 = wave_sum(b) * inv_n;
-#pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                if (!imv[v]) continue;
-                const int j = 4 * (lane + 64 * v);
-                float d[4];
-                {
-#pragma clang fp contract(off)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float t0 = g[v][e] * gam[v][e];
-                        const float t1 = xh[v][e] * c2;
-                        d[e] = j + e < n ? rstd[u] * ((t0 - c1) - t1) : 0.f;
-                        s_dg[v][e] = fmaf(g[v][e], xh[v][e], s_dg[v][e]);
-                        s_db[v][e] = s_db[v][e] + g[v][e];
-                        s_dbias[v][e] = s_dbias[v][e] + d[e];
-                    }
-                }
-                if (okv[v]) {
-                    f4u o; o.x = d[0]; o.y = d[1]; o.z = d[2]; o.w = d[3];
-                    *reinterpret_cast<f4u*>(dz + r * lddz + j) = o;
-                }
-                if (dzp3) p3::store4(dzp3 + r * ldp3, j, d[0], d[1], d[2], d[3]);
-            }
-        }
-    }
-    constexpr int W = NV * 256;
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int j = 4 * (lane + 64 * v) + e;
-            red[(wave * 3 + 0) * W + j] = s_dg[v][e];
-            red[(wave * 3 + 1) * W + j] = s_db[v][e];
-            red[(wave * 3 + 2) * W + j] = s_dbias[v][e];
-        }
-    __syncthreads();
-    float* pp = partial + (int64_t)blockIdx.x * 3 * n;
-    for (int i = threadIdx.x; i < 3 * W; i += 256) {
-        const int q = i / W, j = i - q * W;
-        if (j < n) pp[q * n + j] = red[(0 * 3 + q) * W + j] + red[(1 * 3 + q) * W + j] + red[(2 * 3 + q) * W + j] +
-                                   red[(3 * 3 + q) * W + j];
-    }
-}
-
-// Rows wider than 1024: same maths, the row is re-read from L1/L2 instead of cached in registers, and
-// the column partials are produced 64 columns at a time.  dz must not alias dy here.
-__global__ void __launch_bounds__(256)
-ln_relu_bwd_wide_kernel(const float* __restrict__ dy, int64_t lddy, const float* __restrict__ z, int64_t ldz,
-                        const float* __restrict__ stats, const float* __restrict__ gamma,
-                        const float* __restrict__ beta, int relu, float* __restrict__ dz, int64_t lddz,
-                        float* __restrict__ partial, int M, int n) {
-    __shared__ float red[3][4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool has_ln = gamma != nullptr;
-    for (int j0 = 0; j0 < n; j0 += 64) {
-        const int j = j0 + lane;
-        const bool jok = j < n;
-        const float gj = (has_ln && jok) ? gamma[j] : 1.f;
-        const float bj = (has_ln && jok) ? beta[j] : 0.f;
-        float s_dg = 0.f, s_db = 0.f, s_dbias = 0.f;
-        for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
-            const float* dyr = dy + (int64_t)row * lddy;
-            const float* zr = z + (int64_t)row * ldz;
-            float* dzr = dz + (int64_t)row * lddz;
-            if (has_ln) {
-                const float mean = stats[row], rstd = stats[M + row];
-                float a = 0.f, b = 0.f;
-                for (int jj = lane; jj < n; jj += 64) {
-                    const float xh = (zr[jj] - mean) * rstd;
-                    float g = dyr[jj];
-                    if (relu && ln_affine(xh, gamma[jj], beta[jj]) <= 0.f) g = 0.f;
-                    const float dxh = g * gamma[jj];
-                    a += dxh;
-                    b = fmaf(dxh, xh, b);
-                }
-                const float c1 = wave_sum(a) / (float)n, c2 = wave_sum(b) / (float)n;
-                if (jok) {
-                    const float xh = (zr[j] - mean) * rstd;
-                    float g = dyr[j];
-                    if (relu && ln_affine(xh, gj, bj) <= 0.f) g = 0.f;
-                    const float d = rstd * (g * gj - c1 - xh * c2);
-                    s_dg = fmaf(g, xh, s_dg);
-                    s_db += g;
-                    s_dbias += d;
-                    dzr[j] = d;
-                }
-            } else if (jok) {
-                float g = dyr[j];
-                if (relu && zr[j] <= 0.f) g = 0.f;
-                s_dbias += g;
-                dzr[j] = g;
-            }
-        }
-        red[0][wave][lane] = s_dg; red[1][wave][lane] = s_db; red[2][wave][lane] = s_dbias;
-        __syncthreads();
-        if (wave == 0 && jok) {
-            float* pp = partial + (int64_t)blockIdx.x * 3 * n;
-#pragma unroll
-            for (int q = 0; q < 3; ++q)
-                pp[q * n + j] = red[q][0][lane] + red[q][1][lane] + red[q][2][lane] + red[q][3][lane];
-        }
-        __syncthreads();
-    }
-}
-
-// fold the block partials: block = 64 columns x 16 slices of the block list; fixed order; WRITES results
-__global__ void __launch_bounds__(1024)
-colsum_fold_kernel(const float* __restrict__ partial, int nblocks, int n, float* __restrict__ dgamma,
-                   float* __restrict__ dbeta, float* __restrict__ dbias) {
-    __shared__ float red[3][16][64];
-    const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int j = blockIdx.x * 64 + lane;
-    float a = 0.f, b = 0.f, c = 0.f;
-    if (j < n) {
-#pragma unroll 4
-        for (int k = slice; k < nblocks; k += 16) {               // 4 x 3 independent loads in flight
-            const float* pp = partial + (int64_t)k * 3 * n;
-            a += pp[j]; b += pp[n + j]; c += pp[2 * n + j];
-        }
-    }
-    red[0][slice][lane] = a; red[1][slice][lane] = b; red[2][slice][lane] = c;
-    __syncthreads();
-    if (slice < 3 && j < n) {
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) s += red[slice][k][lane];
-        float* dst = slice == 0 ? dgamma : slice == 1 ? dbeta : dbias;
-        if (dst) dst[j] = s;
-    }
-}
-
-int ln_bwd_blocks(int64_t M) {
-    static const int forced = GTE_MEASURE_INT("GTE_LNB_BLOCKS", 0);
-    const int cap = forced > 0 ? forced : LNB_MAX_BLOCKS;
-    const int64_t b = gte::ceil_div(M, 4);
-    return (int)(b < cap ? b : cap);
-}
-
 // ---- short-K layer (BBOX features: 13 + 13 inputs): linear + bias + LayerNorm + ReLU in ONE pass ------------------------
 // z[r, :] = a1[r, 0:k1] W[:, 0:k1]^T + a2[r, 0:k2] W[:, k1:K]^T + bias,   K = k1 + k2 <= 64, n_out % 4 == 0, n_out <= 256.
 // As a tiled MFMA GEMM this shape is all fixed cost (one K stage per tile: 20.8 us at 24.5 k x 256, K = 26) and the LayerNorm
@@ -1517,7 +918,7 @@ int ln_bwd_blocks(int64_t M) {
 // ([64][Kp], Kp = K rounded up to 4, padding zero) are staged in LDS once -- every global latency of the workgroup is paid in
 // that prologue; lane l owns output columns 4 l .. 4 l + 3 of four rows at a time, a k step of four is 4 + 4 ds_read_b128
 // (the input reads are same-address broadcasts) and 32 packed FMAs; LayerNorm statistics, affine and ReLU follow in
-// registers with the arithmetic of ln_relu_fwd_vec_kernel.  HBM-bound in principle (N (K + 2 n_out) 4 bytes = 50 MB at 24.5 k x
+// registers with the arithmetic of ln_relu_fwd_vec_kernel (layernorm.hip).  HBM-bound in principle (N (K + 2 n_out) 4 bytes = 50 MB at 24.5 k x
 // 256); measured 24 us (GEMM + LayerNorm launches: 32 us) -- the per-workgroup transposing fill of W^T (each of 383
 // workgroups walks all 256 rows of W) and the short dependent phases of a 16-rows-per-wave workgroup are what is left.
 constexpr int SMALLK_MAX = 64;
@@ -1654,22 +1055,6 @@ sage_smallk_fwd_kernel(const float* __restrict__ a1, int64_t lda1, int k1, const
 bool smallk_supported(int64_t K, int64_t n_out) {
     static const bool off = GTE_MEASURE_OFF("GTE_SMALLK");
     return !off && K >= 1 && K <= SMALLK_MAX && n_out % 4 == 0 && n_out >= 4 && n_out <= 256;
-}
-
-void launch_ln_fwd(const float* z, int64_t ldz, const float* gamma, const float* beta, float eps, int relu, float* y,
-                   int64_t ldy, float* stats, int64_t M, int64_t n_out, hipStream_t s) {
-    if (n_out % 4 == 0 && n_out >= 128 && n_out <= 512) {          // 16-byte accesses, two rows per wave
-        const dim3 grid((unsigned)gte::ceil_div(M, 8)), block(256);
-        if (n_out <= 256)
-            hipLaunchKernelGGL((ln_relu_fwd_vec_kernel<1>), grid, block, 0, s, z, ldz, gamma, beta, eps, relu, y, ldy, stats, (int)M,
-                               (int)n_out);
-        else
-            hipLaunchKernelGGL((ln_relu_fwd_vec_kernel<2>), grid, block, 0, s, z, ldz, gamma, beta, eps, relu, y, ldy, stats, (int)M,
-                               (int)n_out);
-        return;
-    }
-    hipLaunchKernelGGL(ln_relu_fwd_kernel, dim3((unsigned)gte::ceil_div(M, 4)), dim3(256), 0, s, z, ldz, gamma, beta, eps, relu, y,
-                       ldy, stats, (int)M, (int)n_out);
 }
 
 }  // namespace
@@ -1908,136 +1293,12 @@ static int sage_linear_fwd_impl(const float* a1, int64_t lda1, int64_t k1, const
         return gte::fail(GTE_ERR_UNSUPPORTED, "sage_linear_fwd: z_save without LayerNorm is not supported");
     }
     if (ln) {
-        launch_ln_fwd(zbuf, ldzz, gamma, beta, eps, relu, y, ldy, stats, M, n_out, s);
-        return gte::check_launch("ln_relu_fwd");
+        return gte_ln_relu_fwd(zbuf, ldzz, gamma, beta, eps, relu, y, ldy, stats, M, n_out, stream);       // (layernorm.hip)
     }
     return GTE_OK;
 }
 
 extern "C" int gte_sage_linear_fwd_fuses_ln(int64_t k_total, int64_t n_out) { return smallk_supported(k_total, n_out) ? 1 : 0; }
-
-extern "C" int gte_ln_relu_fwd(const float* z, int64_t ldz, const float* gamma, const float* beta, float eps, int relu,
-                               float* y, int64_t ldy, float* stats, int64_t M, int64_t n_out, void* stream) {
-    if (M < 0 || n_out <= 0 || M > INT32_MAX || n_out > INT32_MAX)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_fwd: bad sizes");
-    if (M == 0) return GTE_OK;
-    if (!z || !y || !gamma || !beta) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_fwd: null pointer");
-    if (ldz < n_out || ldy < n_out) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_fwd: ld < n_out");
-    launch_ln_fwd(z, ldz, gamma, beta, eps, relu, y, ldy, stats, M, n_out, gte::as_stream(stream));
-    return gte::check_launch("ln_relu_fwd");
-}
-
-// ... any width up to 1024 on PADDED rows (ldz, ldy >= n_out rounded up to 4), y as fp32 (nullable) and / or as a P3 image
-// (nullable): the LayerNorm(+ReLU) of an aggregate-first planes layer, whose output feeds the next layer's planes GEMM
-extern "C" int gte_ln_relu_fwd_p3(const float* z, int64_t ldz, const float* gamma, const float* beta, float eps, int relu,
-                                  float* y, int64_t ldy, void* yp3, int64_t ldyp3, float* stats, int64_t M, int64_t n_out,
-                                  void* stream) {
-    if (M < 0 || n_out <= 0 || M > INT32_MAX || n_out > 1024)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_fwd_p3: bad sizes (n_out <= 1024)");
-    if (M == 0) return GTE_OK;
-    if (!z || !gamma || !beta || (!y && !yp3)) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_fwd_p3: null pointer");
-    const int64_t n4 = gte::round_up(n_out, 4);
-    if (ldz < n4 || (y && ldy < n4) || (yp3 && (ldyp3 < p3::row_bytes(n_out) || ldyp3 % 16 != 0)))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_fwd_p3: rows must be padded to a multiple of 4 floats; ldp >= 96 ceil(n_out / 16)");
-    hipStream_t s = gte::as_stream(stream);
-    char* yp = reinterpret_cast<char*>(yp3);
-    const int64_t n16 = gte::round_up(n_out, 16);
-#define GTE_LNF(NV, RF)                                                                                                      \
-    hipLaunchKernelGGL((ln_relu_fwd_gen_kernel<NV, RF>), dim3((unsigned)gte::ceil_div(M, 4 * RF)), dim3(256), 0, s, z, ldz, gamma, beta, \
-                       eps, relu, y, ldy, yp, ldyp3, stats, (int)M, (int)n_out)
-    if (n16 <= 256) GTE_LNF(1, 2); else if (n16 <= 512) GTE_LNF(2, 2); else if (n16 <= 768) GTE_LNF(3, 1); else GTE_LNF(4, 1);
-#undef GTE_LNF
-    return gte::check_launch("ln_relu_fwd_p3");
-}
-
-extern "C" int64_t gte_ln_relu_bwd_workspace_bytes(int64_t M, int64_t n_out) {
-    return gte::round_up((int64_t)ln_bwd_blocks(M > 0 ? M : 1) * 3 * (n_out > 0 ? n_out : 1) * 4, 256);
-}
-
-static int ln_relu_bwd_impl(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* stats,
-                            const float* gamma, const float* beta, int relu, float* dz, int64_t lddz,
-                            float* dgamma, float* dbeta, float* dbias, int64_t M, int64_t n_out, void* workspace,
-                            int64_t workspace_bytes, void* stream, char* dzp3, int64_t ldp3) {
-    if (M < 0 || n_out <= 0 || M > INT32_MAX || n_out > INT32_MAX)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd: bad sizes");
-    if (M == 0) return GTE_OK;
-    if (!dy || !dz || !workspace) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd: null pointer");
-    if ((gamma || relu) && !z) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd: z is required");
-    if (gamma && (!beta || !stats)) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd: LayerNorm needs beta and stats");
-    if (gamma && n_out > 1024 && dz == dy)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd: dz must not alias dy when n_out > 1024 with LayerNorm");
-    if (workspace_bytes < gte_ln_relu_bwd_workspace_bytes(M, n_out))
-        return gte::fail(GTE_ERR_WORKSPACE_TOO_SMALL, "ln_relu_bwd: workspace too small");
-    hipStream_t s = gte::as_stream(stream);
-    const int nb = ln_bwd_blocks(M);
-    const float* zz = z ? z : dy;
-    const int64_t ldzz = z ? ldz : lddy;
-    float* part = reinterpret_cast<float*>(workspace);
-    dim3 grid((unsigned)nb), block(256);
-#define GTE_LNB(NCH)                                                                                              \
-    hipLaunchKernelGGL((ln_relu_bwd_kernel<NCH>), grid, block, (size_t)(4 * 3 * NCH * 64) * sizeof(float), s, dy, lddy, \
-                       zz, ldzz, stats, gamma, beta, relu, dz, lddz, part, (int)M, (int)n_out)
-#define GTE_LNV(NV)                                                                                                 \
-    hipLaunchKernelGGL((ln_relu_bwd_vec_kernel<NV>), grid, block, (size_t)(4 * 3 * NV * 256) * sizeof(float), s, dy, lddy, \
-                       zz, ldzz, stats, gamma, beta, relu, dz, lddz, part, (int)M, (int)n_out, dzp3, ldp3)
-    if (dzp3 && (ldp3 < p3::row_bytes(n_out) || ldp3 % 16 != 0))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd: the P3 image needs ldp >= 96 ceil(n_out / 16)");
-    if (dzp3 && !(n_out % 16 == 0 && n_out >= 128 && n_out <= 512)) {
-        // any other width up to 1024 with the image: padded rows (ld >= n_out rounded up to 4), LayerNorm layers only
-        const int64_t n4 = gte::round_up(n_out, 4);
-        if (!gamma || n_out > 1024 || lddy < n4 || ldzz < n4 || lddz < n4)
-            return gte::fail(GTE_ERR_UNSUPPORTED, "ln_relu_bwd: the P3 image at this width needs LayerNorm, n_out <= 1024 and rows padded "
-                                                  "to a multiple of 4 floats");
-#define GTE_LNG(NV, RF)                                                                                                  \
-    hipLaunchKernelGGL((ln_relu_bwd_gen_kernel<NV, RF>), grid, block, (size_t)(4 * 3 * NV * 256) * sizeof(float), s, dy, lddy, \
-                       zz, ldzz, stats, gamma, beta, relu, dz, lddz, part, (int)M, (int)n_out, dzp3, ldp3)
-        const int64_t n16 = gte::round_up(n_out, 16);
-        if (n16 <= 256) GTE_LNG(1, 2); else if (n16 <= 512) GTE_LNG(2, 2); else if (n16 <= 768) GTE_LNG(3, 1); else GTE_LNG(4, 1);
-#undef GTE_LNG
-    } else
-    if (n_out % 4 == 0 && n_out >= 128 && n_out <= 512) {              // 16-byte accesses
-        if (n_out <= 256) GTE_LNV(1); else GTE_LNV(2);
-    } else
-    if (n_out <= 64) GTE_LNB(1);
-    else if (n_out <= 128) GTE_LNB(2);
-    else if (n_out <= 256) GTE_LNB(4);
-    else if (n_out <= 512) GTE_LNB(8);
-    else if (n_out <= 1024) GTE_LNB(16);
-    else
-        hipLaunchKernelGGL(ln_relu_bwd_wide_kernel, grid, block, 0, s, dy, lddy, zz, ldzz, stats, gamma, beta, relu, dz,
-                           lddz, part, (int)M, (int)n_out);
-#undef GTE_LNB
-#undef GTE_LNV
-    if (dgamma || dbeta || dbias) {
-        // deferred (gte_fold_defer_begin): the three column sums join the step's fold batch
-        if (gte::defer_fold(part, 3 * n_out, nb, 1, (int)n_out, dgamma, n_out)) {
-            gte::defer_fold(part + n_out, 3 * n_out, nb, 1, (int)n_out, dbeta, n_out);
-            gte::defer_fold(part + 2 * n_out, 3 * n_out, nb, 1, (int)n_out, dbias, n_out);
-        } else {
-            hipLaunchKernelGGL(colsum_fold_kernel, dim3((unsigned)gte::ceil_div(n_out, 64)), dim3(1024), 0, s, part, nb,
-                               (int)n_out, dgamma, dbeta, dbias);
-        }
-    }
-    return gte::check_launch("ln_relu_bwd");
-}
-
-extern "C" int gte_ln_relu_bwd(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* stats,
-                               const float* gamma, const float* beta, int relu, float* dz, int64_t lddz,
-                               float* dgamma, float* dbeta, float* dbias, int64_t M, int64_t n_out, void* workspace,
-                               int64_t workspace_bytes, void* stream) {
-    return ln_relu_bwd_impl(dy, lddy, z, ldz, stats, gamma, beta, relu, dz, lddz, dgamma, dbeta, dbias, M, n_out, workspace,
-                            workspace_bytes, stream, nullptr, 0);
-}
-
-// ... dz additionally as a P3 image (csrc/p3.h): the A operand of the layer's dX / dW planes GEMMs
-extern "C" int gte_ln_relu_bwd_p3(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* stats,
-                                  const float* gamma, const float* beta, int relu, float* dz, int64_t lddz, void* dzp3,
-                                  int64_t ldp3, float* dgamma, float* dbeta, float* dbias, int64_t M, int64_t n_out,
-                                  void* workspace, int64_t workspace_bytes, void* stream) {
-    if (!dzp3) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "ln_relu_bwd_p3: null image");
-    return ln_relu_bwd_impl(dy, lddy, z, ldz, stats, gamma, beta, relu, dz, lddz, dgamma, dbeta, dbias, M, n_out, workspace,
-                            workspace_bytes, stream, reinterpret_cast<char*>(dzp3), ldp3);
-}
 
 extern "C" int gte_sage_linear_fwd(const float* a1, int64_t lda1, int64_t k1, const float* a2, int64_t lda2,
                                    int64_t k2, const float* W, int64_t ldw, const float* bias, const float* gamma,

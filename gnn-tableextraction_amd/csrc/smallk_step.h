@@ -1,7 +1,7 @@
 // One step of the short-input layer's backward (gte_sage_smallk_bwd; also the epilogue of gte_gemm_p3_nt_smallk_bwd): ROWS rows of
 // one wave, lane l = output columns 4 l .. 4 l + 3.  z = [x | ahn] W^T + b is RECOMPUTED with the forward kernel's instruction
 // sequence (sage_smallk_fwd_kernel: bit-identical z, the ReLU mask cannot flip), then the LayerNorm(+ReLU) backward of the rows
-// (the arithmetic of ln_relu_bwd_vec_kernel) and dW[j + e][k] += dz[r][j + e] xin[r][k]; dz never leaves the registers.
+// (the arithmetic of ln_relu_bwd_vec_kernel, layernorm.hip) and dW[j + e][k] += dz[r][j + e] xin[r][k]; dz never leaves the registers.
 //   xq: the rows' inputs in LDS ([row][Kp], columns K .. Kp-1 zero);  wl: W^T in LDS ([Kp][ns]) + this lane's column offset.
 #pragma once
 #include "gte_common.h"

@@ -8,8 +8,9 @@ R, the row-sum depth of a kernel family: the number of float32 additions an elem
 Every kernel sums a lane's elements in a chain and the lanes in a tree:
   scalar   ln_relu_fwd_kernel, ln_relu_bwd_kernel<NCH>, ln_relu_bwd_wide_kernel: lane l owns columns l + 64 t, a chain of
            ceil(n / 64) terms, then the 6-level wave tree:                                     R = ceil(n / 64) - 1 + 6
-  vec      ln_relu_fwd_vec_kernel, the gen kernels, the backward vec / gen kernels: lane l owns the four columns 4 (l + 64 v) .. + 3
-           for every v, a chain of 4 ceil(n / 256) terms, the same tree:                       R = 4 ceil(n / 256) - 1 + 6
+  vec      ln_relu_fwd_vec_kernel<NV, RF, MSK> (both forms: per-chunk validity at n % 4 == 0, per-element validity on padded rows),
+           ln_relu_bwd_vec_kernel<NV> and ln_relu_bwd_gen_kernel<NV, RF> (the same two forms as two kernels): lane l owns the
+           four columns 4 (l + 64 v) .. + 3 for every v, a chain of 4 ceil(n / 256) terms, the same tree:                       R = 4 ceil(n / 256) - 1 + 6
   spmm     the LNE epilogue of spmm_csr.hip at (G, CPL): 4 CPL terms per lane, log2 G tree levels
   narrow   the LNF kernels of narrow_layer.hip: groups of four ((x + y) + (z + w), 2 levels) in a chain, then cross-lane adds.  The
            256-thread kernel (n % 16 != 0): n / 8 groups, one add: R = n / 8 + 3; the 512-thread kernel: n / 16 groups, two adds:
@@ -90,8 +91,8 @@ def depth(family, n, g=64, cpl=1):
 
 
 def standalone_family(n, image):
-    """row-sum family of the stand-alone kernel that runs width n, forward and backward alike (launch_ln_fwd, ln_relu_bwd_impl of
-    sage_linear.hip): the entry points with a P3 image run the vec / gen kernels, the others the vec kernels at n % 4 == 0 in
+    """row-sum family of the stand-alone kernel that runs width n, forward and backward alike (gte_ln_relu_fwd(_p3), ln_relu_bwd_impl
+    of layernorm.hip): the entry points with a P3 image run the 16-byte (vec) kernels at every width, the others at n % 4 == 0 in
     128 .. 512 and the scalar kernels elsewhere"""
     return "vec" if image or (n % 4 == 0 and 128 <= n <= 512) else "scalar"
 

@@ -2,9 +2,9 @@
 
 Why the masks: a LayerNorm output within rounding of zero can get a different ReLU decision on the device than in any host
 re-computation, and then one (node, feature) of the backward differs by a whole contribution.  The device's backward decides
-the mask at exactly one formula, ``fmaf((z - mean) * rstd, gamma, beta) <= 0.f`` with contraction off (csrc/gte_common.h
-gte_ln_bwd_pre4 / _pre4m -- the planes NT GEMM's LayerNorm-backward epilogue and the narrow layer's fused backward share it --,
-csrc/sage_linear.hip ln_relu_bwd kernels, csrc/smallk_step.h), from the step's pre-LayerNorm ``z`` and its row statistics
+the mask at exactly one formula, ``fmaf((z - mean) * rstd, gamma, beta) <= 0.f`` with contraction off (csrc/layernorm.h
+gte_ln_bwd_pre4 / _pre4m -- ln_relu_bwd_vec_kernel, the planes NT GEMM's LayerNorm-backward epilogue and the narrow layer's fused
+backward share it --, the scalar ln_relu_bwd kernels of csrc/layernorm.hip, csrc/smallk_step.h), from the step's pre-LayerNorm ``z`` and its row statistics
 ``stats`` = [mean[0:n] | rstd[0:n]].  Both stay in the step's buffers after the step (dz is formed in ``dy``), so the host
 reproduces the decision bit for bit: xh = fp32(fp32(z - mean) * rstd), and the sign of xh * gamma + beta taken in float64 is the
 sign of the fma (the product of two fp32 values is exact in float64; rounding keeps the sign).  A float64 oracle run with those

@@ -12,7 +12,7 @@ breaks them by more than 10x on these inputs.
               of the sum of their absolute terms
 with u = 2^-24 and (D, Dm, Dr, Db) = (2.5 R + 12, R + 2, R / 2 + 5, 2 R + 22) for a row-sum depth R.
 
-ReLU masks: the backward kernels rebuild xhat from the STORED mean and rstd, the gen forward (and the planes-GEMM epilogue) use
+ReLU masks: the backward kernels rebuild xhat from the STORED mean and rstd, the 16-byte forward (and the planes-GEMM epilogue) use
 fma(-1 / n, sum, z); the two differ by about kappa u, so the masks can differ within the ambiguous band (|pre| <= 2 forward bounds).
 The tests give those elements dy = 0 (at most 1 % of a case, asserted), print how many there are, and require the forward's y > 0 to
 be the reference mask everywhere else.  The backward's mask is, by convention, the one on the stored stats (include/gte.h).  Exact
@@ -30,8 +30,9 @@ Largest error / bound ratios measured on an MI355X (all cases of this module):
 (rstd near 1 is the constant row 1000 at eps = 1e-12, where the bound's min(1, .) term is at its cap: the mean's rounding IS the
 variance there.)  Largest neutralised share of a case 0.50 %.  Forward and backward masks differed at 589 (fwd / bwd) and 6641
 (fwd_p3 / bwd_p3) of some 2.5 million elements each, every one inside the ambiguous band and all but 2 on constant rows, where xhat is
-rounding noise in both kernels; the vector forward (n = 252, 260) differs from the stored-mean form as the gen forward does, the scalar
-forward does not.  No kernel broke a bound, so none was changed.
+rounding noise in both kernels; the 16-byte forward differs from the stored-mean form in both of its forms (per-chunk validity at
+n = 252, 260 as much as per-element validity on padded rows: one body, ln_relu_fwd_vec_kernel<NV, RF, MSK> of csrc/layernorm.hip), the
+scalar forward does not.  No kernel broke a bound, so none was changed.
 """
 import numpy as np
 import pytest
@@ -49,7 +50,7 @@ NAN = float("nan")
 
 PLAIN_NS = sorted(set(lc.FWD_SCALAR_NS + lc.FWD_VEC_NS + lc.BWD_NCH_NS + lc.BWD_VEC_NS + lc.BWD_WIDE_NS))
 PLAIN_BIG = {65, 129, 256}                   # M_BIG at one width per backward kernel family: scalar NCH<2>, NCH<4>, vec
-IMAGE_NS = sorted(set(lc.GEN_NS + [128]))    # (128: the backward vec kernel with an image next to the gen forward)
+IMAGE_NS = sorted(set(lc.GEN_NS + [128]))    # (128: the backward's per-chunk form with an image next to the per-element forward)
 IMAGE_BIG = {218}
 
 
@@ -246,11 +247,57 @@ def test_ln_relu_fwd_and_bwd_on_ill_conditioned_rows(n):
 
 @pytest.mark.parametrize("n", IMAGE_NS)
 def test_ln_relu_fwd_p3_and_bwd_p3_on_ill_conditioned_rows(n):
-    """gte_ln_relu_fwd_p3 (gen kernel, every (NV, RF)) and gte_ln_relu_bwd_p3 (gen kernel; vector kernel with an image at n % 16 == 0 in
-    128 .. 512) on padded rows"""
+    """gte_ln_relu_fwd_p3 (the MSK form of the 16-byte kernel, every (NV, RF)) and gte_ln_relu_bwd_p3 (gen kernel; vec kernel with an
+    image at n % 16 == 0 in 128 .. 512) on padded rows"""
     for case in lc.cases([n], n if n in IMAGE_BIG else None):
         for relu in (True, False):
             check_standalone(case, True, relu)
+
+
+# ------------------------------------------------------------------------------------------------ plain against image entry points
+SAME_BITS_NS = [128, 132, 252, 256, 260, 500, 512]     # multiples of 4 in 128 .. 512, both sides of the NV step, some multiples of 16
+SAME_BITS_MS = [1, 3, 9]
+SAME_BITS_BIG = 260
+
+
+def same_bits_plants(m):
+    """row -> kind so that every kind of layernorm_cases.KINDS is planted at every row count, with ordinary rows in between"""
+    if m > 9:
+        return lc.variants(m)                          # (every kind in one matrix)
+    rows = list(range(0, m, 2))
+    return [dict(zip(rows, lc.KINDS[i:i + len(rows)])) for i in range(0, len(lc.KINDS), len(rows))]
+
+
+@pytest.mark.parametrize("n", SAME_BITS_NS)
+def test_plain_and_image_entry_points_agree_bit_for_bit(n):
+    """gte_ln_relu_fwd against gte_ln_relu_fwd_p3 and gte_ln_relu_bwd against gte_ln_relu_bwd_p3 on the same padded rows: the same y,
+    stats, dz and column sums to the bit at every width both accept.  At n % 16 == 0 both backward entry points launch the same
+    instantiation; elsewhere the plain entry runs the per-chunk-mask kernel and the image entry the per-element-mask kernel.  The forward
+    is one body with both forms (csrc/layernorm.hip); this test holds the forms together in both directions."""
+    ld = n + 4
+    for m in SAME_BITS_MS + ([lc.M_BIG] if n == SAME_BITS_BIG else []):
+        plants = same_bits_plants(m)
+        assert {k for p in plants for k in p.values()} == set(lc.KINDS)
+        for pi, plant in enumerate(plants):
+            rng = np.random.default_rng(31000 + 100 * n + 10 * min(m, 10) + pi)
+            z = lc.plant_rows(rng.standard_normal((m, n)).astype(np.float32), plant, rng)
+            dy = rng.standard_normal((m, n)).astype(np.float32)
+            gamma, beta = lc.make_params(n, rng)
+            gd, bd, zb, gb = dev(gamma), dev(beta), padded(z, ld), padded(dy, ld)
+            eps = (1e-5, 1e-12)[(m + pi) % 2]
+            for relu in (True, False):
+                tag = f"n={n} M={m} plant {pi} relu={int(relu)}"
+                y0, _, st0 = run_fwd(zb, n, gd, bd, eps, relu, False)
+                y1, _, st1 = run_fwd(zb, n, gd, bd, eps, relu, True)
+                assert bool(torch.isfinite(y0[:, :n]).all()) and bool(torch.isfinite(st0).all()), tag
+                assert torch.equal(y0[:, :n], y1[:, :n]), f"y {tag}"
+                assert torch.equal(st0[:m], st1[:m]) and torch.equal(st0[m:], st1[m:]), f"stats {tag}"
+                out0 = run_bwd(gb, zb, st0, n, gd, bd, relu, False)
+                out1 = run_bwd(gb, zb, st0, n, gd, bd, relu, True)
+                assert bool(torch.isfinite(out0[0][:, :n]).all()), tag
+                assert torch.equal(out0[0][:, :n], out1[0][:, :n]), f"dz {tag}"
+                for name, a, b in zip(("dgamma", "dbeta", "dbias"), out0[2:], out1[2:]):
+                    assert torch.equal(a, b), f"{name} {tag}"
 
 
 # ------------------------------------------------------------------------------------------------ the fused forward forms
