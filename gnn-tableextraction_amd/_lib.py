@@ -53,6 +53,15 @@ SIGNATURES = {
     "gte_box_match_max_candidates": (c_int, []),
     "gte_box_match": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p,
                               c_void_p]),
+    "gte_box_match_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
+    # confidence of final layout blocks (csrc/block_scores.hip)
+    "gte_block_scores_max_page_blocks": (c_int, []),
+    "gte_block_scores_max_page_words": (c_int, []),
+    "gte_block_scores_max_classes": (c_int, []),
+    "gte_block_scores_max_categories": (c_int, []),
+    "gte_block_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                 c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     # layout blocks labelled by word vote (csrc/block_vote.hip)
     "gte_block_vote_max_page_blocks": (c_int, []),
     "gte_block_vote_max_categories": (c_int, []),

@@ -4,8 +4,9 @@ Two routes, each an entry point that is three public stages in a row -- host pac
 unpacking -- so that the host stages run (and are tested) without a device, with a CPU oracle in place of the launch:
   ``extract_regions`` = ``region_batches`` -> ``page_regions`` (gte_page_regions[_scored]) -> ``region_tuples``
   ``extract_blocks``  = ``pack_blocks`` -> ``block_vote`` (gte_block_vote) -> ``blocks_to_pages`` (with ``assemble_tables``)
-``regions_json`` / ``regions_gt_json`` / ``blocks_json`` lay the results out as the documents the reference's box-level evaluation
-reads (``utils.metrics.evaluate_regions``).
+                        and, with ``logits``: -> ``pack_final_blocks`` -> ``block_scores`` (gte_block_scores) -> ``attach_block_scores``
+``regions_json`` / ``regions_gt_json`` / ``blocks_json`` / ``blocks_gt_json`` lay the results out as the documents the reference's
+box-level evaluation reads (``utils.metrics.evaluate_regions``; the block documents hold floats: ``float_boxes=True``).
 """
 from __future__ import annotations
 
@@ -465,8 +466,110 @@ def blocks_to_pages(data, batch: BlockBatch, word_block, votes, label, images=No
     return out
 
 
+class BlockScores(NamedTuple):
+    """Result of :func:`block_scores`."""
+    score: torch.Tensor       # float32 [B]  mean over the words that meet the block of their softmax mass on the block's classes; 1.0 without words
+    n_words: torch.Tensor     # int32 [B]    the words that meet the block
+
+
+def category_class_masks(class_category=None, n_cat=13):
+    """uint32 [n_cat]: bit c of mask k is set when ``class_category[c] == k`` (default :data:`DEFAULT_CLASS_CATEGORY`) -- the
+    classes whose softmax mass counts for a block of category k.  TABLE (4) also takes the classes of the column-header,
+    spanning-cell and table-cell categories (7, 8, 10): ``assemble_tables`` merges those blocks into tables and relabels the
+    remaining cell blocks, so a final TABLE block is made of words of these classes.  Host only."""
+    table = np.asarray(DEFAULT_CLASS_CATEGORY if class_category is None else class_category, dtype=np.int64).reshape(-1)
+    if not 1 <= table.size <= 32 or int(n_cat) < 1:
+        raise ValueError(f"category_class_masks: {table.size} classes, n_cat = {n_cat}")
+    masks = np.zeros(int(n_cat), dtype=np.uint32)
+    for c, k in enumerate(table.tolist()):
+        if 0 <= k < masks.size:
+            masks[k] |= np.uint32(1 << c)
+        if k in (_COLH, _SP, _TCELL) and _TABLE < masks.size:
+            masks[_TABLE] |= np.uint32(1 << c)
+    return masks
+
+
+def block_scores(bbox: torch.Tensor, node_off, logits: torch.Tensor, block_box: torch.Tensor, block_off, block_cat: torch.Tensor,
+                 cat_classes) -> BlockScores:
+    """Confidence of final layout blocks (gte_block_scores, one launch).
+
+    ``bbox`` int32 [n, 4] word boxes and ``logits`` float32 [n, C] their logit rows (C <= 16; a row stride is passed on), pages
+    concatenated; ``block_box`` float64 [B, 4] the pages' FINAL blocks in word coordinates, ``block_cat`` int32 [B] their
+    categories; ``cat_classes`` [n_cat] host sequence of class masks (:func:`category_class_masks`); ``node_off`` / ``block_off``
+    host sequences [pages + 1].  A word counts in EVERY block of its page that its rectangle meets (``block_vote``'s closed
+    test); ``score`` = the mean over those words of the softmax mass on the classes of the block's category (2^-19 fixed point:
+    within 2^-18 of the mean; a row with a non-finite logit adds 0), 1.0 for a block no word meets.  Raises ``ValueError`` on
+    shapes, dtypes or offsets that do not fit, ``GteError`` when a page exceeds ``gte_block_scores_max_page_blocks()`` blocks
+    or ``gte_block_scores_max_page_words()`` words.  No synchronisation."""
+    for t in (bbox, logits, block_box, block_cat):
+        _lib.require_device(t, "block_scores")
+    lib, P = _lib.load(), _lib.ptr
+    dev = bbox.device
+    if bbox.dtype != torch.int32 or block_cat.dtype != torch.int32 or block_box.dtype != torch.float64 or logits.dtype != torch.float32:
+        raise ValueError(f"block_scores: bbox {bbox.dtype} and block_cat {block_cat.dtype} must be int32, block_box {block_box.dtype} "
+                         f"float64, logits {logits.dtype} float32")
+    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 or block_cat.dim() != 1 \
+            or block_cat.shape[0] != block_box.shape[0] or logits.dim() != 2 or logits.shape[0] != bbox.shape[0]:
+        raise ValueError(f"block_scores: bbox is {tuple(bbox.shape)}, logits {tuple(logits.shape)}, block_box {tuple(block_box.shape)}, "
+                         f"block_cat {tuple(block_cat.shape)}")
+    if logits.device != dev or block_box.device != dev or block_cat.device != dev:
+        raise ValueError("block_scores: bbox, logits, block_box and block_cat live on different devices")
+    masks = np.ascontiguousarray(np.asarray(cat_classes, dtype=np.uint32).reshape(-1))
+    if not 1 <= logits.shape[1] <= lib.gte_block_scores_max_classes():
+        raise ValueError(f"block_scores: {logits.shape[1]} classes outside 1 .. {lib.gte_block_scores_max_classes()}")
+    if not 1 <= masks.size <= lib.gte_block_scores_max_categories():
+        raise ValueError(f"block_scores: {masks.size} class masks outside 1 .. {lib.gte_block_scores_max_categories()}")
+    n, nb = bbox.shape[0], block_box.shape[0]
+    no, d_no = _lib.partition_offsets(node_off, n, "block_scores: the word offsets", dev)
+    bo, d_bo = _lib.partition_offsets(block_off, nb, "block_scores: the block offsets", dev)
+    if no.size != bo.size:
+        raise ValueError(f"block_scores: offsets of {no.size - 1} / {bo.size - 1} pages do not partition the words and the blocks")
+    pages = no.size - 1
+    if logits.stride(1) != 1 and logits.shape[0] > 0:
+        logits = logits.contiguous()
+    ld = int(logits.stride(0)) if logits.shape[0] > 1 else int(logits.shape[1])
+    bbox, block_box, block_cat = bbox.contiguous(), block_box.contiguous(), block_cat.contiguous()
+    d_masks = torch.from_numpy(masks.view(np.int32)).to(dev)
+    score = torch.empty(nb, dtype=torch.float32, device=dev)
+    n_words = torch.empty(nb, dtype=torch.int32, device=dev)
+    _lib.check(lib.gte_block_scores(P(bbox), P(d_no), P(logits), ld, int(logits.shape[1]), P(block_box), P(d_bo), P(block_cat),
+                                    P(d_masks), masks.size, pages, n, nb, int(np.diff(no).max()) if pages else 0,
+                                    int(np.diff(bo).max()) if pages else 0, P(score), P(n_words), _lib.current_stream()),
+               "gte_block_scores")
+    return BlockScores(score, n_words)
+
+
+class FinalBlocks(NamedTuple):
+    """One launch's worth of :func:`pack_final_blocks`: host arrays, the batch's pages concatenated."""
+    block_box: np.ndarray     # float64 [B, 4] the final blocks in word coordinates (the unscaled block / scale: one float64 division)
+    block_off: np.ndarray     # int64 [pages + 1]
+    block_cat: np.ndarray     # int32 [B]      their categories
+
+
+def pack_final_blocks(pages, scale=0.36, rescaled=True) -> FinalBlocks:
+    """Stage four of :func:`extract_blocks` with ``logits``: the ``'blocks'`` / ``'labels'`` of a batch's page dicts
+    (``blocks_to_pages``) as the arguments of :func:`block_scores`.  The blocks enter as they stand before the rescale divided by
+    ``scale`` -- the operation ``pack_blocks`` applies to the input blocks; ``rescaled`` says that ``blocks_to_pages`` has done
+    that division already (``rescale=True``: the boxes are taken bit for bit)."""
+    boxes = [np.asarray(p['blocks'], dtype=np.float64).reshape(-1, 4) for p in pages]
+    cats = [np.asarray(p['labels'], dtype=np.int32).reshape(-1) for p in pages]
+    box = np.concatenate(boxes) if boxes else np.zeros((0, 4))
+    return FinalBlocks(box if rescaled else box / float(scale), _offsets([b.shape[0] for b in boxes]),
+                       np.concatenate(cats) if cats else np.zeros(0, dtype=np.int32))
+
+
+def attach_block_scores(pages, final: FinalBlocks, score, n_words):
+    """Stage six: the launch's host arrays (``score`` [B], ``n_words`` [B]) onto the batch's page dicts as ``'scores'`` (floats)
+    and ``'n_words'`` (ints) per final block.  Returns ``pages``."""
+    score, n_words = np.asarray(score, dtype=np.float64).reshape(-1), np.asarray(n_words, dtype=np.int64).reshape(-1)
+    for k, p in enumerate(pages):
+        k0, k1 = int(final.block_off[k]), int(final.block_off[k + 1])
+        p['scores'], p['n_words'] = score[k0:k1].tolist(), n_words[k0:k1].tolist()
+    return pages
+
+
 def extract_blocks(data, all_pred, class_category=None, blocks=None, images=None, scale=0.36, rescale=True, batch_pages=64,
-                   device=None):
+                   device=None, logits=None):
     """Page objects by the reference's own route (``get_objects_bboxs``, postprocessing_2.py:197-309): the layout blocks that a
     PDF text extractor delivers for every page are labelled by the vote of the words inside them (``block_vote`` ->
     gte_block_vote: ONE launch per ``batch_pages`` pages, in place of the reference's words x blocks loop in Python), the
@@ -487,28 +590,69 @@ def extract_blocks(data, all_pred, class_category=None, blocks=None, images=None
     ``'headers'`` (never rescaled, as in the reference); ``'word_block'`` the page-local block index of every word or -1;
     ``'votes'`` the input blocks' counters [blocks, categories].
 
-    Out of scope: obtaining the blocks from a PDF (the caller's extractor); block confidences (the reference writes 1.0;
-    ``'votes'`` is there for callers who want a share); feeding the float-valued block document to ``evaluate_regions``, which
-    takes integer boxes."""
+    ``logits`` (device tensor float [all nodes, C <= 16], the pages concatenated in ``data.graphs`` order: what
+    ``predict_resident(return_logits=True)`` returns): every page dict gains ``'scores'`` and ``'n_words'`` per FINAL block, one
+    more launch per batch (``pack_final_blocks`` -> ``block_scores`` -> ``attach_block_scores``): the mean over the words that
+    meet the block -- every block they meet -- of the softmax mass on the classes of the block's category
+    (``category_class_masks(class_category)``), 1.0 (the reference's constant) for a block no word meets.  Without ``logits``
+    nothing changes.  The float-valued document of the result (``blocks_json``) is scored by
+    ``utils.metrics.evaluate_regions(..., float_boxes=True)``.
+
+    Out of scope: obtaining the blocks from a PDF (the caller's extractor)."""
     batches = pack_blocks(data, all_pred, class_category, blocks, images, scale, batch_pages)
+    if logits is not None:
+        total = sum(int(b.node_off[-1]) for b in batches)
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != total:
+            raise ValueError(f"extract_blocks: logits must be a tensor [{total} nodes, classes], got "
+                             f"{tuple(logits.shape) if hasattr(logits, 'shape') else type(logits).__name__}")
     device = _lib.default_device(device)
-    out = []
+    if logits is not None:
+        logits = logits.to(device=device, dtype=torch.float32)
+    out, first = [], 0
     for b in batches:
-        vote = block_vote(torch.from_numpy(b.bbox).to(device), b.node_off, torch.from_numpy(b.word_cat).to(device),
+        d_bbox = torch.from_numpy(b.bbox).to(device)
+        vote = block_vote(d_bbox, b.node_off, torch.from_numpy(b.word_cat).to(device),
                           torch.from_numpy(b.block_box).to(device), b.block_off, n_cat=b.n_cat, double_cat=2)
-        out += blocks_to_pages(data, b, *(t.cpu().numpy() for t in vote), images=images, scale=scale, rescale=rescale)
+        pages = blocks_to_pages(data, b, *(t.cpu().numpy() for t in vote), images=images, scale=scale, rescale=rescale)
+        if logits is not None:
+            final = pack_final_blocks(pages, scale, rescaled=rescale)
+            got = block_scores(d_bbox, b.node_off, logits[first:first + int(b.node_off[-1])], torch.from_numpy(final.block_box).to(device),
+                               final.block_off, torch.from_numpy(final.block_cat).to(device), category_class_masks(class_category, b.n_cat))
+            attach_block_scores(pages, final, *(t.cpu().numpy() for t in got))
+        first += int(b.node_off[-1])
+        out += pages
     return out
 
 
 def blocks_json(data, result):
-    """``{kind_name: {page_name: {'bboxes': [...], 'scores': [1.0, ...]}}}`` of ``extract_blocks``' result: the layout of the
+    """``{kind_name: {page_name: {'bboxes': [...], 'scores': [...]}}}`` of ``extract_blocks``' result: the layout of the
     reference's ``write_json`` (postprocessing_2.py:328-348, its ``ours_bboxs.json``) -- all thirteen lower-case category names
-    as keys, a page only under the kinds it has, coordinates as floats, every score 1.0."""
+    as keys, a page only under the kinds it has, coordinates as floats; a block's score is its confidence where the page carries
+    ``'scores'`` (``extract_blocks(..., logits=...)``) and 1.0, the reference's constant, otherwise."""
     doc = {name: {} for name in CATEGORY_NAMES}
     for i, page in enumerate(result):
         name = str(data.pages[i]['page'])
-        for box, label in zip(page['blocks'], page['labels']):
+        scores = page.get('scores')
+        for j, (box, label) in enumerate(zip(page['blocks'], page['labels'])):
             entry = doc[CATEGORY_NAMES[label]].setdefault(name, {'bboxes': [], 'scores': []})
             entry['bboxes'].append([float(v) for v in box])
-            entry['scores'].append(1.0)
+            entry['scores'].append(1.0 if scores is None else float(scores[j]))
     return doc
+
+
+def blocks_gt_json(data):
+    """``{kind_name: {page_name: [[x0, y0, x1, y1], ...]}}``: the GROUND-TRUTH document of the block route's evaluation from
+    ``data.pages[i]['annotations']``, rows ``[x0, y0, x1, y1, category]`` -- what the reference's ``get_groundtruth_bboxs``
+    (models/evaluate.py:26-62) reads from ``test.json``, here kept per category (its lower-case name, in category order; only the
+    categories that occur).  A page without the key or a row that is no five numbers with a category in 0 .. 12 raises
+    ``ValueError``."""
+    found = {}
+    for i, page in enumerate(data.pages):
+        if 'annotations' not in page:
+            raise ValueError(f"blocks_gt_json: page {i} ({page.get('page')}) carries no 'annotations'")
+        name = str(page['page'])
+        for row in page['annotations']:
+            if len(row) != 5 or int(row[4]) != row[4] or not 0 <= int(row[4]) < len(CATEGORY_NAMES):
+                raise ValueError(f"blocks_gt_json: page {i} ({name}): {row!r} is no [x0, y0, x1, y1, category]")
+            found.setdefault(int(row[4]), {}).setdefault(name, []).append([float(v) for v in row[:4]])
+    return {CATEGORY_NAMES[c]: found[c] for c in sorted(found)}

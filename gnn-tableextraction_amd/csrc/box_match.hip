@@ -18,6 +18,13 @@
 //            per walk with its two bit sets (matched predictions, matched ground truths) in LDS, 256 walks at a time.
 // Every loop bound that stands in front of a barrier is a value all threads read from the same LDS word or argument; the walks
 // diverge, no barrier stands inside them.  Integer outputs only, no float atomics, no allocation, no synchronisation.
+//
+// Two instantiations of the one body, by box type.  int32 boxes (gte_box_match): phase 1 as above.  double boxes
+// (gte_box_match_f64: the block route's document, coordinates / 0.36): the IoU is calc_iou_individual() of metrics.py:20-54 in
+// IEEE double, operation by operation in the reference's order and with contraction OFF -- every intermediate rounds, so the bits
+// depend on both (left alone, the compiler fuses the union's last subtraction into an fma) -- and the launch can write every
+// pair's IoU out, which is how tests/test_gpu_box_match_f64.py checks those bits.  2 x 256 double boxes are exactly the 16 KB of
+// the bit sets; phases 2 and 3 do not know the box type.
 #include "gte_common.h"
 
 #include <cmath>
@@ -34,7 +41,13 @@ static_assert((BM_MAX_CAND & (BM_MAX_CAND - 1)) == 0, "the sort pads to a power 
 static_assert(BM_MAX_BOXES * BM_MAX_BOXES <= 65536, "a pair index is a 16-bit word");
 static_assert(BM_THREADS * 2 * BM_SET_WORDS * 4 >= 2 * BM_MAX_BOXES * 16, "the bit sets reuse the boxes' LDS");
 
+constexpr double BM_MAX_COORD = 16777216.0;            // |v| of a float box: 2^24
 struct Thresholds { double v[BM_MAX_THR]; };
+struct alignas(16) BoxF { double x, y, z, w; };       // a float box (x0, y0, x1, y1): two 16-byte halves
+template <typename T> struct BoxOf;
+template <> struct BoxOf<int32_t> { using type = int4; };
+template <> struct BoxOf<double> { using type = BoxF; };
+static_assert(2 * BM_MAX_BOXES * sizeof(BoxF) <= BM_THREADS * 2 * BM_SET_WORDS * 4, "the float boxes fit the bit sets' LDS");
 
 // (x1 - x0 + 1, y1 - y0 + 1) of a well-formed box whose extents the exact arithmetic covers; (0, 0) otherwise: such a box overlaps
 // nothing
@@ -52,16 +65,40 @@ __device__ __forceinline__ double box_iou(const int4& p, const int4& t) {
     return (double)inter / (double)(ta + pa - inter);
 }
 
+// a float box is well formed when its four values are finite and within +-2^24 and its corners are in order (a NaN fails every
+// comparison); any other box overlaps nothing
+__device__ __forceinline__ bool box_ok(const BoxF& b) {
+    return fabs(b.x) <= BM_MAX_COORD && fabs(b.y) <= BM_MAX_COORD && fabs(b.z) <= BM_MAX_COORD && fabs(b.w) <= BM_MAX_COORD &&
+           b.x <= b.z && b.y <= b.w;
+}
+
+// metrics.py:42-53 on doubles: one rounding per operation, in the reference's order (np.min / np.max of two finite values pick one
+// of them: no rounding)
+__device__ __forceinline__ double box_iou(const BoxF& p, const BoxF& t) {
+#pragma clang fp contract(off)
+    if (t.z < p.x || p.z < t.x || t.w < p.y || p.w < t.y) return 0.0;
+    const double far_x = t.z < p.z ? t.z : p.z, near_x = t.x > p.x ? t.x : p.x;
+    const double far_y = t.w < p.w ? t.w : p.w, near_y = t.y > p.y ? t.y : p.y;
+    const double inter = ((far_x - near_x) + 1.0) * ((far_y - near_y) + 1.0);
+    const double ta = ((t.z - t.x) + 1.0) * ((t.w - t.y) + 1.0);
+    const double pa = ((p.z - p.x) + 1.0) * ((p.w - p.y) + 1.0);
+    return inter / ((ta + pa) - inter);
+}
+
 // list order: IoU descending, then pair index descending
 __device__ __forceinline__ bool cand_before(unsigned long long ia, unsigned pa, unsigned long long ib, unsigned pb) {
     return ia > ib || (ia == ib && pa > pb);
 }
 
-// grid = cells
+// grid = cells.  T = int32_t or double, the boxes' type; iou_out / iou_off: the double instantiation's optional IoU matrices
+template <typename T>
 __global__ void __launch_bounds__(BM_THREADS)
-box_match_kernel(const int32_t* __restrict__ pred_box, const int32_t* __restrict__ pred_off, const int32_t* __restrict__ gt_box,
+box_match_kernel(const T* __restrict__ pred_box, const int32_t* __restrict__ pred_off, const T* __restrict__ gt_box,
                  const int32_t* __restrict__ gt_off, int n_cells, int cap_pred, int cap_gt, Thresholds thr, int n_thr,
-                 int32_t* __restrict__ tp, int32_t* __restrict__ cell_status) {
+                 int32_t* __restrict__ tp, int32_t* __restrict__ cell_status, double* __restrict__ iou_out,
+                 const int64_t* __restrict__ iou_off) {
+    constexpr bool F64 = sizeof(T) == 8;
+    using Box = typename BoxOf<T>::type;
     __shared__ __attribute__((aligned(16))) unsigned long long s_iou[BM_MAX_CAND];       // 32 KB
     __shared__ __attribute__((aligned(16))) int s_scratch[BM_THREADS * 2 * BM_SET_WORDS];   // 16 KB: boxes, then the walks' bit sets
     __shared__ unsigned short s_pair[BM_MAX_CAND];                                       // 8 KB
@@ -76,7 +113,15 @@ box_match_kernel(const int32_t* __restrict__ pred_box, const int32_t* __restrict
         return;
     }
     const int R = r1 - r0 < INT32_MAX ? (int)(r1 - r0) : INT32_MAX, G = g1 - g0 < INT32_MAX ? (int)(g1 - g0) : INT32_MAX;
-    if (R > cap_pred || G > cap_gt || R > BM_MAX_BOXES || G > BM_MAX_BOXES) {             // the caller's maxima were wrong
+    int64_t i0 = 0;
+    bool iou_rows = true;                                 // the cell's IoU matrix has its R x G rows inside [0, iou_off[n_cells]]
+    if constexpr (F64) {
+        if (iou_out) {
+            i0 = iou_off[b];
+            iou_rows = i0 >= 0 && iou_off[b + 1] - i0 == (int64_t)R * G && iou_off[b + 1] <= iou_off[n_cells];
+        }
+    }
+    if (R > cap_pred || G > cap_gt || R > BM_MAX_BOXES || G > BM_MAX_BOXES || !iou_rows) {   // the caller's maxima / offsets were wrong
         for (int64_t i = tid; i < (int64_t)n_thr * R; i += BM_THREADS) tp[(i / R) * r_all + r0 + i % R] = -1;
         if (tid == 0) cell_status[b] = 2;
         return;
@@ -88,10 +133,10 @@ box_match_kernel(const int32_t* __restrict__ pred_box, const int32_t* __restrict
     }
 
     // ---- phase 1 --------------------------------------------------------------------------------------------------------
-    int4* s_pbox = reinterpret_cast<int4*>(s_scratch);
-    int4* s_gbox = s_pbox + BM_MAX_BOXES;
-    for (int i = tid; i < R; i += BM_THREADS) s_pbox[i] = *reinterpret_cast<const int4*>(pred_box + (r0 + i) * 4);
-    for (int i = tid; i < G; i += BM_THREADS) s_gbox[i] = *reinterpret_cast<const int4*>(gt_box + (g0 + i) * 4);
+    Box* s_pbox = reinterpret_cast<Box*>(s_scratch);
+    Box* s_gbox = s_pbox + BM_MAX_BOXES;
+    for (int i = tid; i < R; i += BM_THREADS) s_pbox[i] = *reinterpret_cast<const Box*>(pred_box + (r0 + i) * 4);
+    for (int i = tid; i < G; i += BM_THREADS) s_gbox[i] = *reinterpret_cast<const Box*>(gt_box + (g0 + i) * 4);
     if (tid == 0) s_count = 0;
     if (tid == 0) {
 #pragma unroll
@@ -101,10 +146,14 @@ box_match_kernel(const int32_t* __restrict__ pred_box, const int32_t* __restrict
     const double thr0 = thr.v[0];
     for (int i = tid; i < R * G; i += BM_THREADS) {
         const int p = i / G, g = i - p * G;
-        const int4 pb = s_pbox[p], gb = s_gbox[g];
-        if (!box_ok(pb) || !box_ok(gb)) continue;
-        const double iou = box_iou(pb, gb);
-        if (iou > thr0) {
+        const Box pb = s_pbox[p], gb = s_gbox[g];
+        const bool ok = box_ok(pb) && box_ok(gb);
+        const double iou = ok ? box_iou(pb, gb) : 0.0;
+        if constexpr (F64) {
+            if (iou_out) iou_out[i0 + i] = iou;           // every pair, whatever the thresholds
+            if (!isfinite(iou)) continue;                 // a non-finite quotient is no candidate
+        }
+        if (ok && iou > thr0) {
             const unsigned slot = atomicAdd(&s_count, 1u);
             if (slot < (unsigned)BM_MAX_CAND) {
                 s_iou[slot] = (unsigned long long)__double_as_longlong(iou);
@@ -176,29 +225,50 @@ box_match_kernel(const int32_t* __restrict__ pred_box, const int32_t* __restrict
 extern "C" int gte_box_match_max_boxes(void) { return BM_MAX_BOXES; }
 extern "C" int gte_box_match_max_candidates(void) { return BM_MAX_CAND; }
 
-extern "C" int gte_box_match(const int32_t* pred_box, const int32_t* pred_off, const int32_t* gt_box, const int32_t* gt_off,
-                             int64_t n_cells, int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr,
-                             int32_t* tp, int32_t* cell_status, void* stream) {
+namespace {
+
+// the checks and the launch of both entries (double boxes: + the two IoU arguments)
+template <typename T>
+int box_match_launch(const char* what, const T* pred_box, const int32_t* pred_off, const T* gt_box, const int32_t* gt_off, int64_t n_cells,
+                     int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr, int32_t* tp,
+                     int32_t* cell_status, double* iou, const int64_t* iou_off, void* stream) {
     if (n_cells < 0 || n_cells >= INT32_MAX || max_pred_per_cell < 0 || max_gt_per_cell < 0)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "box_match: bad sizes");
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: bad sizes", what);
     if (n_thr < 1 || n_thr > BM_MAX_THR)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "box_match: %d thresholds (1 .. %d)", n_thr, BM_MAX_THR);
-    if (!iou_thr) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "box_match: null pointer");
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: %d thresholds (1 .. %d)", what, n_thr, BM_MAX_THR);
+    if (!iou_thr) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
     Thresholds thr{};
     for (int j = 0; j < n_thr; ++j) {
         thr.v[j] = iou_thr[j];
         if (!std::isfinite(thr.v[j]) || thr.v[j] < 0.0 || (j > 0 && thr.v[j] < thr.v[j - 1]))
-            return gte::fail(GTE_ERR_INVALID_ARGUMENT, "box_match: the thresholds must be finite, >= 0 and ascending");
+            return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: the thresholds must be finite, >= 0 and ascending", what);
     }
     if (max_pred_per_cell > BM_MAX_BOXES || max_gt_per_cell > BM_MAX_BOXES)
-        return gte::fail(GTE_ERR_UNSUPPORTED, "box_match: a cell of %lld x %lld boxes exceeds %d a side", (long long)max_pred_per_cell,
+        return gte::fail(GTE_ERR_UNSUPPORTED, "%s: a cell of %lld x %lld boxes exceeds %d a side", what, (long long)max_pred_per_cell,
                          (long long)max_gt_per_cell, BM_MAX_BOXES);
     if (n_cells == 0) return GTE_OK;
-    if (!pred_off || !gt_off || !cell_status || (max_pred_per_cell > 0 && (!pred_box || !tp)) || (max_gt_per_cell > 0 && !gt_box))
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "box_match: null pointer");
-    if ((((uintptr_t)pred_box | (uintptr_t)gt_box) & 15) != 0)
-        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "box_match: pred_box and gt_box must be 16-byte aligned");
-    hipLaunchKernelGGL(box_match_kernel, dim3((unsigned)n_cells), dim3(BM_THREADS), 0, gte::as_stream(stream), pred_box, pred_off, gt_box,
-                       gt_off, (int)n_cells, (int)max_pred_per_cell, (int)max_gt_per_cell, thr, n_thr, tp, cell_status);
-    return gte::check_launch("box_match");
+    if (!pred_off || !gt_off || !cell_status || (max_pred_per_cell > 0 && (!pred_box || !tp)) || (max_gt_per_cell > 0 && !gt_box) ||
+        (iou && !iou_off))
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
+    if ((((uintptr_t)pred_box | (uintptr_t)gt_box) & 15) != 0 || ((uintptr_t)iou & 7) != 0 || ((uintptr_t)iou_off & 7) != 0)
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: pred_box and gt_box must be 16-byte aligned (iou and iou_off 8-byte)", what);
+    hipLaunchKernelGGL(box_match_kernel<T>, dim3((unsigned)n_cells), dim3(BM_THREADS), 0, gte::as_stream(stream), pred_box, pred_off, gt_box,
+                       gt_off, (int)n_cells, (int)max_pred_per_cell, (int)max_gt_per_cell, thr, n_thr, tp, cell_status, iou, iou_off);
+    return gte::check_launch(what);
+}
+
+}  // namespace
+
+extern "C" int gte_box_match(const int32_t* pred_box, const int32_t* pred_off, const int32_t* gt_box, const int32_t* gt_off,
+                             int64_t n_cells, int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr,
+                             int32_t* tp, int32_t* cell_status, void* stream) {
+    return box_match_launch<int32_t>("box_match", pred_box, pred_off, gt_box, gt_off, n_cells, max_pred_per_cell, max_gt_per_cell, iou_thr,
+                                     n_thr, tp, cell_status, nullptr, nullptr, stream);
+}
+
+extern "C" int gte_box_match_f64(const double* pred_box, const int32_t* pred_off, const double* gt_box, const int32_t* gt_off,
+                                 int64_t n_cells, int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr,
+                                 int32_t* tp, int32_t* cell_status, double* iou, const int64_t* iou_off, void* stream) {
+    return box_match_launch<double>("box_match_f64", pred_box, pred_off, gt_box, gt_off, n_cells, max_pred_per_cell, max_gt_per_cell,
+                                    iou_thr, n_thr, tp, cell_status, iou, iou_off, stream);
 }

@@ -23,6 +23,7 @@
 // softmax mass its logits give to the classes of its own kind, in 2^-19 fixed point, to one more LDS word of its root (an integer
 // add: the sum does not depend on the arrival order), and the root row receives the mean.  Everything else is the one body.
 #include "gte_common.h"
+#include "word_score.h"
 
 #include <atomic>
 #include <climits>
@@ -40,34 +41,12 @@ constexpr int region_node_bytes(bool scored) { return REGION_NODE_BYTES + (score
 constexpr int REGION_LDS_MAX = REGION_PAGE_MAX * REGION_NODE_BYTES + REGION_TAIL_BYTES;      // 114 704 of the CU's 160 KB
 constexpr int REGION_LDS_MAX_SCORED = REGION_PAGE_MAX * region_node_bytes(true) + REGION_TAIL_BYTES;      // 131 088
 static_assert(REGION_LDS_MAX_SCORED <= 160 * 1024, "a page of REGION_PAGE_MAX nodes must fit the CU's LDS");
-// q(v) = p(v) * 2^19 rounded: a page has <= 4096 = 2^12 words and p <= 1, so a root's sum is <= 2^31 -- an unsigned 32-bit word
-constexpr float REGION_SCORE_ONE = 524288.0f;
-static_assert((uint64_t)REGION_PAGE_MAX * (uint64_t)REGION_SCORE_ONE <= 0xFFFFFFFFull, "the fixed-point sum must fit 32 bits");
+// (the fixed-point word score q(v) = p(v) * 2^19 rounded and its 32-bit sum bound: word_score.h)
+constexpr float REGION_SCORE_ONE = GTE_SCORE_ONE;
+static_assert(REGION_PAGE_MAX <= GTE_SCORE_PAGE_MAX, "the fixed-point sum must fit 32 bits");
 
 __device__ __forceinline__ int lds_get(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void lds_put(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-// p(v) in 2^-19 fixed point: the fp32 max-subtracted softmax mass of row `lg` on the classes c with class_group[c] == kind; 0 for
-// a row with a non-finite logit.  den and num take the same terms in the same order, so num <= den and p == 1 exactly where
-// every class is of the kind.
-__device__ __forceinline__ unsigned region_word_score(const float* __restrict__ lg, int n_classes,
-                                                      const int32_t* __restrict__ class_group, int kind) {
-    float m = lg[0];
-    bool finite = isfinite(m);
-    for (int c = 1; c < n_classes; ++c) {
-        const float x = lg[c];
-        finite = finite && isfinite(x);
-        m = fmaxf(m, x);
-    }
-    if (!finite) return 0u;
-    float den = 0.f, num = 0.f;
-    for (int c = 0; c < n_classes; ++c) {
-        const float e = expf(lg[c] - m);
-        den += e;
-        if (class_group[c] == kind) num += e;
-    }
-    return (unsigned)((num / den) * REGION_SCORE_ONE + 0.5f);      // den >= exp(0) = 1
-}
 
 // grid = pages.  cap = the caller's max_page_nodes (the LDS the launch carries).
 template <bool SCORED>

@@ -161,9 +161,19 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
     return (pred, all_logits) if return_logits else pred
 
 
-def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False, blocks=False):
+def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False, blocks=False,
+         block_scores=False, block_eval=False):
     """``blocks=True``: the result gains ``'blocks'`` = ``extract_blocks(data, all_pred)`` (the pages carry their layout blocks
     as ``data.pages[i]['blocks']``), and with ``save_predictions`` ``{output}/blocks/{logs}.json`` is written (``blocks_json``).
+
+    ``block_scores=True`` (implies ``blocks``): ``extract_blocks(..., logits=...)`` -- every page of ``'blocks'`` gains
+    ``'scores'`` and ``'n_words'`` per final block (gte_block_scores, from the model's own logits), and the JSON carries these
+    scores in place of 1.0.
+
+    ``block_eval`` (implies ``block_scores``): ``True`` -- the ground truth is ``blocks_gt_json(data)``, the pages carry
+    ``'annotations'`` -- or a ground-truth document ``{kind: {page: [box, ...]}}``.  The result gains ``'block_eval'`` =
+    ``evaluate_regions(blocks_json(...), gt, float_boxes=True)``: the reference's AP at IoU 0.50 .. 0.95 of the document it
+    evaluates itself (models/evaluate.py:64-131).
 
     ``regions=True``: the result gains ``'regions'`` (``extract_regions`` of the predictions: per page a list of
     ``(group, [x0, y0, x1, y1], n_words)``), and with ``save_predictions`` ``{output}/regions/{logs}.json`` is written
@@ -177,6 +187,10 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
     labels)``: the only box-level ground truth that pre-built pages carry) -- the reference's AP at IoU 0.50 .. 0.95 and mAP."""
     region_scores = bool(region_scores or box_eval)
     regions = bool(regions or region_scores)
+    want_block_eval = block_eval is not False and block_eval is not None
+    block_scores = bool(block_scores or want_block_eval)
+    blocks = bool(blocks or block_scores)
+    want_logits = region_scores or block_scores
     if not (config.TRAINING.gpu >= 0 and torch.cuda.is_available()):
         raise RuntimeError("model_predict runs on the MI355X HIP path only (no CPU fallback)")
     device = torch.device('cuda', config.TRAINING.gpu)
@@ -208,8 +222,8 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
         # forward (predict_resident); one device -> host copy of all predictions at the end
         from .loop import BatchPipeline
         pipe = BatchPipeline(G.ResidentPages(data.graphs, device))
-        flat_pred = predict_resident(engine, pipe, bs, return_logits=region_scores)
-        if region_scores:
+        flat_pred = predict_resident(engine, pipe, bs, return_logits=want_logits)
+        if want_logits:
             flat_pred, flat_logits = flat_pred
         flat_pred = flat_pred.cpu().numpy()
     else:
@@ -217,7 +231,7 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
         with torch.no_grad():
             for b0 in range(0, len(data.graphs), bs):
                 logits = model(G.batch([g.to(device) for g in data.graphs[b0:b0 + bs]]))
-                if region_scores:
+                if want_logits:
                     kept.append(logits.float().clone())
                 preds.append(logits.argmax(dim=1).cpu().numpy())
         flat_pred = np.concatenate(preds)
@@ -256,9 +270,9 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
             pickle.dump({'all_pred': [a.tolist() for a in all_pred], 'num_nodes': [len(a) for a in all_pred]}, f)
     result = {'accuracy': acc, 'accuracy_nodes': acc_nodes, 'precision': p, 'recall': r, 'f1': f1, 'confusion': conf,
               'all_pred': all_pred, 'all_pred_flat': flat}
+    if want_logits and flat_logits is None:
+        flat_logits = torch.empty((0, n_classes), dtype=torch.float32, device=device)
     if regions:
-        if region_scores and flat_logits is None:
-            flat_logits = torch.empty((0, n_classes), dtype=torch.float32, device=device)
         result['regions'] = PP.extract_regions(data, all_pred, batch_pages=bs, device=device, logits=flat_logits if region_scores else None)
         doc = PP.regions_json(data, result['regions']) if (save_predictions or box_eval) else None
         if save_predictions:
@@ -268,7 +282,11 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
             gt = PP.regions_gt_json(data, PP.extract_regions(data, labels, batch_pages=bs, device=device))
             result['box_eval'] = metrics.evaluate_regions(doc, gt, device=device)
     if blocks:
-        result['blocks'] = PP.extract_blocks(data, all_pred, batch_pages=bs, device=device)
+        result['blocks'] = PP.extract_blocks(data, all_pred, batch_pages=bs, device=device, logits=flat_logits if block_scores else None)
+        doc = PP.blocks_json(data, result['blocks']) if (save_predictions or want_block_eval) else None
         if save_predictions:
-            write_json('blocks', PP.blocks_json(data, result['blocks']))
+            write_json('blocks', doc)
+        if want_block_eval:
+            gt = PP.blocks_gt_json(data) if block_eval is True else block_eval
+            result['block_eval'] = metrics.evaluate_regions(doc, gt, device=device, float_boxes=True)
     return result

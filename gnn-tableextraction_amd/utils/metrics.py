@@ -3,7 +3,8 @@ predictions, and the box-level AP of predicted regions.
 
 ``evaluate_regions`` is three public stages in a row -- ``region_cells`` (host) -> ``box_match`` (gte_box_match, ONE launch) ->
 ``average_precisions`` (host, numpy) -- so that the host stages run (and are tested) without a device, with a CPU oracle in place
-of the launch.
+of the launch.  ``float_boxes=True`` takes the documents' boxes as float64 through the same stages (gte_box_match_f64): the block
+route's document, which is what the reference itself evaluates.
 """
 from __future__ import annotations
 
@@ -34,15 +35,19 @@ class RegionCells(NamedTuple):
     kind: list                # per cell: its kind
     scores: list              # per cell: float64 [r] the page's scores in stable ascending order
     pred_box: np.ndarray      # int32 [R, 4]  the cells' predictions concatenated, inside a cell in the order of ``scores``
-    pred_off: list            # [cells + 1]
+    pred_off: list            # [cells + 1]                                                  (float64 with ``float_boxes``)
     gt_box: np.ndarray        # int32 [G, 4]  the cells' ground truths concatenated
     gt_off: list              # [cells + 1]
 
 
-def region_cells(pred_doc, gt_doc, count_unpaired=False) -> RegionCells:
+def region_cells(pred_doc, gt_doc, count_unpaired=False, float_boxes=False) -> RegionCells:
     """Stage one of :func:`evaluate_regions`: the documents (layouts there) as cells -- the paired pages of every kind (all pages
     with ``count_unpaired``), each page's predictions in stable ascending score order, the boxes concatenated with offsets: the
-    arguments of :func:`box_match`.  ``ValueError`` on unequal box / score counts and on a malformed box; no device is touched."""
+    arguments of :func:`box_match`.  ``ValueError`` on unequal box / score counts and on a malformed box; no device is touched.
+
+    ``float_boxes=False`` casts every coordinate to an integer (a float document is truncated); ``True`` keeps float64 boxes and
+    raises ``ValueError`` for a box with a non-finite value, inverted corners or a value outside +-2^24."""
+    box_type = np.float64 if float_boxes else np.int64
     kinds = list(gt_doc) + [k for k in pred_doc if k not in gt_doc]
     kind_of, scores, pbox, gbox, po, go = [], [], [], [], [0], [0]
     for kind in kinds:
@@ -50,12 +55,17 @@ def region_cells(pred_doc, gt_doc, count_unpaired=False) -> RegionCells:
         pages = [pg for pg in gts if pg in preds or count_unpaired] + [pg for pg in preds if pg not in gts and count_unpaired]
         for pg in pages:
             sc = np.asarray(preds[pg]['scores'], dtype=np.float64).reshape(-1) if pg in preds else np.zeros(0)
-            bx = np.asarray(preds[pg]['bboxes'], dtype=np.int64).reshape(-1, 4) if pg in preds else np.zeros((0, 4), dtype=np.int64)
-            gb = np.asarray(gts.get(pg, []), dtype=np.int64).reshape(-1, 4)
+            bx = np.asarray(preds[pg]['bboxes'], dtype=box_type).reshape(-1, 4) if pg in preds else np.zeros((0, 4), dtype=box_type)
+            gb = np.asarray(gts.get(pg, []), dtype=box_type).reshape(-1, 4)
             if sc.shape[0] != bx.shape[0]:
                 raise ValueError(f"evaluate_regions: {kind} / {pg}: {bx.shape[0]} boxes, {sc.shape[0]} scores")
             for what, a in (("predicted", bx), ("ground-truth", gb)):
-                if a.size and ((a[:, 0] > a[:, 2]).any() or (a[:, 1] > a[:, 3]).any() or np.abs(a).max() >= 1 << 24):
+                if float_boxes:
+                    if a.size and not (np.isfinite(a).all() and (a[:, 0] <= a[:, 2]).all() and (a[:, 1] <= a[:, 3]).all()
+                                       and np.abs(a).max() <= 1 << 24):
+                        raise ValueError(f"evaluate_regions: {kind} / {pg}: a {what} box is non-finite, malformed (metrics.py:35-40) "
+                                         f"or outside +-2^24")
+                elif a.size and ((a[:, 0] > a[:, 2]).any() or (a[:, 1] > a[:, 3]).any() or np.abs(a).max() >= 1 << 24):
                     raise ValueError(f"evaluate_regions: {kind} / {pg}: a {what} box is malformed (metrics.py:35-40) or outside +-2^24")
             order = np.argsort(sc, kind='stable')
             kind_of.append(kind)
@@ -66,11 +76,12 @@ def region_cells(pred_doc, gt_doc, count_unpaired=False) -> RegionCells:
             go.append(go[-1] + gb.shape[0])
     thresholds = {kind: np.unique(np.asarray([s for e in pred_doc.get(kind, {}).values() for s in e['scores']], dtype=np.float64))
                   for kind in kinds}
-    cat = lambda parts: np.concatenate(parts).astype(np.int32) if parts else np.zeros((0, 4), dtype=np.int32)
+    out_type = np.float64 if float_boxes else np.int32
+    cat = lambda parts: np.concatenate(parts).astype(out_type) if parts else np.zeros((0, 4), dtype=out_type)
     return RegionCells(kinds, thresholds, kind_of, scores, cat(pbox), po, cat(gbox), go)
 
 
-def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, iou_thr) -> torch.Tensor:
+def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, iou_thr, float_boxes=False, return_iou=False):
     """Match counts of the box-level evaluation (gte_box_match, one launch): ``tp`` int32 [n_thr, R] on the device.
 
     Cell b (one page and kind) holds the predictions ``pred_box[pred_off[b]:pred_off[b + 1]]`` (int [R, 4], inside a cell ASCENDING
@@ -79,13 +90,20 @@ def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, io
     between the cell's ground truths and its predictions ``k ..``, i.e. after pruning its k lowest-scored boxes.  ``iou_thr``:
     1 .. 16 ascending thresholds.  Raises ``ValueError`` naming the first cell whose candidate pairs exceed
     ``gte_box_match_max_candidates()``; ``GteError`` when a cell has more than ``gte_box_match_max_boxes()`` boxes on a side.
-    One synchronisation (the cells' status words are read before the result is handed out)."""
+    One synchronisation (the cells' status words are read before the result is handed out).
+
+    ``float_boxes=True``: the boxes are taken as float64 (gte_box_match_f64: the reference's ``calc_iou_individual`` in IEEE
+    double, operation by operation); a non-finite, inverted or ``|v| > 2^24`` box overlaps nothing.  With ``return_iou=True``
+    (float boxes only) the result is ``(tp, iou)``, ``iou`` float64 the cells' R_b x G_b IoU matrices, row-major, concatenated."""
     _lib.require_device(pred_box, "box_match")
     _lib.require_device(gt_box, "box_match")
     lib, P = _lib.load(), _lib.ptr
     dev = pred_box.device
-    pred_box = pred_box.to(torch.int32).reshape(-1, 4).contiguous()
-    gt_box = gt_box.to(dev).to(torch.int32).reshape(-1, 4).contiguous()
+    if return_iou and not float_boxes:
+        raise ValueError("box_match: return_iou needs float_boxes")
+    box_type = torch.float64 if float_boxes else torch.int32
+    pred_box = pred_box.to(box_type).reshape(-1, 4).contiguous()
+    gt_box = gt_box.to(dev).to(box_type).reshape(-1, 4).contiguous()
     po, d_po = _lib.partition_offsets(pred_off, pred_box.shape[0], "box_match: the prediction offsets", dev)
     go, d_go = _lib.partition_offsets(gt_off, gt_box.shape[0], "box_match: the ground-truth offsets", dev)
     if po.size != go.size:
@@ -94,15 +112,27 @@ def box_match(pred_box: torch.Tensor, pred_off, gt_box: torch.Tensor, gt_off, io
     thr = np.ascontiguousarray(np.asarray(iou_thr, dtype=np.float64).reshape(-1))
     tp = torch.empty((thr.size, pred_box.shape[0]), dtype=torch.int32, device=dev)
     status = torch.empty(cells, dtype=torch.int32, device=dev)
-    _lib.check(lib.gte_box_match(P(pred_box), P(d_po), P(gt_box), P(d_go), cells, int(np.diff(po).max()) if cells else 0,
-                                 int(np.diff(go).max()) if cells else 0, thr.ctypes.data_as(ctypes.c_void_p), thr.size, P(tp),
-                                 P(status), _lib.current_stream()), "gte_box_match")
+    iou = None
+    if float_boxes:
+        d_io = None
+        if return_iou:
+            io = np.concatenate([[0], np.cumsum(np.diff(po).astype(np.int64) * np.diff(go).astype(np.int64))]).astype(np.int64)
+            d_io = torch.from_numpy(io).to(dev)
+            iou = torch.empty(int(io[-1]), dtype=torch.float64, device=dev)
+        _lib.check(lib.gte_box_match_f64(P(pred_box), P(d_po), P(gt_box), P(d_go), cells, int(np.diff(po).max()) if cells else 0,
+                                         int(np.diff(go).max()) if cells else 0, thr.ctypes.data_as(ctypes.c_void_p), thr.size,
+                                         P(tp), P(status), None if iou is None else P(iou), None if d_io is None else P(d_io),
+                                         _lib.current_stream()), "gte_box_match_f64")
+    else:
+        _lib.check(lib.gte_box_match(P(pred_box), P(d_po), P(gt_box), P(d_go), cells, int(np.diff(po).max()) if cells else 0,
+                                     int(np.diff(go).max()) if cells else 0, thr.ctypes.data_as(ctypes.c_void_p), thr.size, P(tp),
+                                     P(status), _lib.current_stream()), "gte_box_match")
     bad = torch.nonzero(status).flatten()
     if bad.numel():
         b = int(bad[0])
         raise ValueError(f"box_match: cell {b} ({int(po[b + 1] - po[b])} predicted x {int(go[b + 1] - go[b])} ground-truth boxes) has more "
                          f"than {lib.gte_box_match_max_candidates()} pairs above IoU {thr[0]} (status {int(status[b])})")
-    return tp
+    return (tp, iou) if return_iou else tp
 
 
 def average_precisions(cells: RegionCells, tp):
@@ -141,7 +171,7 @@ def average_precisions(cells: RegionCells, tp):
     return out
 
 
-def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, device=None):
+def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, device=None, float_boxes=False):
     """Box-level evaluation of predicted regions: the reference's AP at IoU thresholds (``get_avg_precision_at_iou`` of
     src/utils/metrics.py:162-244 per kind and threshold, their mean as in evaluate.py:116-129), with the box matching of all
     pages, kinds and thresholds in ONE launch (``box_match`` -> gte_box_match) and the curve from its integer counts.
@@ -166,12 +196,17 @@ def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, devi
       ``linspace(0, 1, 11)`` of the largest precision at ``recall >= level`` (0.0 where there is none).
 
     Returns ``{kind: {'ap': [per IoU threshold], 'map': mean, 'precisions': [[...] per IoU threshold], 'recalls': [[...]],
-    'thresholds': [score thresholds]}, ..., 'map': mean of the kinds' 'map'}`` over the kinds of ``gt_doc`` and ``pred_doc``."""
+    'thresholds': [score thresholds]}, ..., 'map': mean of the kinds' 'map'}`` over the kinds of ``gt_doc`` and ``pred_doc``.
+
+    ``float_boxes=True``: the boxes are float64 and the IoU is the reference's ``calc_iou_individual`` on floats, bit for bit
+    (gte_box_match_f64) -- for the block route's document (``postprocessing.blocks_json``, coordinates divided by 0.36) against
+    annotation boxes (``postprocessing.blocks_gt_json``), the evaluation of the reference's models/evaluate.py:64-131.  ``False``
+    casts every coordinate to an integer."""
     iou_thrs = np.linspace(0.5, 0.95, 10) if iou_thrs is None else np.asarray(iou_thrs, dtype=np.float64).reshape(-1)
-    cells = region_cells(pred_doc, gt_doc, count_unpaired)
+    cells = region_cells(pred_doc, gt_doc, count_unpaired, float_boxes)
     tp = np.zeros((iou_thrs.size, 0), dtype=np.int64)
     if cells.kind:
         device = _lib.default_device(device)
         tp = box_match(torch.from_numpy(cells.pred_box).to(device), cells.pred_off, torch.from_numpy(cells.gt_box).to(device),
-                       cells.gt_off, iou_thrs).cpu().numpy()
+                       cells.gt_off, iou_thrs, float_boxes=float_boxes).cpu().numpy()
     return average_precisions(cells, tp)

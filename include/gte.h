@@ -229,6 +229,24 @@ int gte_box_match(const int32_t* pred_box, const int32_t* pred_off, const int32_
                   int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr, int32_t* tp,
                   int32_t* cell_status, void* stream);
 
+/* gte_box_match on FLOAT boxes: the document of the block route (postprocessing_2.py:197-348, coordinates divided by 0.36) against
+ * annotation boxes, what the reference's models/evaluate.py:64-131 scores.  The same cells, offsets, tp layout, status codes and
+ * limits; pred_box / gt_box are double [., 4], 16-byte aligned.  The IoU is calc_iou_individual() of src/utils/metrics.py:20-54 in
+ * IEEE double, one rounding per operation, in this order and with no contraction:
+ *   disjoint (x2_t < x1_p || x2_p < x1_t || y2_t < y1_p || y2_p < y1_t): 0.0; otherwise
+ *   inter = ((far_x - near_x) + 1) * ((far_y - near_y) + 1),  area = ((x2 - x1) + 1) * ((y2 - y1) + 1) per box,
+ *   iou = inter / ((true_area + pred_area) - inter).
+ * A box is well formed when its four values are finite, x0 <= x1, y0 <= y1 and |v| <= 2^24; any other box overlaps nothing (IoU
+ * 0.0 with every box).  A non-finite quotient is no candidate.  Candidates are iou > iou_thr[j] strictly, order = IoU descending,
+ * then p * G_b + g descending (the reference leaves ties unspecified: np.argsort(ious)[::-1], metrics.py:94).
+ *   iou (NULL: not written, no cost)   cell b's R_b x G_b matrix, row-major (p * G_b + g), at iou[iou_off[b] ...]: every pair's
+ *                  IoU whatever the thresholds.  iou_off int64 [n_cells + 1] on the device, iou_off[b + 1] - iou_off[b] ==
+ *                  R_b * G_b; a cell whose entries do not say so ends with status 2 (tp -1) as for wrong maxima.  A cell that
+ *                  ends with status 2 writes nothing to iou; a cell with status 1 has its matrix written. */
+int gte_box_match_f64(const double* pred_box, const int32_t* pred_off, const double* gt_box, const int32_t* gt_off, int64_t n_cells,
+                      int64_t max_pred_per_cell, int64_t max_gt_per_cell, const double* iou_thr, int n_thr, int32_t* tp,
+                      int32_t* cell_status, double* iou, const int64_t* iou_off, void* stream);
+
 /* ---- layout blocks labelled by the vote of their words (postprocessing_2.py:240-258, the words x blocks loop of get_objects_bboxs) -
  * Inputs: bbox int32 [n_nodes, 4] the word boxes; word_cat int32 [n_nodes] the category of every word (a value < 0 or >= n_cat:
  * the word is still assigned to a block but casts no vote); block_box double [n_blocks, 4] the layout blocks ALREADY DIVIDED by
@@ -250,6 +268,34 @@ int gte_block_vote_max_categories(void);    /* 16 */
 int gte_block_vote(const int32_t* bbox, const int32_t* node_off, const int32_t* word_cat, const double* block_box,
                    const int32_t* block_off, int64_t n_pages, int64_t n_nodes, int64_t n_blocks, int64_t max_page_blocks, int n_cat,
                    int double_cat, int32_t* word_block, int32_t* votes, int32_t* block_label, void* stream);
+
+/* ---- confidence of a page's FINAL blocks (after table assembly and figures; the reference's write_json gives every block 1.0,
+ * postprocessing_2.py:337) ----
+ * Inputs: bbox int32 [n_nodes, 4] the word boxes; logits float [n_nodes, .] the words' logit rows, row v at logits + v * ld_logits
+ * (ld_logits >= n_classes, 1 <= n_classes <= 16); block_box double [n_blocks, 4] the final blocks in WORD coordinates (already
+ * divided by the scale factor where they were not yet); block_cat int32 [n_blocks] their categories; cat_classes uint32 [n_cat]
+ * (device, 1 <= n_cat <= 16): bit c of cat_classes[k] set = class c counts for a block of category k (a category outside
+ * [0, n_cat) has the empty mask; bits at and above n_classes are ignored); node_off / block_off [n_pages + 1] as for gte_block_vote.
+ * A word MEETS a block under gte_block_vote's closed rectangle test (corners normalised, fp64, a block with a NaN corner meets
+ * nothing) and counts in EVERY block of its page it meets, not only the first.  For word v and a block of category k:
+ *   q(v, k) = (uint32)(num / den * 2^19 + 0.5f), the fp32 max-subtracted softmax of v's row, den the sum of all classes'
+ *             exponentials and num that of the classes in cat_classes[k], both in ascending class order -- bit for bit the word
+ *             score of gte_page_regions_scored for the same set; 0 for a row with a non-finite logit (which still counts as a word).
+ *   n_words[b]  the number of words that meet block b.
+ *   score[b]    (float)((double)sum_v q(v, k_b) / ((double)n_words[b] * 2^19)); 1.0f where no word meets b.  Within 2^-18 of the mean.
+ * One launch, one workgroup per page, the blocks and two u32 sums per block in LDS (integer atomics: deterministic).
+ * max_page_words / max_page_blocks = the largest page's counts: above gte_block_scores_max_page_words() (4096: the sum of q fits 32
+ * bits) / gte_block_scores_max_page_blocks(), or with more classes / categories than the limits, the call returns
+ * GTE_ERR_UNSUPPORTED before any launch.  A page above the stated maxima writes n_words -1 and score 0; a page whose offsets name
+ * no rows writes nothing.  No allocation, no workspace, no synchronisation.  bbox 16-byte aligned. */
+int gte_block_scores_max_page_blocks(void);   /* 512 */
+int gte_block_scores_max_page_words(void);    /* 4096 */
+int gte_block_scores_max_classes(void);       /* 16 */
+int gte_block_scores_max_categories(void);    /* 16 */
+int gte_block_scores(const int32_t* bbox, const int32_t* node_off, const float* logits, int64_t ld_logits, int n_classes,
+                     const double* block_box, const int32_t* block_off, const int32_t* block_cat, const uint32_t* cat_classes,
+                     int n_cat, int64_t n_pages, int64_t n_nodes, int64_t n_blocks, int64_t max_page_words, int64_t max_page_blocks,
+                     float* score, int32_t* n_words, void* stream);
 
 /* The whole batch in ONE launch (what the train loop calls every step; gte_batch_csr / gte_batch_rows are its pieces):
  * a page's rows are CONTIGUOUS in the resident arrays and in the batch, so every array of the batch is the concatenation
