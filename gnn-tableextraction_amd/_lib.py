@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTE_LIB_PATH: profiling builds of the same ABI (e.g. ablation variants); default = the in-tree library
@@ -67,6 +67,12 @@ SIGNATURES = {
     "gte_block_vote_max_categories": (c_int, []),
     "gte_block_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    # word labels and figure nodes from page annotations (csrc/word_labels.hip)
+    "gte_word_labels_chunk": (c_int, []),
+    "gte_word_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_uint32, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gte_word_labels_compact": (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                                         c_void_p, c_void_p, c_void_p]),
     "gte_batch_assemble": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_batch_assemble_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,

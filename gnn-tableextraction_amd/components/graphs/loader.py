@@ -20,6 +20,8 @@ from ...data import synthetic as S
 
 # src/components/graphs/labels.py:13-19: 13 categories minus the never-instantiated {4, 9, 11, 12}
 ORIGIN_TO_CONV = {0: 0, 1: 1, 2: 2, 3: 3, 5: 4, 6: 5, 7: 6, 8: 7, 10: 8, 4: None, 9: None, 11: None, 12: None}
+# builder.py:159, 164: the categories get_label passes over (TABLE, TABLE_GCELL, TABLE_COL, TABLE_ROW) and the one that drops a word
+SKIPPED, FIGURE = (4, 9, 11, 12), 5
 
 
 class LabelTransformer:
@@ -81,13 +83,38 @@ class PrebuiltPages:
     @classmethod
     def from_boxes(cls, page_boxes, page_sizes, page_texts, page_labels, device, k: int = 5, max_dist: int = 500,
                    bidirectional: bool = True, range_island: int = 0, extra_feats=None, mode: str = "knn",
-                   **kw) -> "PrebuiltPages":
+                   page_annotations=None, converted: bool = True, **kw) -> "PrebuiltPages":
         """Pages from word boxes with the graph stage on the DEVICE: k-NN edges, island removal,
         to_simple + to_bidirected, edge weights (graph.knn_graph_from_boxes) and the 13 BBOX node features
         (graph.bbox_features) -- what builder.get_graph + loader.modify_graphs + nlp/bbox.py do per page in Python.
         ``page_boxes[p]`` int [n_p, 4], ``page_sizes[p]`` = (width, height), ``page_texts[p]`` the words (for the character
         histogram; None -> empty texts), ``page_labels[p]`` converted class ids, ``extra_feats[p]`` optional float32 [n_p, F']
-        columns appended after the BBOX features (REPR / SPACY / SCIBERT embeddings stay pre-computed)."""
+        columns appended after the BBOX features (REPR / SPACY / SCIBERT embeddings stay pre-computed).
+
+        ``page_annotations`` INSTEAD of ``page_labels`` (exactly one of the two, the other None): ``page_annotations[p]`` rows
+        ``[x0, y0, x1, y1, category]`` with ORIGINAL category ids, what ``postprocessing.blocks_gt_json`` reads.  The node list
+        is then built as ``GraphBuilder.get_graph(set_labels=True)`` builds it (graph.label_words: labels by the first
+        annotation that holds a word's centre, words inside a FIGURE dropped, every FIGURE a node "IMAGE!" in front of its
+        page's words) and the path above runs on it; ``converted`` applies ``LableModification``'s conversion (False: original
+        ids, ``num_classes`` 13).  ``extra_feats`` must then be a callable ``(page_texts, page_boxes) -> [n_p, F'] arrays`` of the
+        FINAL node lists: arrays per input word cannot line up once figure nodes are added and words dropped.
+        ``pages[i]`` gains ``'annotations'`` (as given) and ``'texts'`` (of the final nodes)."""
+        if (page_labels is None) == (page_annotations is None):
+            raise ValueError("from_boxes: exactly one of page_labels and page_annotations must be given, for all pages (got "
+                             f"{'both' if page_labels is not None else 'neither'})")
+        if page_annotations is not None:
+            return cls._from_annotations(page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats,
+                                         dict(k=k, max_dist=max_dist, bidirectional=bidirectional, range_island=range_island,
+                                              mode=mode), kw)
+        return cls._from_node_lists(page_boxes, page_sizes, page_texts, page_labels, device, k, max_dist, bidirectional,
+                                    range_island, extra_feats, mode, kw)[0]
+
+    @classmethod
+    def _from_node_lists(cls, page_boxes, page_sizes, page_texts, page_labels, device, k, max_dist, bidirectional, range_island,
+                         extra_feats, mode, kw, extra_feats_fn=None):
+        """from_boxes for node lists that carry their labels -> (dataset, keep: bool [N] on the device over the given nodes).
+        ``extra_feats_fn(page_texts, page_boxes)``: the extra columns as a callable on the node lists that are left after island
+        removal."""
         from ... import graph as G
         from ..nlp.bbox import Bbox
         device = torch.device(device)
@@ -104,6 +131,15 @@ class PrebuiltPages:
         if extra_feats is not None:
             extra = torch.from_numpy(np.concatenate([np.asarray(e, dtype=np.float32) for e in extra_feats])).to(device)[keep]
             feat = torch.cat([feat, extra], dim=1)
+        if extra_feats_fn is not None:
+            keep_h = keep.cpu().numpy()
+            kept = [keep_h[int(node_off[p]):int(node_off[p + 1])] for p in range(n_pages)]
+            final_texts = [[t for t, ok in zip(texts[p], kept[p].tolist()) if ok] for p in range(n_pages)]
+            final_boxes = [np.asarray(page_boxes[p], dtype=np.int32).reshape(-1, 4)[kept[p]] for p in range(n_pages)]
+            extra = extra_feats_fn(final_texts, final_boxes)
+            extra = torch.from_numpy(np.concatenate([np.asarray(e, dtype=np.float32).reshape(len(t), -1)
+                                                     for e, t in zip(extra, final_texts)])).to(device)
+            feat = torch.cat([feat, extra], dim=1)
         # per-page host arrays (the dataset object's contract: .graphs[i] with ndata feat/label, edata feat, .pages[i]['bboxs'])
         src, dst = (t.cpu().numpy() for t in g.edges())
         w = g.edata['feat'].cpu().numpy()
@@ -118,6 +154,76 @@ class PrebuiltPages:
         out = cls(pages, **kw)
         g.ndata['feat'] = feat
         out.whole = g                                       # the batched device graph, for callers that stay on the device
+        return out, keep
+
+    @staticmethod
+    def check_annotations(page_annotations, n_pages: int):
+        """Host validation of ``page_annotations`` (no device needed) -> (ann_box float64 [A, 4], ann_cat int32 [A], ann_off int64
+        [P + 1]).  ``ValueError`` naming the page for: a page count other than ``n_pages``; a row that is not five numbers; a
+        category that is not an integer in 0 .. 12; a FIGURE annotation (it becomes a node with an int32 box) with a
+        non-integral coordinate or one beyond +-2^30."""
+        import math
+        import numbers
+        if len(page_annotations) != n_pages:
+            raise ValueError(f"from_boxes: page_annotations names {len(page_annotations)} pages, page_boxes {n_pages}")
+        boxes, cats, off = [], [], [0]
+        for p, rows in enumerate(page_annotations):
+            for row in rows:
+                row = row.tolist() if isinstance(row, np.ndarray) else row
+                if (not isinstance(row, (list, tuple)) or len(row) != 5
+                        or not all(isinstance(v, numbers.Real) and not isinstance(v, bool) for v in row)):
+                    raise ValueError(f"from_boxes: page {p}: annotation {row!r} is not five numbers [x0, y0, x1, y1, category]")
+                c = row[4]
+                if not math.isfinite(c) or int(c) != c or not 0 <= int(c) < len(ORIGIN_TO_CONV):
+                    raise ValueError(f"from_boxes: page {p}: annotation {row!r}: the category is not an integer in 0 .. "
+                                     f"{len(ORIGIN_TO_CONV) - 1}")
+                if int(c) == FIGURE:
+                    for v in row[:4]:
+                        if not math.isfinite(v) or abs(v) > 2 ** 30 or int(v) != v:
+                            raise ValueError(f"from_boxes: page {p}: FIGURE annotation {row!r} becomes a node: its coordinates "
+                                             f"must be whole numbers within +-2^30")
+                boxes.append([float(v) for v in row[:4]])
+                cats.append(int(c))
+            off.append(len(cats))
+        return (np.asarray(boxes, dtype=np.float64).reshape(-1, 4), np.asarray(cats, dtype=np.int32),
+                np.asarray(off, dtype=np.int64))
+
+    @classmethod
+    def _from_annotations(cls, page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats, graph_kw, kw):
+        from ... import graph as G
+        n_pages = len(page_boxes)
+        ann_box, ann_cat, ann_off = cls.check_annotations(page_annotations, n_pages)
+        if extra_feats is not None and not callable(extra_feats):
+            raise ValueError("from_boxes: with page_annotations extra_feats must be a callable (page_texts, page_boxes) -> arrays "
+                             "of the final node lists: arrays per input word cannot line up once figure nodes are added and "
+                             "words inside a figure dropped")
+        device = torch.device(device)
+        sizes = [len(b) for b in page_boxes]
+        node_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        bbox = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.int32).reshape(-1, 4) for b in page_boxes] +
+                                               [np.zeros((0, 4), dtype=np.int32)])).to(device)
+        cat_map = [-1 if ORIGIN_TO_CONV[c] is None else ORIGIN_TO_CONV[c] for c in range(len(ORIGIN_TO_CONV))] if converted else None
+        out_bbox, out_label, out_src, out_off, _, _ = G.label_words(bbox, node_off, ann_box, ann_cat, ann_off, cat_map=cat_map,
+                                                                    skip=SKIPPED, figure_cat=FIGURE, n_cat=len(ORIGIN_TO_CONV))
+        box_h, lab_h, src_h, off_h = (t.cpu().numpy() for t in (out_bbox, out_label, out_src, out_off))
+        texts = page_texts if page_texts is not None else [[""] * n for n in sizes]
+        new_boxes, new_labels, new_texts = [], [], []
+        for p in range(n_pages):
+            o0, o1 = int(off_h[p]), int(off_h[p + 1])
+            new_boxes.append(box_h[o0:o1])
+            new_labels.append(lab_h[o0:o1].astype(np.int64))
+            new_texts.append(["IMAGE!" if s < 0 else texts[p][s - int(node_off[p])] for s in src_h[o0:o1].tolist()])
+        if not converted:
+            kw = dict(kw)
+            kw.setdefault('num_classes', len(ORIGIN_TO_CONV))
+        out, keep = cls._from_node_lists(new_boxes, page_sizes, new_texts, new_labels, device, graph_kw['k'], graph_kw['max_dist'],
+                                         graph_kw['bidirectional'], graph_kw['range_island'], None, graph_kw['mode'], kw,
+                                         extra_feats_fn=extra_feats)
+        keep_h = keep.cpu().numpy()
+        for p in range(n_pages):
+            o0, o1 = int(off_h[p]), int(off_h[p + 1])
+            out.pages[p]['annotations'] = page_annotations[p]
+            out.pages[p]['texts'] = [t for t, kept in zip(new_texts[p], keep_h[o0:o1].tolist()) if kept]
         return out
 
     @classmethod

@@ -813,3 +813,63 @@ def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, ma
     if edge_features:
         g.edata["feat"] = edge_weights_from_boxes(bbox, indices, dst_of, page_of_node, n_pages)
     return g, keep
+
+
+def label_words(bbox: torch.Tensor, node_off, ann_box, ann_cat, ann_off, *, cat_map=None, skip=(4, 9, 11, 12),
+                figure_cat: int = 5, n_cat: int = 13):
+    """Word labels and figure nodes from page annotations, on the device: the node list of
+    ``GraphBuilder.get_graph(set_labels=True)`` (``get_label``, builder.py:151-167, and the two loops of ``get_nodes``,
+    builder.py:195-216) for all pages at once -- gte_word_labels -> one device cumsum -> gte_word_labels_compact.
+
+    ``bbox`` int32 [N, 4] the word boxes (pages concatenated), ``node_off`` [P + 1]; ``ann_box`` float64 [A, 4] the annotation
+    rectangles as given, ``ann_cat`` [A] their ORIGINAL category ids, ``ann_off`` [P + 1].  A word takes the category of the first
+    annotation of its page, outside ``skip``, whose rectangle strictly contains the word's centre; a word inside a
+    ``figure_cat`` annotation is dropped; every ``figure_cat`` annotation becomes a node in front of its page's words.
+    ``cat_map`` [n_cat] converts the categories of the OUTPUT nodes (``LableModification.origin_to_conv``, -1 for ``None``).
+    Returns ``(out_bbox [M, 4], out_label [M], out_src [M], out_node_off [P + 1], word_label [N], word_ann [N])``, int32 on the
+    device: ``out_src`` = the input word of a node, or -1 - the annotation of a figure node; ``word_label`` = the original
+    category per INPUT word (-1 dropped, 0 no annotation), ``word_ann`` its annotation (-1 none).  One host synchronisation (the
+    node count)."""
+    _lib.require_device(bbox, "label_words")
+    lib, P = _lib.load(), _lib.ptr
+    dev = bbox.device
+    bbox = bbox.to(torch.int32).reshape(-1, 4).contiguous()
+    n = bbox.shape[0]
+    ann_box = torch.as_tensor(ann_box, dtype=torch.float64).reshape(-1, 4).to(dev).contiguous()
+    ann_cat = torch.as_tensor(ann_cat).to(torch.int32).reshape(-1).to(dev).contiguous()
+    n_ann = ann_cat.numel()
+    if ann_box.shape[0] != n_ann:
+        raise ValueError(f"{ann_box.shape[0]} annotation rectangles, {n_ann} categories")
+    _, node_off_d = _lib.partition_offsets(torch.as_tensor(node_off).cpu().numpy(), n, "label_words: node_off", dev)
+    _, ann_off_d = _lib.partition_offsets(torch.as_tensor(ann_off).cpu().numpy(), n_ann, "label_words: ann_off", dev)
+    n_pages = node_off_d.numel() - 1
+    if ann_off_d.numel() - 1 != n_pages:
+        raise ValueError(f"node_off names {n_pages} pages, ann_off {ann_off_d.numel() - 1}")
+    skip_mask = 0
+    for c in skip:
+        if not 0 <= int(c) < 32:
+            raise ValueError(f"label_words: skip category {c} outside 0 .. 31")
+        skip_mask |= 1 << int(c)
+    map_d = None
+    if cat_map is not None:
+        map_d = torch.as_tensor(cat_map).to(torch.int32).reshape(-1).to(dev).contiguous()
+        if map_d.numel() != n_cat:
+            raise ValueError(f"label_words: cat_map has {map_d.numel()} entries for {n_cat} categories")
+    stream = _lib.current_stream()
+    word_label = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    word_ann = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    counts = torch.zeros((n_pages, 2), dtype=torch.int32, device=dev)
+    _lib.check(lib.gte_word_labels(P(bbox), P(node_off_d), P(ann_box), P(ann_cat), P(ann_off_d), n_pages, n, n_ann, int(n_cat),
+                                   skip_mask, int(figure_cat), P(word_label), P(word_ann), P(counts), stream), "gte_word_labels")
+    out_off = torch.zeros(n_pages + 1, dtype=torch.int32, device=dev)
+    out_off[1:] = torch.cumsum(counts.sum(1), 0)
+    m = int(out_off[-1].item())                                 # the one synchronisation: the size of the node list
+    out_bbox = torch.empty((max(m, 1), 4), dtype=torch.int32, device=dev)[:m]
+    out_label = torch.empty(max(m, 1), dtype=torch.int32, device=dev)[:m]
+    out_src = torch.empty(max(m, 1), dtype=torch.int32, device=dev)[:m]
+    # out_off is the cumulative sum of the counts gte_word_labels wrote itself: every page agrees, page_status is not read back
+    status = torch.zeros(max(n_pages, 1), dtype=torch.int32, device=dev)[:n_pages]
+    _lib.check(lib.gte_word_labels_compact(P(bbox), P(node_off_d), P(word_label), P(ann_box), P(ann_cat), P(ann_off_d), P(out_off),
+                                           P(map_d), n_pages, n, n_ann, int(n_cat), int(figure_cat), m, P(out_bbox), P(out_label),
+                                           P(out_src), P(status), stream), "gte_word_labels_compact")
+    return out_bbox, out_label, out_src, out_off, word_label, word_ann

@@ -269,6 +269,48 @@ int gte_block_vote(const int32_t* bbox, const int32_t* node_off, const int32_t* 
                    const int32_t* block_off, int64_t n_pages, int64_t n_nodes, int64_t n_blocks, int64_t max_page_blocks, int n_cat,
                    int double_cat, int32_t* word_block, int32_t* votes, int32_t* block_label, void* stream);
 
+/* ---- word labels and figure nodes from page annotations (builder.py:151-167 get_label with utils.py:107-108 center; the two loops
+ * of get_nodes, builder.py:195-216) ----
+ * Inputs, pages concatenated: bbox int32 [n_nodes, 4] the word boxes (x0, y0, x2, y3), 16-byte aligned; node_off[n_pages + 1];
+ * ann_box double [n_ann, 4] the annotation rectangles (r0, r1, r2, r3) AS GIVEN -- they are not normalised: an inverted rectangle
+ * contains nothing, as in the reference, and so does one with a NaN coordinate; ann_cat int32 [n_ann] their categories;
+ * ann_off[n_pages + 1]; 1 <= n_cat <= 32; skip_mask: bit c set = an annotation of category c never labels a word (the reference:
+ * {4, 9, 11, 12} = TABLE, TABLE_GCELL, TABLE_COL, TABLE_ROW, builder.py:159); figure_cat in [0, n_cat) (the reference: 5).  Empty
+ * pages and pages without annotations are legal.
+ * For word v of page p:  cx = (x0 + x2) / 2, cy = (y0 + y3) / 2, the sums in 64-bit integers, C's division (towards zero): for
+ * every int32 box that is int(x2 - (x2 - x0) / 2) of center().  The page's annotations are scanned in index order; one whose
+ * category is in skip_mask or outside [0, n_cat) is passed over; the FIRST of the others with
+ *     cx > r0 && cx < r2 && cy > r1 && cy < r3      (strict, fp64, on exact values)
+ * WINS and the scan ends there (a FIGURE annotation behind an earlier winner does not drop the word).
+ *   word_ann[v]      the winner's global index; -1 where there is none.
+ *   word_label[v]    the winner's category; -1 where that is figure_cat (the word is DROPPED); 0 (OTHER) where there is none.
+ *   page_counts[p]   (the page's annotations with category figure_cat -- passed over or not --, its words with word_label >= 0).
+ * gte_word_labels: one launch, one workgroup per page, the annotations staged through LDS in chunks of gte_word_labels_chunk():
+ * no limit on the annotations of a page, no GTE_ERR_UNSUPPORTED.  A page whose runs are not ascending inside [0, n_nodes] /
+ * [0, n_ann] writes page_counts (0, 0) and nothing else.  Counts are LDS integer atomics: deterministic.
+ *
+ * gte_word_labels_compact: the node list of get_nodes from word_label.  out_off int32 [n_pages + 1] on the device: the caller's
+ * exclusive cumulative sum of figures + kept words (page_counts summed per page); cat_map int32 [n_cat] or NULL for the identity
+ * (LableModification.origin_to_conv, labels.py:13-19, with -1 for None).  Page p writes the rows out_off[p] ...:
+ *   first its annotations of category figure_cat, in annotation order:  out_bbox = the four doubles clamped to [-2^30, 2^30] (NaN ->
+ *     0) and converted to int32 (towards zero);  out_src = -1 - the annotation's global index;  out_label = cat_map[figure_cat];
+ *   then its words with word_label >= 0, in word order:  out_bbox = the word's box;  out_src = the word's global index;
+ *     out_label = cat_map[word_label] (-1 for a word_label >= n_cat).
+ *   page_status[p]   0: written; 2: the page's runs are not ascending inside their arrays ([0, n_out] for out_off) or
+ *     out_off[p + 1] - out_off[p] is not what the kernel counts: the page writes NOTHING.  Other pages are not affected.
+ * Ranks come from a workgroup prefix scan (wave ballot, popcount of the lower lanes, per-wave totals in LDS): no atomics, the order
+ * is exact.  out_bbox 16-byte aligned.
+ * Both: no allocation, no workspace, no synchronisation; null or misaligned pointers, sizes >= 2^31 - 1, n_cat outside 1 .. 32 or
+ * figure_cat outside [0, n_cat) return GTE_ERR_INVALID_ARGUMENT before any launch; n_pages == 0 is GTE_OK. */
+int gte_word_labels_chunk(void);            /* 1024 */
+int gte_word_labels(const int32_t* bbox, const int32_t* node_off, const double* ann_box, const int32_t* ann_cat,
+                    const int32_t* ann_off, int64_t n_pages, int64_t n_nodes, int64_t n_ann, int n_cat, uint32_t skip_mask,
+                    int figure_cat, int32_t* word_label, int32_t* word_ann, int32_t* page_counts, void* stream);
+int gte_word_labels_compact(const int32_t* bbox, const int32_t* node_off, const int32_t* word_label, const double* ann_box,
+                            const int32_t* ann_cat, const int32_t* ann_off, const int32_t* out_off, const int32_t* cat_map,
+                            int64_t n_pages, int64_t n_nodes, int64_t n_ann, int n_cat, int figure_cat, int64_t n_out,
+                            int32_t* out_bbox, int32_t* out_label, int32_t* out_src, int32_t* page_status, void* stream);
+
 /* ---- confidence of a page's FINAL blocks (after table assembly and figures; the reference's write_json gives every block 1.0,
  * postprocessing_2.py:337) ----
  * Inputs: bbox int32 [n_nodes, 4] the word boxes; logits float [n_nodes, .] the words' logit rows, row v at logits + v * ld_logits
