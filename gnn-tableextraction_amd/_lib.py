@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GTE_LIB_PATH: profiling builds of the same ABI (e.g. ablation variants); default = the in-tree library
@@ -83,6 +83,12 @@ SIGNATURES = {
     "gte_edge_weights_bbox": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                       c_int64, c_void_p]),
     "gte_bbox_features": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    # REPR node features (csrc/repr_features.hip)
+    "gte_repr_max_centroids": (c_int, []),
+    "gte_repr_max_dim": (c_int, []),
+    "gte_repr_max_out": (c_int, []),
+    "gte_repr_features": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
+                                  c_void_p, c_int64, c_void_p]),
     "gte_inv_degree": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_sage_linear_fwd": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int,

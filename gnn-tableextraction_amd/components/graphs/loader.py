@@ -89,7 +89,12 @@ class PrebuiltPages:
         (graph.bbox_features) -- what builder.get_graph + loader.modify_graphs + nlp/bbox.py do per page in Python.
         ``page_boxes[p]`` int [n_p, 4], ``page_sizes[p]`` = (width, height), ``page_texts[p]`` the words (for the character
         histogram; None -> empty texts), ``page_labels[p]`` converted class ids, ``extra_feats[p]`` optional float32 [n_p, F']
-        columns appended after the BBOX features (REPR / SPACY / SCIBERT embeddings stay pre-computed).
+        columns appended behind them (SPACY / SCIBERT embeddings, which need language models and stay pre-computed).
+        ``repr_embedder`` (keyword, default None): a ``components.nlp.repr.Repr``; its P REPR columns (50 in the reference) follow
+        the 13 BBOX columns and precede ``extra_feats`` -- the order of the reference's feature list -- computed on the device
+        (graph.repr_features) from the texts of the node lists.  Token j of a page belongs to node j of the list BEFORE island
+        removal (an empty word shifts the tokens of its page, as in the reference); the rows are then filtered as the BBOX rows
+        are.  None leaves every result as it was.
 
         ``page_annotations`` INSTEAD of ``page_labels`` (exactly one of the two, the other None): ``page_annotations[p]`` rows
         ``[x0, y0, x1, y1, category]`` with ORIGINAL category ids, what ``postprocessing.blocks_gt_json`` reads.  The node list
@@ -97,21 +102,23 @@ class PrebuiltPages:
         annotation that holds a word's centre, words inside a FIGURE dropped, every FIGURE a node "IMAGE!" in front of its
         page's words) and the path above runs on it; ``converted`` applies ``LableModification``'s conversion (False: original
         ids, ``num_classes`` 13).  ``extra_feats`` must then be a callable ``(page_texts, page_boxes) -> [n_p, F'] arrays`` of the
-        FINAL node lists: arrays per input word cannot line up once figure nodes are added and words dropped.
+        FINAL node lists: arrays per input word cannot line up once figure nodes are added and words dropped.  A
+        ``repr_embedder`` reads the texts of those node lists, ``"IMAGE!"`` for a figure node.
         ``pages[i]`` gains ``'annotations'`` (as given) and ``'texts'`` (of the final nodes)."""
+        repr_embedder = kw.pop('repr_embedder', None)
         if (page_labels is None) == (page_annotations is None):
             raise ValueError("from_boxes: exactly one of page_labels and page_annotations must be given, for all pages (got "
                              f"{'both' if page_labels is not None else 'neither'})")
         if page_annotations is not None:
             return cls._from_annotations(page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats,
                                          dict(k=k, max_dist=max_dist, bidirectional=bidirectional, range_island=range_island,
-                                              mode=mode), kw)
+                                              mode=mode), kw, repr_embedder=repr_embedder)
         return cls._from_node_lists(page_boxes, page_sizes, page_texts, page_labels, device, k, max_dist, bidirectional,
-                                    range_island, extra_feats, mode, kw)[0]
+                                    range_island, extra_feats, mode, kw, repr_embedder=repr_embedder)[0]
 
     @classmethod
     def _from_node_lists(cls, page_boxes, page_sizes, page_texts, page_labels, device, k, max_dist, bidirectional, range_island,
-                         extra_feats, mode, kw, extra_feats_fn=None):
+                         extra_feats, mode, kw, extra_feats_fn=None, repr_embedder=None):
         """from_boxes for node lists that carry their labels -> (dataset, keep: bool [N] on the device over the given nodes).
         ``extra_feats_fn(page_texts, page_boxes)``: the extra columns as a callable on the node lists that are left after island
         removal."""
@@ -128,6 +135,8 @@ class PrebuiltPages:
                                          mode=mode)                  # PREPROCESS.mode: 'knn' | 'visibility' (loader.py:80)
         texts = page_texts if page_texts is not None else [[""] * n for n in sizes]
         feat = Bbox(device).features(page_boxes, texts)[keep]
+        if repr_embedder is not None:                      # [BBOX | REPR | extra]: the order of the reference's feature list
+            feat = torch.cat([feat, repr_embedder.features(texts)[keep]], dim=1)
         if extra_feats is not None:
             extra = torch.from_numpy(np.concatenate([np.asarray(e, dtype=np.float32) for e in extra_feats])).to(device)[keep]
             feat = torch.cat([feat, extra], dim=1)
@@ -189,7 +198,8 @@ class PrebuiltPages:
                 np.asarray(off, dtype=np.int64))
 
     @classmethod
-    def _from_annotations(cls, page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats, graph_kw, kw):
+    def _from_annotations(cls, page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats, graph_kw, kw,
+                          repr_embedder=None):
         from ... import graph as G
         n_pages = len(page_boxes)
         ann_box, ann_cat, ann_off = cls.check_annotations(page_annotations, n_pages)
@@ -218,7 +228,7 @@ class PrebuiltPages:
             kw.setdefault('num_classes', len(ORIGIN_TO_CONV))
         out, keep = cls._from_node_lists(new_boxes, page_sizes, new_texts, new_labels, device, graph_kw['k'], graph_kw['max_dist'],
                                          graph_kw['bidirectional'], graph_kw['range_island'], None, graph_kw['mode'], kw,
-                                         extra_feats_fn=extra_feats)
+                                         extra_feats_fn=extra_feats, repr_embedder=repr_embedder)
         keep_h = keep.cpu().numpy()
         for p in range(n_pages):
             o0, o1 = int(off_h[p]), int(off_h[p + 1])

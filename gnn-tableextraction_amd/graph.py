@@ -717,6 +717,42 @@ def bbox_features(bbox: torch.Tensor, char_counts: torch.Tensor) -> torch.Tensor
     return out
 
 
+def repr_features(node_tok: torch.Tensor, embeddings: torch.Tensor, centers: torch.Tensor, i_proto: torch.Tensor,
+                  alpha: float = 1.0, combined: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The REPR node features of src/components/nlp/repr.py:75-87, 111-139 as float32 [N, P] in one launch of gte_repr_features
+    (the rule is stated in include/gte.h): ``node_tok`` int32 [N] token ids with -1 for "no token" (a row of zeros),
+    ``embeddings`` float64 [V, D], ``centers`` float64 [C, D], ``i_proto`` float64 [C, P].  Normalising and looking up the words is
+    string work and stays on the host (components/nlp/repr.py); every arithmetic step runs on the device.
+    ``out``: a float32 [N, P] device tensor with unit column stride to write into -- usually a column slice of a wider feature
+    matrix, of which nothing outside the slice is touched; None allocates one."""
+    _lib.require_device(node_tok, "repr_features")
+    tables = (("embeddings", embeddings), ("centers", centers), ("i_proto", i_proto))
+    for name, t in tables:
+        _lib.require_device(t, f"repr_features: {name}")
+        if t.dtype != torch.float64 or t.dim() != 2:
+            raise ValueError(f"repr_features: {name} must be a float64 matrix, got {t.dtype} {tuple(t.shape)}")
+    if centers.shape[1] != embeddings.shape[1] or i_proto.shape[0] != centers.shape[0]:
+        raise ValueError(f"repr_features: embeddings {tuple(embeddings.shape)}, centers {tuple(centers.shape)} and i_proto "
+                         f"{tuple(i_proto.shape)} do not fit together ([V, D], [C, D], [C, P])")
+    if node_tok.dim() != 1:
+        raise ValueError(f"repr_features: node_tok must be one id per node, got {tuple(node_tok.shape)}")
+    tok = node_tok.to(torch.int32).contiguous()
+    embeddings, centers, i_proto = (t.contiguous() for _, t in tables)
+    n, p = tok.shape[0], i_proto.shape[1]
+    if out is None:
+        out = torch.empty((n, p), dtype=torch.float32, device=tok.device)
+    else:
+        _lib.require_device(out, "repr_features: out")
+        if out.dtype != torch.float32 or tuple(out.shape) != (n, p) or (n > 0 and p > 0 and out.stride(1) != 1):
+            raise ValueError(f"repr_features: out must be float32 [{n}, {p}] with unit column stride, got {out.dtype} "
+                             f"{tuple(out.shape)} strides {out.stride()}")
+    ldo = out.stride(0) if n > 1 else max(p, 1)
+    _lib.check(_lib.load().gte_repr_features(_lib.ptr(tok), n, _lib.ptr(embeddings), embeddings.shape[0], embeddings.shape[1],
+                                             _lib.ptr(centers), _lib.ptr(i_proto), centers.shape[0], p, float(alpha),
+                                             int(bool(combined)), _lib.ptr(out), ldo, _lib.current_stream()), "gte_repr_features")
+    return out
+
+
 def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, max_dist: int = 500, bidirectional: bool = True,
                          labels: Optional[torch.Tensor] = None, range_island: int = 0, text_label: int = 1,
                          edge_features: bool = True, mode: str = "knn"):

@@ -393,6 +393,30 @@ int gte_edge_weights_bbox(const int32_t* bbox, const int32_t* src, const int32_t
  * float64 arithmetic as the reference, stored as float32.  Bit-exact vs the host formula. */
 int gte_bbox_features(const int32_t* bbox, const int32_t* char_counts, float* out, int64_t ldo, int64_t n_nodes,
                       void* stream);
+/* REPR node features (replaces Repr.get_similarity and the per-page loop of Repr.__call__, nlp/repr.py:75-87, 111-139, called at
+ * model_train.py:293).  node_tok int32 [n_nodes]: the id of every word's normalised token, -1 for a node without one;
+ * embeddings double [n_vocab, dim]; centers double [n_centroids, dim]; i_proto double [n_centroids, n_out]; all packed.
+ * For a word with token row e, all in float64:
+ *   d_c = sqrt(sum_k (e_k - c_k)^2)   k = 0 .. dim-1 in that order, product and sum rounded separately
+ *   t_c = max(d_c, 1e-4);  w_c = pow(1 / t_c, alpha)  (alpha == 1: 1 / t_c as it stands);  s = sum_c w_c in the order c = 0 .. C-1;
+ *   q_c = w_c / s.
+ * combined == 0: out[i, 0:n_out] = (float)i_proto[c*, :] with c* the FIRST index at which q is largest -- every centre closer
+ *   than 1e-4 ties, and the lowest index of them wins even where a later centre matches exactly, as in the reference.
+ * combined == 1: out[i, j] = sum_c (float)q_c * (float)i_proto[c, j], float32 FMAs in the order c = 0 .. C-1.
+ * node_tok[i] == -1 -- or any id outside [0, n_vocab): the kernel reads no row it was not given -- writes a row of zeros.  Only the
+ * columns [0, n_out) of a row are written; row i starts at out + i * ldo, ldo >= n_out (a column slice of a wider feature matrix).
+ * One launch, one wave per word, centre c on lane c, the centres staged through LDS; no allocation, no workspace, no
+ * synchronisation.  Invalid arguments (null or misaligned pointers, negative sizes, dim / n_centroids / n_out < 1, ldo < n_out, a
+ * non-finite alpha, combined outside {0, 1}) return GTE_ERR_INVALID_ARGUMENT; above gte_repr_max_centroids() / _max_dim() /
+ * _max_out() the call returns GTE_ERR_UNSUPPORTED before any launch; n_nodes == 0 is GTE_OK with nothing launched.
+ * Limitation: the reference's torch.sum / torch.norm orders are not defined; a word whose two best clamped distances differ by less
+ * than about 1e-12 relative may be assigned differently there. */
+int gte_repr_max_centroids(void);   /* 64 */
+int gte_repr_max_dim(void);         /* 1024 */
+int gte_repr_max_out(void);         /* 1024 */
+int gte_repr_features(const int32_t* node_tok, int64_t n_nodes, const double* embeddings, int64_t n_vocab, int dim,
+                      const double* centers, const double* i_proto, int n_centroids, int n_out, double alpha,
+                      int combined, float* out, int64_t ldo, void* stream);
 /* inv_deg[v] = 1/(indptr[v+1]-indptr[v]) or 0  (models.py:74-78 as a standalone vector) */
 int gte_inv_degree(const int32_t* indptr, float* inv_deg, int64_t n_nodes, void* stream);
 
