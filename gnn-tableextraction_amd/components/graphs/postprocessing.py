@@ -342,6 +342,33 @@ def assemble_tables(blocks, labels):
     return blocks, labels, headers
 
 
+def _block_launch_inputs(what, bbox, node_off, block_box, block_off, per_word, per_block):
+    """The input check of the two block launches (``what``: "block_vote" / "block_scores"): ``bbox`` int32 [n, 4] and
+    ``block_box`` float64 [B, 4] on one device, with the caller's own tensors of one row per word / per block (``per_word`` /
+    ``per_block``: name -> tensor; their dtype and rank are the caller's to check, before this); the two host offset sequences
+    partition the words and the blocks into the same pages.  ``ValueError`` otherwise; the offsets are the first device access.
+    Returns (device, n, B, pages, the two int32 offset tensors on the device, the largest page's word count, its block count)."""
+    named = {"bbox": bbox, **per_word, "block_box": block_box, **per_block}
+    for t in named.values():
+        _lib.require_device(t, what)
+    if bbox.dtype != torch.int32 or block_box.dtype != torch.float64:
+        raise ValueError(f"{what}: bbox {bbox.dtype} must be int32, block_box {block_box.dtype} float64")
+    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 \
+            or any(t.shape[0] != bbox.shape[0] for t in per_word.values()) \
+            or any(t.shape[0] != block_box.shape[0] for t in per_block.values()):
+        raise ValueError(f"{what}: " + ", ".join(f"{name} is {tuple(t.shape)}" for name, t in named.items()))
+    dev = bbox.device
+    if any(t.device != dev for t in named.values()):
+        raise ValueError(f"{what}: {', '.join(named)} live on different devices")
+    n, nb = bbox.shape[0], block_box.shape[0]
+    no, d_no = _lib.partition_offsets(node_off, n, f"{what}: the word offsets", dev)
+    bo, d_bo = _lib.partition_offsets(block_off, nb, f"{what}: the block offsets", dev)
+    if no.size != bo.size:
+        raise ValueError(f"{what}: offsets of {no.size - 1} / {bo.size - 1} pages do not partition the words and the blocks")
+    pages = no.size - 1
+    return dev, n, nb, pages, d_no, d_bo, int(np.diff(no).max()) if pages else 0, int(np.diff(bo).max()) if pages else 0
+
+
 class BlockVote(NamedTuple):
     """Result of :func:`block_vote`."""
     word_block: torch.Tensor  # int32 [n]        global index of the word's block, -1 for a word outside every block
@@ -361,33 +388,19 @@ def block_vote(bbox: torch.Tensor, node_off, word_cat: torch.Tensor, block_box: 
     of its category if that is ``double_cat`` (TITLE; -1: none), else 1; a category outside ``[0, n_cat)`` casts no vote.
     Raises ``ValueError`` on shapes, dtypes or offsets that do not fit, ``GteError`` when a page has more than
     ``gte_block_vote_max_page_blocks()`` blocks.  No synchronisation."""
-    _lib.require_device(bbox, "block_vote")
-    _lib.require_device(word_cat, "block_vote")
-    _lib.require_device(block_box, "block_vote")
     lib, P = _lib.load(), _lib.ptr
-    dev = bbox.device
-    if bbox.dtype != torch.int32 or word_cat.dtype != torch.int32 or block_box.dtype != torch.float64:
-        raise ValueError(f"block_vote: bbox {bbox.dtype} and word_cat {word_cat.dtype} must be int32, block_box {block_box.dtype} float64")
-    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 or word_cat.dim() != 1 \
-            or word_cat.shape[0] != bbox.shape[0]:
-        raise ValueError(f"block_vote: bbox is {tuple(bbox.shape)}, word_cat {tuple(word_cat.shape)}, block_box {tuple(block_box.shape)}")
-    if word_cat.device != dev or block_box.device != dev:
-        raise ValueError("block_vote: bbox, word_cat and block_box live on different devices")
-    n, nb = bbox.shape[0], block_box.shape[0]
-    no, d_no = _lib.partition_offsets(node_off, n, "block_vote: the word offsets", dev)
-    bo, d_bo = _lib.partition_offsets(block_off, nb, "block_vote: the block offsets", dev)
-    if no.size != bo.size:
-        raise ValueError(f"block_vote: offsets of {no.size - 1} / {bo.size - 1} pages do not partition the words and the blocks")
+    if word_cat.dtype != torch.int32 or word_cat.dim() != 1:
+        raise ValueError(f"block_vote: word_cat {word_cat.dtype} {tuple(word_cat.shape)} must be int32 [n]")
+    dev, n, nb, pages, d_no, d_bo, _, max_blocks = _block_launch_inputs("block_vote", bbox, node_off, block_box, block_off,
+                                                                        {"word_cat": word_cat}, {})
     if not 1 <= int(n_cat) <= lib.gte_block_vote_max_categories():
         raise ValueError(f"block_vote: n_cat = {n_cat} outside 1 .. {lib.gte_block_vote_max_categories()}")
-    pages = no.size - 1
     bbox, word_cat, block_box = bbox.contiguous(), word_cat.contiguous(), block_box.contiguous()
     word_block = torch.empty(n, dtype=torch.int32, device=dev)
     votes = torch.empty((nb, int(n_cat)), dtype=torch.int32, device=dev)
     label = torch.empty(nb, dtype=torch.int32, device=dev)
-    _lib.check(lib.gte_block_vote(P(bbox), P(d_no), P(word_cat), P(block_box), P(d_bo), pages, n, nb,
-                                  int(np.diff(bo).max()) if pages else 0, int(n_cat), int(double_cat), P(word_block), P(votes),
-                                  P(label), _lib.current_stream()), "gte_block_vote")
+    _lib.check(lib.gte_block_vote(P(bbox), P(d_no), P(word_cat), P(block_box), P(d_bo), pages, n, nb, max_blocks, int(n_cat),
+                                  int(double_cat), P(word_block), P(votes), P(label), _lib.current_stream()), "gte_block_vote")
     return BlockVote(word_block, votes, label)
 
 
@@ -501,30 +514,17 @@ def block_scores(bbox: torch.Tensor, node_off, logits: torch.Tensor, block_box: 
     within 2^-18 of the mean; a row with a non-finite logit adds 0), 1.0 for a block no word meets.  Raises ``ValueError`` on
     shapes, dtypes or offsets that do not fit, ``GteError`` when a page exceeds ``gte_block_scores_max_page_blocks()`` blocks
     or ``gte_block_scores_max_page_words()`` words.  No synchronisation."""
-    for t in (bbox, logits, block_box, block_cat):
-        _lib.require_device(t, "block_scores")
     lib, P = _lib.load(), _lib.ptr
-    dev = bbox.device
-    if bbox.dtype != torch.int32 or block_cat.dtype != torch.int32 or block_box.dtype != torch.float64 or logits.dtype != torch.float32:
-        raise ValueError(f"block_scores: bbox {bbox.dtype} and block_cat {block_cat.dtype} must be int32, block_box {block_box.dtype} "
-                         f"float64, logits {logits.dtype} float32")
-    if bbox.dim() != 2 or bbox.shape[1] != 4 or block_box.dim() != 2 or block_box.shape[1] != 4 or block_cat.dim() != 1 \
-            or block_cat.shape[0] != block_box.shape[0] or logits.dim() != 2 or logits.shape[0] != bbox.shape[0]:
-        raise ValueError(f"block_scores: bbox is {tuple(bbox.shape)}, logits {tuple(logits.shape)}, block_box {tuple(block_box.shape)}, "
-                         f"block_cat {tuple(block_cat.shape)}")
-    if logits.device != dev or block_box.device != dev or block_cat.device != dev:
-        raise ValueError("block_scores: bbox, logits, block_box and block_cat live on different devices")
+    if logits.dtype != torch.float32 or logits.dim() != 2 or block_cat.dtype != torch.int32 or block_cat.dim() != 1:
+        raise ValueError(f"block_scores: logits {logits.dtype} {tuple(logits.shape)} must be float32 [n, C], block_cat {block_cat.dtype} "
+                         f"{tuple(block_cat.shape)} int32 [B]")
     masks = np.ascontiguousarray(np.asarray(cat_classes, dtype=np.uint32).reshape(-1))
     if not 1 <= logits.shape[1] <= lib.gte_block_scores_max_classes():
         raise ValueError(f"block_scores: {logits.shape[1]} classes outside 1 .. {lib.gte_block_scores_max_classes()}")
     if not 1 <= masks.size <= lib.gte_block_scores_max_categories():
         raise ValueError(f"block_scores: {masks.size} class masks outside 1 .. {lib.gte_block_scores_max_categories()}")
-    n, nb = bbox.shape[0], block_box.shape[0]
-    no, d_no = _lib.partition_offsets(node_off, n, "block_scores: the word offsets", dev)
-    bo, d_bo = _lib.partition_offsets(block_off, nb, "block_scores: the block offsets", dev)
-    if no.size != bo.size:
-        raise ValueError(f"block_scores: offsets of {no.size - 1} / {bo.size - 1} pages do not partition the words and the blocks")
-    pages = no.size - 1
+    dev, n, nb, pages, d_no, d_bo, max_words, max_blocks = _block_launch_inputs(
+        "block_scores", bbox, node_off, block_box, block_off, {"logits": logits}, {"block_cat": block_cat})
     if logits.stride(1) != 1 and logits.shape[0] > 0:
         logits = logits.contiguous()
     ld = int(logits.stride(0)) if logits.shape[0] > 1 else int(logits.shape[1])
@@ -533,9 +533,8 @@ def block_scores(bbox: torch.Tensor, node_off, logits: torch.Tensor, block_box: 
     score = torch.empty(nb, dtype=torch.float32, device=dev)
     n_words = torch.empty(nb, dtype=torch.int32, device=dev)
     _lib.check(lib.gte_block_scores(P(bbox), P(d_no), P(logits), ld, int(logits.shape[1]), P(block_box), P(d_bo), P(block_cat),
-                                    P(d_masks), masks.size, pages, n, nb, int(np.diff(no).max()) if pages else 0,
-                                    int(np.diff(bo).max()) if pages else 0, P(score), P(n_words), _lib.current_stream()),
-               "gte_block_scores")
+                                    P(d_masks), masks.size, pages, n, nb, max_words, max_blocks, P(score), P(n_words),
+                                    _lib.current_stream()), "gte_block_scores")
     return BlockScores(score, n_words)
 
 

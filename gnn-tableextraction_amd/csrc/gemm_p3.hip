@@ -1531,14 +1531,6 @@ TnPlan tn_plan(int64_t M, int64_t N, int64_t Nseg, int64_t K) {
     return pl;
 }
 
-// a kernel's dynamic-LDS limit, raised the first time its launcher runs (`done`: the launcher's own static flag)
-template <typename K>
-inline void set_lds_once(bool& done, K* kernel, int bytes) {
-    if (done) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done = true;
-}
-
 }  // namespace
 
 extern "C" int64_t gte_p3_row_bytes(int64_t cols) { return cols > 0 ? p3::row_bytes(cols) : 0; }
@@ -1666,8 +1658,8 @@ template <int WM, int WN, int TM, int TN, int NBUF, int WGS>
 void launch_ring(const P3Gemm& p, hipStream_t s) {
     constexpr int NW = WM * WN, BM = WM * TM * 32, BN = WN * TN * 32;
     constexpr int NI = ((BM + BN) * 96 / 1024 + NW - 1) / NW, shm = NBUF * NI * NW * 1024;
-    static bool configured = false;
-    set_lds_once(configured, &gemm_p3_nt_ring_kernel<WM, WN, TM, TN, NBUF, WGS>, shm);
+    static gte::LdsOptIn opt_in;
+    gte::allow_dynamic_lds(opt_in, &gemm_p3_nt_ring_kernel<WM, WN, TM, TN, NBUF, WGS>, shm);
     const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, BN)));
     hipLaunchKernelGGL((gemm_p3_nt_ring_kernel<WM, WN, TM, TN, NBUF, WGS>), grid, dim3(NW * 64), shm, s, p);
 }
@@ -1678,8 +1670,8 @@ void launch_lw(const P3Gemm& p, hipStream_t s) {
     constexpr int NI = ((BM + BN) * 96 / 1024 + NL - 1) / NL, shm = 3 * NI * NL * 1024;
     static_assert(LNB == 0 || (BN == 256 && shm >= TM * 32 * 256 * 4 && shm >= WM * WN * 3 * 256 * 4),
                   "the epilogue's row slice lives in the stage images");
-    static bool configured = false;
-    set_lds_once(configured, &gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, LNB, BIG>, shm);
+    static gte::LdsOptIn opt_in;
+    gte::allow_dynamic_lds(opt_in, &gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, LNB, BIG>, shm);
     const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, BN)));
     hipLaunchKernelGGL((gemm_p3_nt_lw_kernel<WM, WN, TM, TN, NL, LNB, BIG>), grid, dim3((WM * WN + NL) * 64), shm, s, p);
 }
@@ -1688,8 +1680,8 @@ template <int TM, int NL, int LNB>
 void launch_sq(const P3Gemm& p, hipStream_t s) {
     constexpr int BM = TM * 32, shm = 3 * 4 * BM * 96 + 1024;
     static_assert(LNB == 0 || (shm >= BM * 256 * 4 && shm >= 8 * 3 * 256 * 4), "the epilogue's row slice lives in the slots");
-    static bool configured = false;
-    set_lds_once(configured, &gemm_p3_nt_sq_kernel<TM, NL, LNB>, shm);
+    static gte::LdsOptIn opt_in;
+    gte::allow_dynamic_lds(opt_in, &gemm_p3_nt_sq_kernel<TM, NL, LNB>, shm);
     const dim3 grid((unsigned)(gte::ceil_div(p.M, BM) * gte::ceil_div(p.N, 256)));
     hipLaunchKernelGGL((gemm_p3_nt_sq_kernel<TM, NL, LNB>), grid, dim3((8 + NL) * 64), shm, s, p);
 }
@@ -2059,8 +2051,8 @@ int gte::gemm_p3_nt_smallk_bwd(const P3NtOperands& op, const float* x, int64_t l
     p.ln_part = p.sk_part_dw + (int64_t)nb * n * K;
     hipStream_t s = gte::as_stream(stream);
     constexpr int shm = 160 * 1024;                             // the 128 x 256 ring tile (3 x 40 KB) + room for the whole fp32 tile
-    static bool configured = false;
-    set_lds_once(configured, &gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>, shm);
+    static gte::LdsOptIn opt_in;
+    gte::allow_dynamic_lds(opt_in, &gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>, shm);
     hipLaunchKernelGGL((gemm_p3_nt_ring_kernel<2, 4, 2, 2, 3, 1, 2>), dim3((unsigned)nb), dim3(512), shm, s, p);
     rc = gte::check_launch(name);
     if (rc != GTE_OK) return rc;
@@ -2143,10 +2135,10 @@ int gte::gemm_p3_tn(const P3TnOperands& o, float* c, int64_t ldc, int64_t m, int
     }
     const int64_t tiles = gte::ceil_div(m, 128) * (nseg > 0 ? 2 * gte::ceil_div(nseg, 128) : gte::ceil_div(n, 128));
     constexpr int shm_small = 3 * 6 * 4 * 1024;
-    static bool configured[3] = {};
-    set_lds_once(configured[0], &gemm_p3_tn_kernel<2, 2, 2>, shm_small);
-    set_lds_once(configured[1], &gemm_p3_tn_kernel<2, 2, 2, true>, shm_small);
-    set_lds_once(configured[2], &gemm_p3_tn_kernel<2, 2, 2, true, true>, shm_small);
+    static gte::LdsOptIn opt_in[3];
+    gte::allow_dynamic_lds(opt_in[0], &gemm_p3_tn_kernel<2, 2, 2>, shm_small);
+    gte::allow_dynamic_lds(opt_in[1], &gemm_p3_tn_kernel<2, 2, 2, true>, shm_small);
+    gte::allow_dynamic_lds(opt_in[2], &gemm_p3_tn_kernel<2, 2, 2, true, true>, shm_small);
     const dim3 grid((unsigned)(tiles * pl.splits));
     if (p.rowsB && p.rows64) hipLaunchKernelGGL((gemm_p3_tn_kernel<2, 2, 2, true, true>), grid, dim3(256), shm_small, s, p);
     else if (p.rowsB) hipLaunchKernelGGL((gemm_p3_tn_kernel<2, 2, 2, true>), grid, dim3(256), shm_small, s, p);

@@ -6,6 +6,8 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <atomic>
+
 #include "../../include/gte.h"
 
 namespace gte {
@@ -20,6 +22,22 @@ inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GTE_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
     return GTE_OK;
+}
+
+// A kernel's dynamic-LDS limit: more than 64 KB needs the opt-in once per kernel AND per device (a
+// process-wide flag configures only the device that is current at the first call, and a plain bool is written from threads whose
+// forced configurations are thread-local).  A launcher owns one static LdsOptIn per kernel instantiation and calls
+// allow_dynamic_lds ahead of the launch: one bit per device id 0 .. 63; any other id, or a failed hipGetDevice, sets the
+// attribute on every call.
+struct LdsOptIn { std::atomic<uint64_t> devices{0}; };
+template <typename K>
+inline void allow_dynamic_lds(LdsOptIn& state, K* kernel, int bytes) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    const bool tracked = dev >= 0 && dev < 64;
+    if (tracked && ((state.devices.load(std::memory_order_acquire) >> dev) & 1)) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (tracked) state.devices.fetch_or(uint64_t(1) << dev, std::memory_order_release);
 }
 
 constexpr int kWave = 64;          // gfx950 wavefront

@@ -306,12 +306,8 @@ extern "C" int gte_knn_select(const int32_t* bbox, const int32_t* node_off, cons
     if (!bbox || !node_off || !page_size || !sel) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "knn_select: null pointer");
     if (((uintptr_t)bbox & 15) != 0) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "knn_select: bbox must be 16-byte aligned");
     const size_t shm = (size_t)(max_page_nodes > 0 ? max_page_nodes : 1) * sizeof(Box);
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&knn_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  KNN_PAGE_MAX * (int)sizeof(Box));
-        configured = true;
-    }
+    static gte::LdsOptIn opt_in;
+    gte::allow_dynamic_lds(opt_in, &knn_select_kernel, KNN_PAGE_MAX * (int)sizeof(Box));
     hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)gte::ceil_div(max_page_nodes > 0 ? max_page_nodes : 1, 256), (unsigned)n_pages),
                        dim3(256), shm, gte::as_stream(stream), bbox, node_off, page_size, k, max_dist, sel);
     return gte::check_launch("knn_select");
@@ -330,14 +326,9 @@ extern "C" int gte_visibility_select(const int32_t* bbox, const int32_t* node_of
     if ((((uintptr_t)bbox | (uintptr_t)sel) & 15) != 0)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "visibility_select: bbox and sel must be 16-byte aligned");
     const size_t shm = (size_t)(max_page_nodes > 0 ? max_page_nodes : 1) * sizeof(Box);
-    static bool configured = false;
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vis_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  KNN_PAGE_MAX * (int)sizeof(Box));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&vis_prune_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  KNN_PAGE_MAX * (int)sizeof(VisNode));
-        configured = true;
-    }
+    static gte::LdsOptIn opt_in_select, opt_in_prune;
+    gte::allow_dynamic_lds(opt_in_select, &vis_select_kernel, KNN_PAGE_MAX * (int)sizeof(Box));
+    gte::allow_dynamic_lds(opt_in_prune, &vis_prune_kernel, KNN_PAGE_MAX * (int)sizeof(VisNode));
     const dim3 grid((unsigned)gte::ceil_div(max_page_nodes > 0 ? max_page_nodes : 1, 256), (unsigned)n_pages);
     hipStream_t s = gte::as_stream(stream);
     hipLaunchKernelGGL(vis_select_kernel, grid, dim3(256), shm, s, bbox, node_off, page_size, max_dist, sel);

@@ -25,7 +25,6 @@
 #include "gte_common.h"
 #include "word_score.h"
 
-#include <atomic>
 #include <climits>
 
 namespace {
@@ -149,21 +148,6 @@ page_regions_kernel(const int32_t* __restrict__ indptr, const int32_t* __restric
     }
 }
 
-// > 64 KB of dynamic LDS needs the opt-in once per kernel AND per device (a process-wide flag configures only
-// the device that is current at the first call): one bit per device id and instantiation, ids past the mask set the attribute
-// every time.
-template <bool SCORED>
-void allow_region_lds() {
-    static std::atomic<uint64_t> configured{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    const bool tracked = dev >= 0 && dev < 64;
-    if (tracked && ((configured.load(std::memory_order_acquire) >> dev) & 1)) return;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&page_regions_kernel<SCORED>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              SCORED ? REGION_LDS_MAX_SCORED : REGION_LDS_MAX);
-    if (tracked) configured.fetch_or(uint64_t(1) << dev, std::memory_order_release);
-}
-
 // the checks and the launch of both entries (SCORED: + the three score arguments)
 template <bool SCORED>
 int page_regions_launch(const char* what, const int32_t* indptr, const int32_t* indices, const int32_t* node_off, int64_t n_pages,
@@ -185,7 +169,8 @@ int page_regions_launch(const char* what, const int32_t* indptr, const int32_t* 
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: logits and region_score must be 4-byte aligned", what);
     const int cap = (int)(max_page_nodes > 0 ? max_page_nodes : 1);
     const size_t shm = (size_t)cap * region_node_bytes(SCORED) + REGION_TAIL_BYTES;
-    allow_region_lds<SCORED>();
+    static gte::LdsOptIn opt_in;                          // (one per instantiation)
+    gte::allow_dynamic_lds(opt_in, &page_regions_kernel<SCORED>, SCORED ? REGION_LDS_MAX_SCORED : REGION_LDS_MAX);
     hipLaunchKernelGGL(page_regions_kernel<SCORED>, dim3((unsigned)n_pages), dim3(REGION_THREADS), shm, gte::as_stream(stream), indptr,
                        indices, node_off, group, bbox, cap, (int)n_nodes, comp, region_box, region_count, logits, n_classes,
                        class_group, region_score);

@@ -816,25 +816,16 @@ bool plan_tail(GemmParams& p, int tiles, dim3& grid) {
 template <bool AK, bool BKC, int BM, int BN, int WM, int WN>
 void launch_tile(GemmParams p, dim3 grid, hipStream_t s) {
     constexpr int shm = gemm_lds_bytes<AK, BKC, BM, BN>();
-    static bool configured = false;                       // > 64 KB of dynamic LDS needs the opt-in, once per kernel
-    if (!configured) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_mfma_kernel<AK, BKC, BM, BN, WM, WN>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, shm);
-        configured = true;
-    }
+    static gte::LdsOptIn opt_in;                          // (one per instantiation, as the two below)
+    gte::allow_dynamic_lds(opt_in, &gemm_f32_mfma_kernel<AK, BKC, BM, BN, WM, WN>, shm);
     const int tiles = (int)grid.x;
     const bool tail = plan_tail<BM, BN>(p, tiles, grid);
     if constexpr (BN == 128 && (BM == 128 || BM == 64) && WM == 2 && WN == 2) {
         if (gemm_mode() == GTE_GEMM_SPLIT_BF16) {
             constexpr int shm_s = gemm_split_lds_bytes<AK, BKC, BM, BN>();
-            static bool configured_s = false;
-            if (!configured_s) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_kernel<AK, BKC, BM, BN, true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, shm_s);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_split_kernel<AK, BKC, BM, BN, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, shm_s);
-                configured_s = true;
-            }
+            static gte::LdsOptIn opt_in_ktail, opt_in_plain;
+            gte::allow_dynamic_lds(opt_in_ktail, &gemm_split_kernel<AK, BKC, BM, BN, true>, shm_s);
+            gte::allow_dynamic_lds(opt_in_plain, &gemm_split_kernel<AK, BKC, BM, BN, false>, shm_s);
             // K-contiguous operands with a K range that is not a multiple of 4 need the chunk tail masks
             const bool ktail = (AK || BKC) && (p.K1 % 4 != 0 || p.K2 % 4 != 0);
             if (ktail) hipLaunchKernelGGL((gemm_split_kernel<AK, BKC, BM, BN, true>), grid, dim3(256), shm_s, s, p);

@@ -8,29 +8,26 @@
 // output is an integer and compared exactly.
 //
 // Structure.  Two launches with the caller's cumulative sum between them, one workgroup per page in both.
-//   word_labels_kernel   the page's annotations go through LDS in chunks of WL_CHUNK rectangles (32 bytes each); an annotation
-//       that is passed over is stored as four NaNs, so it contains nothing and indices stay aligned.  Words are strided over the
-//       workgroup; a word scans a chunk four annotations at a time -- every lane reads the same LDS address, a broadcast -- and
-//       stops after the group that holds its first hit; it still meets the barriers that restage LDS for the later chunks.  The
-//       test is four strict fp64 comparisons on exact values: no arithmetic, nothing to round.  The page's two counts are LDS
-//       integer atomics on per-thread partial counts: the sums do not depend on the order of arrival.
+//   word_labels_kernel   the page-box skeleton of page_boxes.h, the table restaged per chunk: the page's annotations go through
+//       LDS WL_CHUNK rectangles at a time, AS GIVEN (no normalisation); an annotation that is passed over is stored as four NaNs,
+//       so it contains nothing and indices stay aligned.  A word takes the first hit of each chunk's table until it has one; it
+//       still meets the barriers that restage LDS for the later chunks.  The page's two counts are LDS integer atomics on
+//       per-thread partial counts: the sums do not depend on the order of arrival.
 //   word_labels_compact_kernel   counts the page's figures and kept words (wave ballots), compares with the caller's run of
 //       out_off, and only then writes: tiles of WL_THREADS candidates, a candidate's rank = the running base + the totals of the
 //       lower waves (LDS) + the number of lower lanes of its wave that hold one (ballot, popcount).  No atomics: the order is exact.
 // No float atomics, no allocation, no synchronisation.
-#include "gte_common.h"
+#include "page_boxes.h"
 
 namespace {
 
-constexpr int WL_THREADS = 1024;                      // a page has hundreds of words, the largest a few thousand
+namespace pb = page_boxes;
+constexpr int WL_THREADS = pb::kThreads;
 constexpr int WL_WAVES = WL_THREADS / gte::kWave;
 constexpr int WL_CHUNK = 1024;                        // annotations in LDS at a time: 32 KB
-constexpr int WL_SCAN = 4;                            // annotations a word tests between two looks at its result
 constexpr int WL_MAX_CAT = 32;                        // skip_mask is 32 bits
-static_assert(WL_CHUNK % WL_SCAN == 0, "a chunk is whole scan groups");
-static_assert(WL_CHUNK * 32 + 64 <= 48 * 1024, "a chunk fits LDS without an opt-in attribute");
-
-__device__ __forceinline__ bool run_ok(int lo, int hi, int n) { return lo >= 0 && hi >= lo && hi <= n; }
+static_assert(WL_CHUNK % pb::kScan == 0, "a chunk is whole scan groups");
+static_assert(WL_CHUNK * pb::kRowBytes + 64 <= 48 * 1024, "a chunk fits LDS without an opt-in attribute");
 
 // popcount of the bits of `mask` below the calling lane
 __device__ __forceinline__ int lower_lanes(unsigned long long mask) {
@@ -48,15 +45,14 @@ word_labels_kernel(const int32_t* __restrict__ bbox, const int32_t* __restrict__
     const int tid = threadIdx.x;
     const int p = blockIdx.x;
     const int n0 = node_off[p], n1 = node_off[p + 1], a0 = ann_off[p], a1 = ann_off[p + 1];
-    if (!run_ok(n0, n1, n_nodes) || !run_ok(a0, a1, n_ann)) {            // offsets that name no row: nothing to label
+    if (!pb::run_ok(n0, n1, n_nodes) || !pb::run_ok(a0, a1, n_ann)) {            // offsets that name no row: nothing to label
         if (tid < 2) page_counts[2 * (int64_t)p + tid] = 0;
         return;
     }
     const int N = n1 - n0, A = a1 - a0;
     const int n_chunks = (A + WL_CHUNK - 1) / WL_CHUNK;
     const int n_tiles = N > 0 ? (N + WL_THREADS - 1) / WL_THREADS : 1;   // a page without words still counts its figures
-    const double q = __longlong_as_double(0x7ff8000000000000ll);
-    const double2* s_corner = reinterpret_cast<const double2*>(s_box);   // [2 j] = (r0, r1), [2 j + 1] = (r2, r3)
+    const double q = pb::quiet_nan();
     if (tid < 2) s_count[tid] = 0;
     int figures = 0, kept = 0;
 
@@ -73,33 +69,24 @@ word_labels_kernel(const int32_t* __restrict__ bbox, const int32_t* __restrict__
         for (int c = 0; c < n_chunks; ++c) {
             const int c0 = c * WL_CHUNK;
             const int len = min(WL_CHUNK, A - c0);
-            const int rows = (len + WL_SCAN - 1) / WL_SCAN * WL_SCAN;
             if (t == 0 || n_chunks > 1) {                                // a page of one chunk is staged once for all its tiles
                 if (t > 0 || c > 0) __syncthreads();                     // every word is done with the chunk that is in LDS
-                for (int j = tid; j < rows; j += WL_THREADS) {
+                for (int j = tid; j < len; j += WL_THREADS) {
                     double r0 = q, r1 = q, r2 = q, r3 = q;
-                    if (j < len) {
-                        const int cat = ann_cat[a0 + c0 + j];
-                        if (t == 0 && cat == figure_cat) ++figures;
-                        if (cat >= 0 && cat < n_cat && !((skip_mask >> cat) & 1u)) {
-                            const double* src = ann_box + (int64_t)(a0 + c0 + j) * 4;
-                            r0 = src[0]; r1 = src[1]; r2 = src[2]; r3 = src[3];
-                        }
+                    const int cat = ann_cat[a0 + c0 + j];
+                    if (t == 0 && cat == figure_cat) ++figures;
+                    if (cat >= 0 && cat < n_cat && !((skip_mask >> cat) & 1u)) {
+                        const double* src = ann_box + (int64_t)(a0 + c0 + j) * 4;
+                        r0 = src[0]; r1 = src[1]; r2 = src[2]; r3 = src[3];
                     }
                     s_box[j * 4 + 0] = r0; s_box[j * 4 + 1] = r1; s_box[j * 4 + 2] = r2; s_box[j * 4 + 3] = r3;
                 }
+                pb::pad_scan_group(s_box, len);
                 __syncthreads();
             }
             if (word && hit < 0) {
-                // WL_SCAN annotations at a time, their loads independent of the tests; inside a group the descending order
-                // leaves the lowest hit
-                for (int j0 = 0; j0 < rows && hit < 0; j0 += WL_SCAN) {
-#pragma unroll
-                    for (int u = WL_SCAN - 1; u >= 0; --u) {
-                        const double2 lo = s_corner[2 * (j0 + u)], hi = s_corner[2 * (j0 + u) + 1];
-                        if (cx > lo.x && cx < hi.x && cy > lo.y && cy < hi.y) hit = c0 + j0 + u;
-                    }
-                }
+                const int h = pb::first_hit(pb::corners(s_box), len, pb::HoldsCentre{cx, cy});
+                if (h >= 0) hit = c0 + h;
             }
         }
         if (word) {
@@ -168,7 +155,7 @@ word_labels_compact_kernel(const int32_t* __restrict__ bbox, const int32_t* __re
     const int tid = threadIdx.x;
     const int p = blockIdx.x;
     const int n0 = node_off[p], n1 = node_off[p + 1], a0 = ann_off[p], a1 = ann_off[p + 1], o0 = out_off[p], o1 = out_off[p + 1];
-    if (!run_ok(n0, n1, n_nodes) || !run_ok(a0, a1, n_ann)) {            // offsets that name no row: nothing to write
+    if (!pb::run_ok(n0, n1, n_nodes) || !pb::run_ok(a0, a1, n_ann)) {            // offsets that name no row: nothing to write
         if (tid == 0) page_status[p] = 2;
         return;
     }
@@ -183,7 +170,7 @@ word_labels_compact_kernel(const int32_t* __restrict__ bbox, const int32_t* __re
         const int i = i0 + tid;
         kept += block_count(i < N && word_label[n0 + i] >= 0, s_wave);
     }
-    if (!run_ok(o0, o1, n_out) || o1 - o0 != figures + kept) {           // the caller's run is not this page's: write nothing
+    if (!pb::run_ok(o0, o1, n_out) || o1 - o0 != figures + kept) {           // the caller's run is not this page's: write nothing
         if (tid == 0) page_status[p] = 2;
         return;
     }
@@ -220,7 +207,7 @@ word_labels_compact_kernel(const int32_t* __restrict__ bbox, const int32_t* __re
 }
 
 int check_sizes(const char* what, int64_t n_pages, int64_t n_nodes, int64_t n_ann, int n_cat, int figure_cat) {
-    if (n_pages < 0 || n_pages >= INT32_MAX || n_nodes < 0 || n_nodes >= INT32_MAX || n_ann < 0 || n_ann >= INT32_MAX)
+    if (!pb::counts_ok(n_pages, n_nodes, n_ann))
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: bad sizes", what);
     if (n_cat < 1 || n_cat > WL_MAX_CAT) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "%s: %d categories (1 .. %d)", what, n_cat, WL_MAX_CAT);
     if (figure_cat < 0 || figure_cat >= n_cat)
@@ -241,7 +228,7 @@ extern "C" int gte_word_labels(const int32_t* bbox, const int32_t* node_off, con
     if (!node_off || !ann_off || !page_counts || (n_nodes > 0 && (!bbox || !word_label || !word_ann)) ||
         (n_ann > 0 && (!ann_box || !ann_cat)))
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "word_labels: null pointer");
-    if (((uintptr_t)bbox & 15) != 0 || ((uintptr_t)ann_box & 7) != 0 ||
+    if (!pb::boxes_aligned(bbox, ann_box) ||
         (((uintptr_t)node_off | (uintptr_t)ann_off | (uintptr_t)ann_cat | (uintptr_t)word_label | (uintptr_t)word_ann |
           (uintptr_t)page_counts) & 3) != 0)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "word_labels: bbox must be 16-byte aligned, ann_box 8-byte, int32 arrays 4-byte");
@@ -257,12 +244,12 @@ extern "C" int gte_word_labels_compact(const int32_t* bbox, const int32_t* node_
                                        int64_t n_ann, int n_cat, int figure_cat, int64_t n_out, int32_t* out_bbox,
                                        int32_t* out_label, int32_t* out_src, int32_t* page_status, void* stream) {
     if (int rc = check_sizes("word_labels_compact", n_pages, n_nodes, n_ann, n_cat, figure_cat)) return rc;
-    if (n_out < 0 || n_out >= INT32_MAX) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "word_labels_compact: bad sizes");
+    if (!pb::counts_ok(n_out)) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "word_labels_compact: bad sizes");
     if (n_pages == 0) return GTE_OK;
     if (!node_off || !ann_off || !out_off || !page_status || (n_nodes > 0 && (!bbox || !word_label)) ||
         (n_ann > 0 && (!ann_box || !ann_cat)) || (n_out > 0 && (!out_bbox || !out_label || !out_src)))
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "word_labels_compact: null pointer");
-    if ((((uintptr_t)bbox | (uintptr_t)out_bbox) & 15) != 0 || ((uintptr_t)ann_box & 7) != 0 ||
+    if (!pb::boxes_aligned(bbox, ann_box) || ((uintptr_t)out_bbox & 15) != 0 ||
         (((uintptr_t)node_off | (uintptr_t)ann_off | (uintptr_t)ann_cat | (uintptr_t)word_label | (uintptr_t)out_off |
           (uintptr_t)cat_map | (uintptr_t)out_label | (uintptr_t)out_src | (uintptr_t)page_status) & 3) != 0)
         return gte::fail(GTE_ERR_INVALID_ARGUMENT,

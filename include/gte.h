@@ -17,7 +17,10 @@
  *     goes to that stream; no call synchronises.
  *   - return 0 on success, a negative gte_status otherwise; gte_last_error() returns a
  *     thread-local message for the last failure on the calling thread.
- *   - re-entrant and thread-safe (autograd calls backward from another thread).
+ *   - re-entrant and thread-safe (autograd calls backward from another thread).  Forced
+ *     configurations are thread-local (each setter says so); what a kernel needs from the
+ *     device it runs on -- the opt-in to more than 64 KB of dynamic LDS -- is made per DEVICE,
+ *     for the device that is current at the call: a process may drive several.
  *   - "ld*" arguments are leading dimensions in ELEMENTS (row stride); rows need only be
  *     4-byte aligned (F = 831 is a first-class shape), 16-byte alignment is faster.
  */

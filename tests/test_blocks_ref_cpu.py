@@ -6,6 +6,7 @@ import os
 import numpy as np
 
 from tests import blocks_ref as ref
+from tests import scan_group_cases as cases
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "blocks_cases.json")
 
@@ -62,6 +63,23 @@ def test_nan_blocks_meet_nothing_and_out_of_range_categories_cast_no_vote():
     word_block, votes, labels = ref.vote_page([[10, 10, 20, 20], [30, 30, 40, 40], [50, 50, 60, 60]], [3, -1, 13], blocks)
     assert word_block == [2, 2, 2] and votes[2] == [0, 0, 0, 1] + [0] * 9 and labels == [0, 0, 3]
     assert ref.vote_page([[10, 10, 20, 20]], [2], blocks, double_cat=-1)[1][2][2] == 1
+
+
+def test_the_scan_group_pages_fill_every_block_and_leave_words_outside():
+    """what the device tests on tests/scan_group_cases.py compare against is not empty: every block takes words, every page
+    leaves words in no block, and with the NaN corner the last block takes none"""
+    for nan_last in (False, True):
+        for k, (words, cats, blocks) in enumerate(cases.scan_group_pages(nan_last)):
+            n_blocks = k + 1
+            assert len(blocks) == n_blocks and len(words) == cases.WORDS > 64
+            word_block, votes, _ = ref.vote_page(words, cats, blocks)
+            live = n_blocks - 1 if nan_last else n_blocks
+            cell = cases.word_cells(k)
+            assert word_block == np.where(cell < live, cell, -1).tolist()
+            assert all(word_block.count(j) >= 1 and sum(votes[j]) >= 1 for j in range(live))
+            assert word_block.count(-1) >= 1
+            if nan_last:
+                assert np.isnan(blocks[-1]).sum() == 1 and word_block.count(n_blocks - 1) == 0 and not any(votes[-1])
 
 
 def test_synthetic_blocks_cover_most_words_and_leave_some_outside():

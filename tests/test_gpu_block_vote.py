@@ -10,6 +10,7 @@ import torch
 
 from gnn_tableextraction_amd import _lib
 from tests import blocks_ref as ref
+from tests import scan_group_cases as cases
 
 pytestmark = pytest.mark.gpu
 
@@ -185,6 +186,15 @@ def test_a_page_with_exactly_the_largest_block_count_and_one_block_too_many():
     assert (word_block[50:90] == -1).all() and not votes[3:12].any() and not label[3:12].any()
     np.testing.assert_array_equal(word_block[90:], np.where(alone[0] >= 0, alone[0] + 12, -1))
     np.testing.assert_array_equal(label[12:], alone[2])
+
+
+def test_block_counts_around_a_scan_group():
+    """tests/scan_group_cases.py: one launch of 9 pages of 1 .. 9 blocks, then the same launch with a NaN corner in every page's
+    last block (tests/test_blocks_ref_cpu.py shows that every live block takes words and every page leaves some outside)"""
+    for nan_last in (False, True):
+        pages = cases.scan_group_pages(nan_last)
+        want = _assert_equal_ref(pages)
+        assert (want[0] >= 0).any() and (want[0] < 0).any()
 
 
 def test_a_batch_of_20_uneven_pages_with_empty_ones_page_by_page():
