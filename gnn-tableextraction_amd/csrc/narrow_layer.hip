@@ -433,7 +433,8 @@ struct LnBackward {
 // out-edge CSR inside the kernel: 18 us of dependent loads for the 6 us launch it saved.  profiles/r03/gemm_p3.md keeps the numbers.)
 // MSK (with Ft < F): the rows are PADDED -- Ft true columns, zeros up to F (a multiple of 16): W is [C][2 Ft], the dW / LayerNorm
 // partials are written compact ([.][Ft]), the LayerNorm backward runs over the Ft true columns with per-element validity (the
-// arithmetic of ln_relu_bwd_gen_kernel, layernorm.hip: gte_ln_bwd_pre4m / _post4m of layernorm.h) and writes zeros into the padding of dz and of its image
+// arithmetic of ln_relu_bwd_gen_kernel, layernorm.hip: gte_ln_bwd_pre4m / _post4m of layernorm.h), writes zeros into dz up to the next multiple
+// of 4 columns (the columns beyond are not written: include/gte.h) and into all the padding of its image
 #ifndef NB_ABL
 #define NB_ABL 0          // measurement builds (profiles/debug/build_variant.sh): 1 no dW products, 2 no LayerNorm phase, 4 no dh products,
 #endif                    // 8 no dz stores, 16 no z loads, 32 no CE fold / alpha
@@ -1125,7 +1126,7 @@ extern "C" int gte_sage_narrow_bwd_ln_p3(const float* dl, int64_t lddl, const fl
 // gte_sage_narrow_bwd_ln_p3 on PADDED rows (gte_sage_narrow_fwd_pad): h / z_below / dz_below rows hold n_feat true columns and
 // zeros up to n_pad (a multiple of 16; the image dzp3 is ceil(n_feat / 16) = n_pad / 16 blocks wide); W, dW are the reference's
 // [C][2 n_feat]; the LayerNorm backward runs over the n_feat true columns (the arithmetic of gte_ln_relu_bwd_p3 at that width) and
-// writes zeros into the padding.  Workspaces as for n_pad.
+// writes zeros into dz_below up to the next multiple of 4 columns and into all the padding of the image.  Workspaces as for n_pad.
 extern "C" int gte_sage_narrow_bwd_ln_p3_pad(const float* dl, int64_t lddl, const float* q, int64_t ldq, const float* h, int64_t ldh,
                                              int64_t n_feat, int64_t n_pad, const float* W, int64_t ldw, int64_t n_out, float* dz_below,
                                              int64_t lddz, void* dzp3, int64_t ldp3, float* dW, int64_t lddw, float* dbias,

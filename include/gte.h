@@ -937,8 +937,11 @@ int gte_sage_narrow_bwd_ln_p3(const float* dl, int64_t lddl, const float* q, int
  * 149 / 157 / 206 / 218 of the reference's scaled runs -- keep the narrow kernels instead of three planes GEMMs): h, z_below and
  * dz_below rows hold n_feat true columns and zeros up to n_pad (a multiple of 16, <= 256); W / dW are the reference's [C][2 n_feat].
  * The products run over n_pad columns against a weight image whose padding is zero (the same sums); the fused LayerNorm backward
- * runs over the n_feat true columns with the arithmetic of gte_ln_relu_bwd_p3 at that width and writes zeros into the padding of
- * dz_below and of its image (n_pad / 16 blocks).  Workspace sizes: the functions above with n_feat = n_pad. */
+ * runs over the n_feat true columns with the arithmetic of gte_ln_relu_bwd_p3 at that width.  dz_below is written in whole 16-byte
+ * chunks of the true width: columns n_feat .. the next multiple of 4 as zeros; the columns from there to n_pad are NOT written -- they
+ * stay what the caller put there (the one-call plan zero-initialises the buffer once, and nothing else writes it).  The image is
+ * written as zeros in all of its padding (n_pad / 16 blocks).  tests/test_gpu_narrow_layer.py pins both.  Workspace sizes: the
+ * functions above with n_feat = n_pad. */
 int gte_sage_narrow_pad_supported(int64_t n_feat, int64_t n_pad, int64_t n_out);
 int gte_sage_narrow_fwd_pad(const float* h, int64_t ldh, int64_t n_feat, int64_t n_pad, const float* W, int64_t ldw, const float* bias,
                             int64_t n_out, float* t_self, int64_t ld_self, float* t_neigh, int64_t ld_neigh, int64_t n_nodes,
