@@ -89,6 +89,11 @@ SIGNATURES = {
     "gte_repr_max_out": (c_int, []),
     "gte_repr_features": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_double, c_int,
                                   c_void_p, c_int64, c_void_p]),
+    # token pooling of the SCIBERT embedder (csrc/token_pool.hip)
+    "gte_token_pool_max_width": (c_int, []),
+    "gte_token_pool_max_dim": (c_int, []),
+    "gte_token_pool_access_bytes": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
+    "gte_token_pool_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_inv_degree": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_sage_linear_fwd": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_int,

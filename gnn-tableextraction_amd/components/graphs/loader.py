@@ -89,12 +89,17 @@ class PrebuiltPages:
         (graph.bbox_features) -- what builder.get_graph + loader.modify_graphs + nlp/bbox.py do per page in Python.
         ``page_boxes[p]`` int [n_p, 4], ``page_sizes[p]`` = (width, height), ``page_texts[p]`` the words (for the character
         histogram; None -> empty texts), ``page_labels[p]`` converted class ids, ``extra_feats[p]`` optional float32 [n_p, F']
-        columns appended behind them (SPACY / SCIBERT embeddings, which need language models and stay pre-computed).
+        columns appended behind them (SPACY embeddings, which need a language model and stay pre-computed).
         ``repr_embedder`` (keyword, default None): a ``components.nlp.repr.Repr``; its P REPR columns (50 in the reference) follow
         the 13 BBOX columns and precede ``extra_feats`` -- the order of the reference's feature list -- computed on the device
         (graph.repr_features) from the texts of the node lists.  Token j of a page belongs to node j of the list BEFORE island
         removal (an empty word shifts the tokens of its page, as in the reference); the rows are then filtered as the BBOX rows
         are.  None leaves every result as it was.
+        ``scibert_embedder`` (keyword, default None): a ``components.nlp.scibert.SciBERT``; its D SCIBERT columns (768 in the
+        reference) follow the REPR columns and precede ``extra_feats``: ``[BBOX 13 | REPR P | SCIBERT D | extra_feats]``.  They are
+        computed on the device (graph.token_pool, one launch) from the texts of the node lists BEFORE island removal -- which words
+        pool their ``[SEP]`` depends on the longest word of the page as the reference sees it -- and written for the kept rows
+        only, straight into their columns of the final matrix.  None leaves every result as it was.
 
         ``page_annotations`` INSTEAD of ``page_labels`` (exactly one of the two, the other None): ``page_annotations[p]`` rows
         ``[x0, y0, x1, y1, category]`` with ORIGINAL category ids, what ``postprocessing.blocks_gt_json`` reads.  The node list
@@ -103,22 +108,25 @@ class PrebuiltPages:
         page's words) and the path above runs on it; ``converted`` applies ``LableModification``'s conversion (False: original
         ids, ``num_classes`` 13).  ``extra_feats`` must then be a callable ``(page_texts, page_boxes) -> [n_p, F'] arrays`` of the
         FINAL node lists: arrays per input word cannot line up once figure nodes are added and words dropped.  A
-        ``repr_embedder`` reads the texts of those node lists, ``"IMAGE!"`` for a figure node.
+        ``repr_embedder`` and a ``scibert_embedder`` read the texts of those node lists, ``"IMAGE!"`` for a figure node.
         ``pages[i]`` gains ``'annotations'`` (as given) and ``'texts'`` (of the final nodes)."""
         repr_embedder = kw.pop('repr_embedder', None)
+        scibert_embedder = kw.pop('scibert_embedder', None)
         if (page_labels is None) == (page_annotations is None):
             raise ValueError("from_boxes: exactly one of page_labels and page_annotations must be given, for all pages (got "
                              f"{'both' if page_labels is not None else 'neither'})")
         if page_annotations is not None:
             return cls._from_annotations(page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats,
                                          dict(k=k, max_dist=max_dist, bidirectional=bidirectional, range_island=range_island,
-                                              mode=mode), kw, repr_embedder=repr_embedder)
+                                              mode=mode), kw, repr_embedder=repr_embedder,
+                                         scibert_embedder=scibert_embedder)
         return cls._from_node_lists(page_boxes, page_sizes, page_texts, page_labels, device, k, max_dist, bidirectional,
-                                    range_island, extra_feats, mode, kw, repr_embedder=repr_embedder)[0]
+                                    range_island, extra_feats, mode, kw, repr_embedder=repr_embedder,
+                                    scibert_embedder=scibert_embedder)[0]
 
     @classmethod
     def _from_node_lists(cls, page_boxes, page_sizes, page_texts, page_labels, device, k, max_dist, bidirectional, range_island,
-                         extra_feats, mode, kw, extra_feats_fn=None, repr_embedder=None):
+                         extra_feats, mode, kw, extra_feats_fn=None, repr_embedder=None, scibert_embedder=None):
         """from_boxes for node lists that carry their labels -> (dataset, keep: bool [N] on the device over the given nodes).
         ``extra_feats_fn(page_texts, page_boxes)``: the extra columns as a callable on the node lists that are left after island
         removal."""
@@ -134,12 +142,12 @@ class PrebuiltPages:
                                          bidirectional=bidirectional, labels=labels, range_island=range_island,
                                          mode=mode)                  # PREPROCESS.mode: 'knn' | 'visibility' (loader.py:80)
         texts = page_texts if page_texts is not None else [[""] * n for n in sizes]
-        feat = Bbox(device).features(page_boxes, texts)[keep]
-        if repr_embedder is not None:                      # [BBOX | REPR | extra]: the order of the reference's feature list
-            feat = torch.cat([feat, repr_embedder.features(texts)[keep]], dim=1)
+        parts = [Bbox(device).features(page_boxes, texts)[keep]]
+        if repr_embedder is not None:                      # [BBOX | REPR | SCIBERT | extra]: the order of the reference's feature list
+            parts.append(repr_embedder.features(texts)[keep])
+        scibert_at = len(parts)                            # (its columns are written in place once the whole width is known)
         if extra_feats is not None:
-            extra = torch.from_numpy(np.concatenate([np.asarray(e, dtype=np.float32) for e in extra_feats])).to(device)[keep]
-            feat = torch.cat([feat, extra], dim=1)
+            parts.append(torch.from_numpy(np.concatenate([np.asarray(e, dtype=np.float32) for e in extra_feats])).to(device)[keep])
         if extra_feats_fn is not None:
             keep_h = keep.cpu().numpy()
             kept = [keep_h[int(node_off[p]):int(node_off[p + 1])] for p in range(n_pages)]
@@ -148,7 +156,20 @@ class PrebuiltPages:
             extra = extra_feats_fn(final_texts, final_boxes)
             extra = torch.from_numpy(np.concatenate([np.asarray(e, dtype=np.float32).reshape(len(t), -1)
                                                      for e, t in zip(extra, final_texts)])).to(device)
-            feat = torch.cat([feat, extra], dim=1)
+            parts.append(extra)
+        if scibert_embedder is None:
+            feat = torch.cat(parts, dim=1) if len(parts) > 1 else parts[0]
+        else:
+            # the SCIBERT columns go straight into their slice of the final matrix, for the kept rows only (graph.token_pool:
+            # row_map): no [N, D] temporary, no [keep] copy of it, no cat
+            widths = [p.shape[1] for p in parts[:scibert_at]] + [scibert_embedder.n_out] + [p.shape[1] for p in parts[scibert_at:]]
+            cols = np.concatenate([[0], np.cumsum(widths)])
+            feat = torch.empty((parts[0].shape[0], int(cols[-1])), dtype=torch.float32, device=device)
+            for j, p in enumerate(parts[:scibert_at] + [None] + parts[scibert_at:]):
+                if p is not None:
+                    feat[:, int(cols[j]):int(cols[j + 1])] = p
+            row_map = torch.where(keep, torch.cumsum(keep, 0) - 1, -1)
+            scibert_embedder.features(texts, out=feat[:, int(cols[scibert_at]):int(cols[scibert_at + 1])], row_map=row_map)
         # per-page host arrays (the dataset object's contract: .graphs[i] with ndata feat/label, edata feat, .pages[i]['bboxs'])
         src, dst = (t.cpu().numpy() for t in g.edges())
         w = g.edata['feat'].cpu().numpy()
@@ -199,7 +220,7 @@ class PrebuiltPages:
 
     @classmethod
     def _from_annotations(cls, page_boxes, page_sizes, page_texts, page_annotations, device, converted, extra_feats, graph_kw, kw,
-                          repr_embedder=None):
+                          repr_embedder=None, scibert_embedder=None):
         from ... import graph as G
         n_pages = len(page_boxes)
         ann_box, ann_cat, ann_off = cls.check_annotations(page_annotations, n_pages)
@@ -228,7 +249,8 @@ class PrebuiltPages:
             kw.setdefault('num_classes', len(ORIGIN_TO_CONV))
         out, keep = cls._from_node_lists(new_boxes, page_sizes, new_texts, new_labels, device, graph_kw['k'], graph_kw['max_dist'],
                                          graph_kw['bidirectional'], graph_kw['range_island'], None, graph_kw['mode'], kw,
-                                         extra_feats_fn=extra_feats, repr_embedder=repr_embedder)
+                                         extra_feats_fn=extra_feats, repr_embedder=repr_embedder,
+                                         scibert_embedder=scibert_embedder)
         keep_h = keep.cpu().numpy()
         for p in range(n_pages):
             o0, o1 = int(off_h[p]), int(off_h[p + 1])

@@ -753,6 +753,52 @@ def repr_features(node_tok: torch.Tensor, embeddings: torch.Tensor, centers: tor
     return out
 
 
+def token_pool(tok: torch.Tensor, table: torch.Tensor, mode: str = "mean", row_map: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pooled table rows per word in one launch of gte_token_pool_f32 (the rule is stated in include/gte.h): the embedding lookup
+    and ``mean_pooling`` / ``max_pooling`` of src/components/nlp/scibert.py:53-65, 143-160.  ``tok`` int32 [N, W]: the ids of each
+    word's pieces in position order, anything outside [0, V) skipped (-1: a masked position); ``table`` float32 [V, D]; ``mode``
+    'mean' or 'max'.  Finding the ids is string work and stays on the host (components/nlp/scibert.py).
+    ``row_map`` int64 [N]: the destination row of every word, negative for a word that is dropped; None: word i -> row i.
+    ``out``: a float32 [R, D] device tensor with unit column stride to write into -- usually a column slice of a wider feature
+    matrix, of which nothing outside the named rows of the slice is touched; None (only without ``row_map``) allocates [N, D].
+    The rows that ``row_map`` names must be distinct; that they lie below R is checked here (one read-back of two numbers)."""
+    _lib.require_device(tok, "token_pool")
+    _lib.require_device(table, "token_pool: table")
+    if mode not in ("mean", "max"):
+        raise ValueError(f"token_pool: mode must be 'mean' or 'max', got {mode!r}")
+    if table.dtype != torch.float32 or table.dim() != 2:
+        raise ValueError(f"token_pool: table must be a float32 matrix, got {table.dtype} {tuple(table.shape)}")
+    if tok.dim() != 2 or tok.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"token_pool: tok must be integer ids [words, width], got {tok.dtype} {tuple(tok.shape)}")
+    tok = tok.to(torch.int32).contiguous()
+    table = table.contiguous()
+    n, w = tok.shape
+    d = table.shape[1]
+    if row_map is not None:
+        _lib.require_device(row_map, "token_pool: row_map")
+        if row_map.dim() != 1 or row_map.shape[0] != n or row_map.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"token_pool: row_map must be one integer row per word [{n}], got {row_map.dtype} {tuple(row_map.shape)}")
+        if out is None:
+            raise ValueError("token_pool: row_map names rows of `out`, which was not given")
+        row_map = row_map.to(torch.int64).contiguous()
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.float32, device=tok.device)
+    else:
+        _lib.require_device(out, "token_pool: out")
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != d or (row_map is None and out.shape[0] != n) \
+                or (out.shape[0] > 0 and d > 0 and out.stride(1) != 1):
+            raise ValueError(f"token_pool: out must be float32 [{'rows' if row_map is not None else n}, {d}] with unit column stride, "
+                             f"got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+        if row_map is not None and n > 0 and int(row_map.max()) >= out.shape[0]:
+            raise ValueError(f"token_pool: row_map names row {int(row_map.max())}, out has {out.shape[0]} rows")
+    ldo = out.stride(0) if out.shape[0] > 1 else max(d, 1)
+    _lib.check(_lib.load().gte_token_pool_f32(_lib.ptr(tok), n, w, _lib.ptr(table), table.shape[0], d, 0 if mode == "mean" else 1,
+                                              None if row_map is None else _lib.ptr(row_map), _lib.ptr(out), ldo,
+                                              _lib.current_stream()), "gte_token_pool_f32")
+    return out
+
+
 def knn_graph_from_boxes(bbox: torch.Tensor, node_off, page_size, k: int = 5, max_dist: int = 500, bidirectional: bool = True,
                          labels: Optional[torch.Tensor] = None, range_island: int = 0, text_label: int = 1,
                          edge_features: bool = True, mode: str = "knn"):

@@ -420,6 +420,29 @@ int gte_repr_max_out(void);         /* 1024 */
 int gte_repr_features(const int32_t* node_tok, int64_t n_nodes, const double* embeddings, int64_t n_vocab, int dim,
                       const double* centers, const double* i_proto, int n_centroids, int n_out, double alpha,
                       int combined, float* out, int64_t ldo, void* stream);
+/* Token pooling, the arithmetic of the SCIBERT embedder (replaces the embedding lookup and mean_pooling / max_pooling of
+ * SciBERT.list_of_sentence, nlp/scibert.py:53-65, 143-160, called per page at model_train.py:293).  tok int32 [n_words, width],
+ * packed: the ids of a word's pieces in position order; table float [n_vocab, dim], packed (for SCIBERT: the row-normalised input
+ * embeddings).  An entry of tok TAKES PART if 0 <= id < n_vocab; anything else (the -1 of a masked position, an id that names no
+ * row) is skipped and is never used as an address.  With c the number of entries of word i that take part, per column j:
+ *   mode 0 (mean): s = 0.0f; s = s + table[id, j] for the entries that take part, in position order, every add rounded to float32;
+ *                  out = s / (float)c, a correctly rounded division; c == 0 gives 0.0f.
+ *   mode 1 (max):  m = 0.0f; m = x > m ? x : m with x = table[id, j], in position order: max(0, the entries); a NaN is passed over.
+ * row_map int64 [n_words], or NULL for the identity: row_map[i] is the destination row of word i, negative if the word is dropped
+ * (nothing is read or written for it).  The call writes exactly out[r * ldo .. r * ldo + dim) of the named rows r and nothing else:
+ * out may be a column slice of the final feature matrix that holds the kept nodes only.  The caller guarantees that the named rows
+ * exist and are distinct.  out and ldo need 4-byte alignment only (column 63 of an 831-float row): where table, out, ldo and dim
+ * are all 16-byte friendly (gte_token_pool_access_bytes == 16) a lane takes four columns with 16-byte accesses, otherwise one with
+ * dword accesses; both forms perform the same operations per element and give the same bits.
+ * One launch, one wave per word, grid-stride over words, the ids wave-uniform, up to 16 row reads in flight per column chunk; no
+ * atomics, no LDS, no workspace, no synchronisation.  Invalid arguments (negative sizes, width or dim < 1, n_vocab above INT32_MAX,
+ * ldo < dim, mode outside {0, 1}, null or misaligned pointers) return GTE_ERR_INVALID_ARGUMENT; above gte_token_pool_max_width() /
+ * _max_dim() the call returns GTE_ERR_UNSUPPORTED; both before any launch.  n_words == 0 is GTE_OK with nothing launched. */
+int gte_token_pool_max_width(void);   /* 32 */
+int gte_token_pool_max_dim(void);     /* 4096 */
+int gte_token_pool_access_bytes(const float* table, int dim, const float* out, int64_t ldo);   /* 16 or 4; host arithmetic only */
+int gte_token_pool_f32(const int32_t* tok, int64_t n_words, int width, const float* table, int64_t n_vocab, int dim, int mode,
+                       const int64_t* row_map, float* out, int64_t ldo, void* stream);
 /* inv_deg[v] = 1/(indptr[v+1]-indptr[v]) or 0  (models.py:74-78 as a standalone vector) */
 int gte_inv_degree(const int32_t* indptr, float* inv_deg, int64_t n_nodes, void* stream);
 
