@@ -73,6 +73,11 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "gte_word_labels_compact": (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p,
                                                          c_void_p, c_void_p, c_void_p]),
+    # area-weighted confusion of node predictions (csrc/doc_eval.hip)
+    "gte_doc_eval_max_classes": (c_int, []),
+    "gte_doc_eval_chunk_nodes": (c_int, []),
+    "gte_doc_eval_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "gte_doc_eval": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_batch_assemble": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_batch_assemble_rows": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,

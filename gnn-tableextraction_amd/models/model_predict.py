@@ -162,8 +162,13 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
 
 
 def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False, blocks=False,
-         block_scores=False, block_eval=False):
-    """``blocks=True``: the result gains ``'blocks'`` = ``extract_blocks(data, all_pred)`` (the pages carry their layout blocks
+         block_scores=False, block_eval=False, doc_eval=False):
+    """``doc_eval=True``: the result gains ``'doc_eval'`` = ``metrics.evaluate_doc`` of the pages' labels, ``all_pred`` and the
+    word boxes ``data.pages[i]['bboxs']``: area-weighted precision / recall / F1 per class (the reference's ``evaluate_doc``,
+    models/evaluate.py:142-209), both as the reference computes them (``'reference'``) and by the DocBank formula (``'docbank'``);
+    one line per class is printed.  A page without ``'bboxs'`` raises ``ValueError``.
+
+    ``blocks=True``: the result gains ``'blocks'`` = ``extract_blocks(data, all_pred)`` (the pages carry their layout blocks
     as ``data.pages[i]['blocks']``), and with ``save_predictions`` ``{output}/blocks/{logs}.json`` is written (``blocks_json``).
 
     ``block_scores=True`` (implies ``blocks``): ``extract_blocks(..., logits=...)`` -- every page of ``'blocks'`` gains
@@ -289,4 +294,14 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
         if want_block_eval:
             gt = PP.blocks_gt_json(data) if block_eval is True else block_eval
             result['block_eval'] = metrics.evaluate_regions(doc, gt, device=device, float_boxes=True)
+    if doc_eval:
+        for i, page in enumerate(data.pages):
+            if 'bboxs' not in page:
+                raise ValueError(f"test(doc_eval=True): page {i} carries no 'bboxs'")
+        boxes = [np.asarray(page['bboxs']).reshape(-1, 4) for page in data.pages]
+        ev = result['doc_eval'] = metrics.evaluate_doc(all_true, all_pred, boxes, device=device)
+        for c in range(ev['n_classes']):                                                  # evaluate.py:207, without its class names
+            ref, bank = ev['reference'], ev['docbank']
+            print(f"class {c}: precision {ref['precision'][c]} - recall {ref['recall'][c]} - f1 {ref['f1'][c]}"
+                  f" (DocBank: {bank['precision'][c]} - {bank['recall'][c]} - {bank['f1'][c]})")
     return result

@@ -210,3 +210,133 @@ def evaluate_regions(pred_doc, gt_doc, iou_thrs=None, count_unpaired=False, devi
         tp = box_match(torch.from_numpy(cells.pred_box).to(device), cells.pred_off, torch.from_numpy(cells.gt_box).to(device),
                        cells.gt_off, iou_thrs, float_boxes=float_boxes).cpu().numpy()
     return average_precisions(cells, tp)
+
+
+# ---- area-weighted precision / recall / F1 per class: the DocBank token metric, and the reference's evaluate_doc ------------------
+# Three public stages in a row, as evaluate_regions: doc_cells (host) -> area_confusion (gte_doc_eval, ONE C call) -> doc_prf
+# (host, numpy), so that the host stages run (and are tested) without a device, with a CPU oracle in place of the call.
+class DocCells(NamedTuple):
+    """Result of :func:`doc_cells`: the arguments of :func:`area_confusion`."""
+    gt: np.ndarray            # int32 [N]  all pages concatenated
+    pred: np.ndarray          # int32 [N]
+    bbox: np.ndarray          # int32 [N, 4]
+    n_classes: int
+
+
+def _doc_flat(x, what, paged, width=None):
+    """``x`` -- one array, or a sequence with one array per page when ``paged`` -- as (one integer array, the pages' sizes)."""
+    def one(a):
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        if width is not None and a.size % width:
+            raise ValueError(f"evaluate_doc: {what} of {a.size} values are not rows of {width}")
+        a = a.reshape(-1) if width is None else a.reshape(-1, width)
+        if a.dtype.kind not in 'iu':
+            if a.dtype.kind not in 'fb' or not (np.isfinite(a).all() and (a == np.trunc(a)).all()):
+                raise ValueError(f"evaluate_doc: {what} are not integral")
+        if a.size and (a.min() < -(1 << 31) or a.max() >= 1 << 31):
+            raise ValueError(f"evaluate_doc: {what} do not fit 32 bits")
+        return a.astype(np.int64)
+    if not paged:
+        return one(x), None
+    parts = [one(a) for a in x]
+    empty = np.zeros(0 if width is None else (0, width), dtype=np.int64)
+    return (np.concatenate(parts) if parts else empty), [a.shape[0] for a in parts]
+
+
+def doc_cells(labels, preds, boxes, n_classes=None) -> DocCells:
+    """Stage one of :func:`evaluate_doc`; no device is touched.  ``labels``, ``preds`` (integers) and ``boxes`` ([., 4] integers,
+    x0, y0, x1, y1) are either flat arrays over all nodes, or sequences with one array per page (``labels`` decides: a list or
+    tuple whose first element is itself an array or a sequence), concatenated in that order.  ``n_classes``: default ``max(gt) + 1``,
+    as the reference's loop runs.  ``ValueError`` on a page-count mismatch, on unequal lengths (per page and in all), on values
+    that are not integral or do not fit 32 bits, on ``n_classes < 1`` (or no node to take it from), and where
+    ``max|area| * N >= 2^62``: the int64 sums of gte_doc_eval could overflow."""
+    paged = isinstance(labels, (list, tuple)) and len(labels) > 0 and np.ndim(labels[0]) >= 1
+    if paged:
+        for what, x in (("predictions", preds), ("boxes", boxes)):
+            if not isinstance(x, (list, tuple)) or len(x) != len(labels):
+                raise ValueError(f"evaluate_doc: {len(labels)} pages of labels, but the {what} are not {len(labels)} pages")
+    gt, gt_pages = _doc_flat(labels, "labels", paged)
+    pred, pred_pages = _doc_flat(preds, "predictions", paged)
+    bbox, box_pages = _doc_flat(boxes, "boxes", paged, width=4)
+    if gt_pages != pred_pages or gt_pages != box_pages:
+        bad = next(i for i, sizes in enumerate(zip(gt_pages, pred_pages, box_pages)) if len(set(sizes)) > 1)
+        raise ValueError(f"evaluate_doc: page {bad} has {gt_pages[bad]} labels, {pred_pages[bad]} predictions, {box_pages[bad]} boxes")
+    n = gt.shape[0]
+    if pred.shape[0] != n or bbox.shape[0] != n:
+        raise ValueError(f"evaluate_doc: {n} labels, {pred.shape[0]} predictions, {bbox.shape[0]} boxes")
+    if n_classes is None:
+        if n == 0:
+            raise ValueError("evaluate_doc: no node to take n_classes from")
+        n_classes = int(gt.max()) + 1
+    n_classes = int(n_classes)
+    if n_classes < 1:
+        raise ValueError(f"evaluate_doc: n_classes {n_classes} (the largest label is {int(gt.max()) if n else None})")
+    w, h = bbox[:, 2] - bbox[:, 0], bbox[:, 3] - bbox[:, 1]
+    largest = int((np.abs(w).astype(np.uint64) * np.abs(h).astype(np.uint64)).max()) if n else 0       # (< 2^64: exact in uint64)
+    if largest * n >= 1 << 62:
+        raise ValueError(f"evaluate_doc: max|area| * N = {largest} * {n} reaches 2^62: the int64 sums could overflow")
+    return DocCells(gt.astype(np.int32), pred.astype(np.int32), np.ascontiguousarray(bbox.astype(np.int32)), n_classes)
+
+
+def area_confusion(gt, pred, bbox, n_classes, device=None):
+    """Stage two of :func:`evaluate_doc`, the one C call (gte_doc_eval; include/gte.h has the contract): ``gt``, ``pred`` int32
+    [N] and ``bbox`` int32 [N, 4] (host arrays or tensors) -> ``(area, count, lead)`` as numpy int64.  ``area[g, p]`` /
+    ``count[g, p]`` [C + 1, C + 1]: summed box area / number of the nodes labelled ``g`` and predicted ``p``, index ``C`` = none
+    of the classes; ``lead`` [2, C]: the area that the reference's evaluate_doc loses from its false positives (row 0) and false
+    negatives (row 1).  ``GteError`` above ``gte_doc_eval_max_classes()`` classes.  One synchronisation (the copy back)."""
+    lib, P = _lib.load(), _lib.ptr
+    device = _lib.default_device(device)
+    as_dev = lambda a, shape: torch.as_tensor(a).to(device=device, dtype=torch.int32).reshape(shape).contiguous()
+    d_gt, d_pred, d_box = as_dev(gt, (-1,)), as_dev(pred, (-1,)), as_dev(bbox, (-1, 4))
+    for t in (d_gt, d_pred, d_box):
+        _lib.require_device(t, "area_confusion")
+    n, C = d_gt.shape[0], int(n_classes)
+    if d_pred.shape[0] != n or d_box.shape[0] != n:
+        raise ValueError(f"area_confusion: {n} labels, {d_pred.shape[0]} predictions, {d_box.shape[0]} boxes")
+    side = max(C, 0) + 1
+    area = torch.empty((side, side), dtype=torch.int64, device=device)
+    count = torch.empty((side, side), dtype=torch.int64, device=device)
+    lead = torch.empty((2, max(C, 0)), dtype=torch.int64, device=device)
+    ws = torch.empty(max(int(lib.gte_doc_eval_workspace_bytes(n, C)), 8), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(lib.gte_doc_eval(P(d_gt), P(d_pred), P(d_box), n, C, P(area), P(count), P(lead), P(ws), ws.numel(),
+                                    _lib.current_stream()), "gte_doc_eval")
+    return area.cpu().numpy(), count.cpu().numpy(), lead.cpu().numpy()
+
+
+def doc_prf(area, count, lead, mode='reference'):
+    """Stage three of :func:`evaluate_doc`: the sums of :func:`area_confusion` -> a dict of ``precision``, ``recall``, ``f1``
+    (float64 [C]) and ``tp_area``, ``fp_area``, ``fn_area`` (int64 [C]).  Pure numpy.
+
+    ``tp = area[c, c]``; ``mode='docbank'``: ``fp`` = the area predicted ``c`` but not labelled ``c``, ``fn`` = labelled but not
+    predicted -- the DocBank definition.  ``mode='reference'``: ``fp - lead[0]``, ``fn - lead[1]``, the numbers that the
+    reference's evaluate_doc prints (models/evaluate.py:182-202: its ``np.delete`` takes a two-column index array, so the first
+    ``t_c`` entries of a class's predicted / labelled list leave the false positives / negatives next to the true positives, and
+    the result depends on node order).  ``p = tp / (tp + fp)``, ``r = tp / (tp + fn)``, ``f1 = 2 p r / (p + r)``: float64 divisions
+    of the int64 sums, ``0 / 0`` NaN, as numpy gives them there."""
+    area, count, lead = (np.asarray(a, dtype=np.int64) for a in (area, count, lead))
+    C = area.shape[0] - 1
+    if area.shape != (C + 1, C + 1) or count.shape != area.shape or lead.shape != (2, C):
+        raise ValueError(f"doc_prf: area {area.shape}, count {count.shape}, lead {lead.shape} are not [C+1, C+1] twice and [2, C]")
+    if mode not in ('reference', 'docbank'):
+        raise ValueError(f"doc_prf: mode {mode!r} is neither 'reference' nor 'docbank'")
+    tp = np.diagonal(area)[:C].copy()
+    fp = area[:, :C].sum(axis=0) - tp
+    fn = area[:C, :].sum(axis=1) - tp
+    if mode == 'reference':
+        fp, fn = fp - lead[0], fn - lead[1]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        p, r = tp / (tp + fp), tp / (tp + fn)
+        f1 = (2 * p * r) / (p + r)
+    return {'precision': p, 'recall': r, 'f1': f1, 'tp_area': tp, 'fp_area': fp, 'fn_area': fn}
+
+
+def evaluate_doc(labels, preds, boxes, n_classes=None, device=None):
+    """Area-weighted precision / recall / F1 per class (the reference's ``evaluate_doc``, models/evaluate.py:142-209: the DocBank
+    token metric, a word counting with the area of its box), all sums in ONE C call on the device.  Arguments as
+    :func:`doc_cells`.  Returns ``{'n_classes': C, 'reference': doc_prf(mode='reference'), 'docbank': doc_prf(mode='docbank'),
+    'area', 'count', 'lead'}`` -- both the numbers the reference prints and those of the formula it quotes, from the same pass."""
+    cells = doc_cells(labels, preds, boxes, n_classes)
+    area, count, lead = area_confusion(cells.gt, cells.pred, cells.bbox, cells.n_classes, device=device)
+    return {'n_classes': cells.n_classes, 'reference': doc_prf(area, count, lead, 'reference'),
+            'docbank': doc_prf(area, count, lead, 'docbank'), 'area': area, 'count': count, 'lead': lead}

@@ -342,6 +342,34 @@ int gte_block_scores(const int32_t* bbox, const int32_t* node_off, const float* 
                      int n_cat, int64_t n_pages, int64_t n_nodes, int64_t n_blocks, int64_t max_page_words, int64_t max_page_blocks,
                      float* score, int32_t* n_words, void* stream);
 
+/* ---- area-weighted confusion of node predictions: the sums of the DocBank token metric and of the reference's evaluate_doc
+ * (models/evaluate.py:182-202) ----
+ * Inputs: gt, pred int32 [n_nodes], all pages concatenated; bbox int32 [n_nodes, 4] (x0, y0, x1, y1), 16-byte aligned;
+ * C = n_classes, 1 <= C <= gte_doc_eval_max_classes().  area(v) = (x1 - x0) * (y1 - y0), the differences in 64 bits, the product
+ * as int64: inverted corners give negative or zero areas, and they are summed as they are.  The caller keeps every sum inside
+ * int64 (max |area| * n_nodes < 2^62 is enough).  A label or prediction outside [0, C) has index C, "none of the classes".
+ * With P_c = the nodes with pred == c and G_c = those with gt == c, both in node order, T_c = P_c and G_c, t_c = |T_c|:
+ *   area_out[g * (C+1) + p]   int64 [(C+1)^2]: the summed area of the nodes with gt index g and pred index p.
+ *   count_out[g * (C+1) + p]  the same layout: their number.  t_c = count_out[c * (C+1) + c].
+ *   lead_out[c]               int64 [2 C]: the summed area of the nodes of P_c \ T_c whose 0-based position within P_c is < t_c;
+ *   lead_out[C + c]           the same for G_c \ T_c within G_c.
+ * lead is what the reference loses: its np.delete calls take a two-column index array, so next to the true positives the first
+ * t_c entries of the predicted (ground-truth) list leave its false positives (negatives), wrong or not.
+ *   DocBank:    TP_c = area[c][c], FP_c = sum_g area[g][c] - TP_c,  FN_c = sum_p area[c][p] - TP_c;
+ *   reference:  FP_c - lead_out[c], FN_c - lead_out[C + c].
+ * The call writes every entry of the three outputs (n_nodes == 0: zeros) and does not need them zeroed.  One memset and at most
+ * three launches on `stream`: a tally of chunks of gte_doc_eval_chunk_nodes() nodes (LDS integer atomics, one flush of 64-bit
+ * global atomics per workgroup), a one-workgroup scan of the chunks' class counts, and the lead pass (ranks from wave ballots and
+ * the scan's prefix).  Integer sums only: deterministic.  No allocation, no synchronisation, no workgroup waits on another.
+ * workspace: gte_doc_eval_workspace_bytes(n_nodes, n_classes) bytes (-1 for sizes the call refuses), 8-byte aligned.
+ * A null or misaligned pointer, n_nodes < 0 or n_classes < 1 return GTE_ERR_INVALID_ARGUMENT; n_classes above the limit or
+ * n_nodes > 2^31 - 1 GTE_ERR_UNSUPPORTED; a short workspace GTE_ERR_WORKSPACE_TOO_SMALL: nothing is launched or written then. */
+int gte_doc_eval_max_classes(void);     /* 16 */
+int gte_doc_eval_chunk_nodes(void);     /* 2048 */
+int64_t gte_doc_eval_workspace_bytes(int64_t n_nodes, int n_classes);
+int gte_doc_eval(const int32_t* gt, const int32_t* pred, const int32_t* bbox, int64_t n_nodes, int n_classes, int64_t* area_out,
+                 int64_t* count_out, int64_t* lead_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The whole batch in ONE launch (what the train loop calls every step; gte_batch_csr / gte_batch_rows are its pieces):
  * a page's rows are CONTIGUOUS in the resident arrays and in the batch, so every array of the batch is the concatenation
  * of per-page runs -- features and labels copied, indptr / indices copied with a per-page constant added.
