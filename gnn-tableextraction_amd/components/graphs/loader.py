@@ -32,8 +32,11 @@ class LabelTransformer:
 
 class PrebuiltPages:
     def __init__(self, pages: Sequence[S.Page], num_classes: int = 9, rate: float = 0.95, seed: int = 42,
-                 float_labels: bool = True):
+                 float_labels: bool = True, labeled: bool = True):
+        """``labeled=False``: pages without ground truth (``from_boxes(unlabeled=True)``; ``Page.label`` is None): the graphs
+        carry no ``ndata['label']`` and ``stats`` counts nothing.  Such a set is for ``model_predict.predict()`` only."""
         self.page_arrays = list(pages)
+        self.labeled = bool(labeled)
         self.num_classes = num_classes
         self.rate, self.seed = rate, seed
         self.label_tranformer = LabelTransformer()          # (sic) the reference's attribute name
@@ -43,10 +46,12 @@ class PrebuiltPages:
             g = PageGraph(p.src, p.dst, p.num_nodes)
             g.ndata['feat'] = torch.from_numpy(p.feat)
             # the reference stores labels as float32 and casts at the loss (loader.py:350-354)
-            g.ndata['label'] = torch.from_numpy(p.label.astype(np.float32) if float_labels else p.label)
+            if self.labeled:
+                g.ndata['label'] = torch.from_numpy(p.label.astype(np.float32) if float_labels else p.label)
             g.edata['feat'] = torch.from_numpy(p.weight)
             self.graphs.append(g)
-            counts += np.bincount(p.label, minlength=num_classes)
+            if self.labeled:
+                counts += np.bincount(p.label, minlength=num_classes)
         total = max(int(counts.sum()), 1)
         self.stats = {'numbers': counts.tolist(), 'percentages': [round(c / total, 2) for c in counts.tolist()]}
         self.pages = [{'page': f'synthetic_{i}', 'bboxs': p.bbox, 'texts': None} for i, p in enumerate(self.page_arrays)]
@@ -66,18 +71,24 @@ class PrebuiltPages:
     def save(self, path: str) -> None:
         src, dst, w, feat, label, off = S.concat_pages(self.page_arrays)
         eoff = np.cumsum([0] + [len(p.src) for p in self.page_arrays])
-        np.savez(path, src=src, dst=dst, weight=w, feat=feat, label=label, node_off=off, edge_off=eoff,
-                 bbox=np.concatenate([p.bbox for p in self.page_arrays]), num_classes=self.num_classes)
+        arrays = dict(src=src, dst=dst, weight=w, feat=feat, label=label, node_off=off, edge_off=eoff,
+                      bbox=np.concatenate([p.bbox for p in self.page_arrays]), num_classes=self.num_classes)
+        if not self.labeled:                                # an unlabelled set: no 'label' entry; load() tells by its absence
+            del arrays['label']
+        np.savez(path, **arrays)
 
     @classmethod
     def load(cls, path: str, **kw) -> "PrebuiltPages":
         z = np.load(path)
         no, eo = z["node_off"], z["edge_off"]
+        labeled = "label" in z.files
         pages = []
         for i in range(len(no) - 1):
             n0, n1, e0, e1 = int(no[i]), int(no[i + 1]), int(eo[i]), int(eo[i + 1])
             pages.append(S.Page((z["src"][e0:e1] - n0).astype(np.int32), (z["dst"][e0:e1] - n0).astype(np.int32),
-                                z["weight"][e0:e1], z["feat"][n0:n1], z["label"][n0:n1], z["bbox"][n0:n1]))
+                                z["weight"][e0:e1], z["feat"][n0:n1], z["label"][n0:n1] if labeled else None, z["bbox"][n0:n1]))
+        if not labeled:
+            kw = dict(kw, labeled=False)
         return cls(pages, num_classes=int(z["num_classes"]), **kw)
 
     @classmethod
@@ -109,9 +120,26 @@ class PrebuiltPages:
         ids, ``num_classes`` 13).  ``extra_feats`` must then be a callable ``(page_texts, page_boxes) -> [n_p, F'] arrays`` of the
         FINAL node lists: arrays per input word cannot line up once figure nodes are added and words dropped.  A
         ``repr_embedder`` and a ``scibert_embedder`` read the texts of those node lists, ``"IMAGE!"`` for a figure node.
-        ``pages[i]`` gains ``'annotations'`` (as given) and ``'texts'`` (of the final nodes)."""
+        ``pages[i]`` gains ``'annotations'`` (as given) and ``'texts'`` (of the final nodes).
+
+        ``unlabeled=True`` (keyword, default False): the words of a document without ground truth -- the reference's ``GenericPapers2Graphs``
+        (loader.py:431-573: ``get_graph(..., set_labels=False)``, so no labels, no FIGURE nodes, no island removal).
+        ``page_labels`` and ``page_annotations`` must both be None and ``range_island`` 0 (island removal reads labels);
+        ``ValueError`` otherwise, before any device call.  The labels route runs without labels -- the same graph, edge weights
+        and feature columns, every word kept -- and the result has ``labeled == False``: graphs without ``ndata['label']``,
+        ``stats`` of zero counts, ``num_classes`` from the keyword (default 9).  It is input to ``model_predict.predict()``;
+        ``train()`` and ``test()`` refuse it."""
         repr_embedder = kw.pop('repr_embedder', None)
         scibert_embedder = kw.pop('scibert_embedder', None)
+        if kw.pop('unlabeled', False):
+            if page_labels is not None or page_annotations is not None:
+                raise ValueError("from_boxes: unlabeled=True takes neither page_labels nor page_annotations (got "
+                                 f"{'page_labels' if page_labels is not None else 'page_annotations'})")
+            if range_island != 0:
+                raise ValueError(f"from_boxes: unlabeled=True needs range_island 0 (got {range_island}): island removal reads labels")
+            return cls._from_node_lists(page_boxes, page_sizes, page_texts, None, device, k, max_dist, bidirectional, 0,
+                                        extra_feats, mode, dict(kw, labeled=False), repr_embedder=repr_embedder,
+                                        scibert_embedder=scibert_embedder)[0]
         if (page_labels is None) == (page_annotations is None):
             raise ValueError("from_boxes: exactly one of page_labels and page_annotations must be given, for all pages (got "
                              f"{'both' if page_labels is not None else 'neither'})")
@@ -137,7 +165,9 @@ class PrebuiltPages:
         sizes = [len(b) for b in page_boxes]
         node_off = np.concatenate([[0], np.cumsum(sizes)])
         bbox = torch.from_numpy(np.concatenate([np.asarray(b, dtype=np.int32).reshape(-1, 4) for b in page_boxes])).to(device)
-        labels = torch.from_numpy(np.concatenate([np.asarray(l, dtype=np.int64) for l in page_labels])).to(device)
+        labels = None                                      # (page_labels None: the unlabelled route -- no labels anywhere below)
+        if page_labels is not None:
+            labels = torch.from_numpy(np.concatenate([np.asarray(l, dtype=np.int64) for l in page_labels])).to(device)
         g, keep = G.knn_graph_from_boxes(bbox, node_off, np.asarray(page_sizes, dtype=np.int32), k=k, max_dist=max_dist,
                                          bidirectional=bidirectional, labels=labels, range_island=range_island,
                                          mode=mode)                  # PREPROCESS.mode: 'knn' | 'visibility' (loader.py:80)
@@ -173,14 +203,16 @@ class PrebuiltPages:
         # per-page host arrays (the dataset object's contract: .graphs[i] with ndata feat/label, edata feat, .pages[i]['bboxs'])
         src, dst = (t.cpu().numpy() for t in g.edges())
         w = g.edata['feat'].cpu().numpy()
-        feat_h, lab_h, bbox_h = feat.cpu().numpy(), g.ndata['label'].cpu().numpy(), g.ndata['bbox'].cpu().numpy()
+        feat_h, bbox_h = feat.cpu().numpy(), g.ndata['bbox'].cpu().numpy()
+        lab_h = None if labels is None else g.ndata['label'].cpu().numpy()
         off = np.concatenate([[0], np.cumsum(g.batch_num_nodes_)])
         eoff = np.searchsorted(dst, off)                   # edges are sorted by destination
         pages = []
         for p in range(n_pages):
             n0, n1, e0, e1 = int(off[p]), int(off[p + 1]), int(eoff[p]), int(eoff[p + 1])
             pages.append(S.Page((src[e0:e1] - n0).astype(np.int32), (dst[e0:e1] - n0).astype(np.int32), w[e0:e1],
-                                np.ascontiguousarray(feat_h[n0:n1]), lab_h[n0:n1].astype(np.int64), bbox_h[n0:n1]))
+                                np.ascontiguousarray(feat_h[n0:n1]), None if lab_h is None else lab_h[n0:n1].astype(np.int64),
+                                bbox_h[n0:n1]))
         out = cls(pages, **kw)
         g.ndata['feat'] = feat
         out.whole = g                                       # the batched device graph, for callers that stay on the device

@@ -28,7 +28,7 @@ class Page:
     dst: np.ndarray       # int32 [E]
     weight: np.ndarray    # float32 [E]
     feat: np.ndarray      # float32 [n, F0]
-    label: np.ndarray     # int64 [n]
+    label: Optional[np.ndarray]     # int64 [n]; None: a page without ground truth (PrebuiltPages.from_boxes(unlabeled=True))
     bbox: np.ndarray      # int32 [n, 4]
 
     @property
@@ -121,7 +121,7 @@ def concat_pages(pages: List[Page]):
     dst = np.concatenate([p.dst.astype(np.int64) + off[i] for i, p in enumerate(pages)]).astype(np.int32)
     weight = np.concatenate([p.weight for p in pages])
     feat = np.concatenate([p.feat for p in pages], axis=0)
-    label = np.concatenate([p.label for p in pages])
+    label = None if any(p.label is None for p in pages) else np.concatenate([p.label for p in pages])    # None: unlabelled pages
     return src, dst, weight, feat, label, off
 
 

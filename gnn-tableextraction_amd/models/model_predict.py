@@ -18,6 +18,9 @@ the reference; ``test()`` only calls them.  Output contract (what post-processin
                                       the reference's box-level evaluation reads (``regions_json``)
                                       (``region_scores=True``: with the regions' confidences as scores; ``box_eval=True``: the
                                       result also holds that evaluation, ``metrics.evaluate_regions``)
+``predict(data, config)`` is the label-free sibling (the reference's ``GenericPapers2Graphs`` route, loader.py:431-573): the same
+forward on pages without ground truth, a confidence per word, the same artefacts (``predictions/{logs}.pkl`` gains
+``'confidence'``), no metric.
 The printed accuracy is the reference's "Mean Test Accuracy": the MEAN OVER PAGES of the per-page accuracy (:150,163),
 not the node-weighted accuracy (returned as ``accuracy_nodes``).
 """
@@ -32,6 +35,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import graph as G
+from .. import ops
 from ..components.features.utils import calculate_hidden, get_in_feats_
 from ..components.graphs.models import GcnSAGE
 from ..components.graphs import postprocessing as PP
@@ -117,7 +121,7 @@ class PageForwardGraphs:
         return b["logits"][:n], b["pred"][:n]
 
 
-def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logits=False):
+def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logits=False, head=False, return_prob=False):
     """Predictions (arg-max class per node, int64, pages concatenated in ``page_ids`` order -- default: all resident pages) with
     ``batch_pages`` pages per forward.  The reference's loop (model_predict.py:141-151) is one forward per page from the host;
     here a forward is ONE host call (``engine.forward_logits`` -> gte_gcnsage_forward) on a batch that the pipeline
@@ -125,7 +129,14 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
     caller reads the result.
 
     ``return_logits=True``: returns ``(pred, logits)``, the logits of all nodes as ONE device tensor float32 [nodes, n_classes]
-    in the same order (every batch's view is copied out before the next forward overwrites the engine's buffer)."""
+    in the same order (every batch's view is copied out before the next forward overwrites the engine's buffer).
+
+    ``head=True``: every batch's arg-max launch is ONE ``ops.predict_head`` launch (gte_predict_head) that also writes the
+    confidence of every node -- the softmax probability of its predicted class, float32 -- and, with ``return_prob=True``, the
+    whole softmax row, straight into the batch's slices of the flat results.  Returns ``(pred, conf)`` or ``(pred, conf, prob)``,
+    with ``return_logits=True`` the logits appended last.  ``head=False`` (default): as above, ``return_prob`` is not accepted."""
+    if return_prob and not head:
+        raise ValueError("predict_resident: return_prob needs head=True")
     res = pipe.res
     ids = np.arange(len(res.page_sizes()), dtype=np.int64) if page_ids is None else np.asarray(page_ids, dtype=np.int64)
     steps = [ids[i:i + batch_pages] for i in range(0, ids.size, batch_pages)]
@@ -140,8 +151,17 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
     total = sum(pipe.nodes(s) for s in range(len(steps)))
     pred = torch.empty(total, dtype=torch.int64, device=pipe.device)
     all_logits = None
+    conf = torch.empty(total, dtype=torch.float32, device=pipe.device) if head else None
+    prob = None
+
+    def result():
+        empty = torch.empty((0, 0), dtype=torch.float32, device=pipe.device)          # (no step: the class count is unknown)
+        out = (pred,) + ((conf,) if head else ()) + ((empty if prob is None else prob,) if return_prob else ())
+        out += ((empty if all_logits is None else all_logits,) if return_logits else ())
+        return out if len(out) > 1 else pred
+
     if not steps:
-        return (pred, torch.empty((0, 0), dtype=torch.float32, device=pipe.device)) if return_logits else pred
+        return result()
     engine.reserve(pipe.max_batch_nodes(), f0, cached=bool(res.p3_mode == "rows" and res.agg_p3 is not None))
     pipe.start(0)
     off = 0
@@ -151,14 +171,20 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
         g = pipe.get(s)
         logits = engine.forward_logits(g)
         n = pipe.nodes(s)
-        torch.argmax(logits, dim=1, out=pred[off:off + n])
+        if head:
+            if return_prob and prob is None:
+                prob = torch.empty((total, logits.shape[1]), dtype=torch.float32, device=pipe.device)
+            ops.predict_head(logits, n, out_pred=pred[off:off + n], out_conf=conf[off:off + n],
+                             out_prob=prob[off:off + n] if return_prob else None)
+        else:
+            torch.argmax(logits, dim=1, out=pred[off:off + n])
         if return_logits:
             if all_logits is None:
                 all_logits = torch.empty((total, logits.shape[1]), dtype=torch.float32, device=pipe.device)
             all_logits[off:off + n].copy_(logits[:n])
         pipe.release(s)
         off += n
-    return (pred, all_logits) if return_logits else pred
+    return result()
 
 
 def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False, blocks=False,
@@ -190,58 +216,17 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
     ``box_eval=True`` (implies ``region_scores``): the result gains ``'box_eval'`` = ``evaluate_regions`` of the scored regions
     against the ground-truth regions that the same component rule forms from the pages' labels (``extract_regions(data,
     labels)``: the only box-level ground truth that pre-built pages carry) -- the reference's AP at IoU 0.50 .. 0.95 and mAP."""
+    if not getattr(data, 'labeled', True):
+        raise ValueError("test(): the pages carry no labels (labeled == False, from_boxes(unlabeled=True)); use predict()")
     region_scores = bool(region_scores or box_eval)
     regions = bool(regions or region_scores)
     want_block_eval = block_eval is not False and block_eval is not None
     block_scores = bool(block_scores or want_block_eval)
     blocks = bool(blocks or block_scores)
     want_logits = region_scores or block_scores
-    if not (config.TRAINING.gpu >= 0 and torch.cuda.is_available()):
-        raise RuntimeError("model_predict runs on the MI355X HIP path only (no CPU fallback)")
-    device = torch.device('cuda', config.TRAINING.gpu)
-    n_classes = data.num_classes
-    in_feats = get_in_feats_(config)
-    logs = logs_from_config(config)
-    out_root = config.GENERAL.get('output_dir', 'output')
-    weights_path = weights_path or os.path.join(out_root, 'weights', f'{logs}.pt')
-
-    model = GcnSAGE(in_feats, int(hidden_width(config, in_feats, n_classes)), n_classes, config.TRAINING.n_layers,
-                    F.relu, config.TRAINING.dropout)
-    model.load_state_dict(torch.load(weights_path, map_location='cpu'))
-    model = model.to(device).eval()
-
-    bs = max(1, int(config.TRAINING.batch_size))
-    engine = None
-    flat_logits = None                                     # region_scores: the logits of all nodes, pages in data.graphs order
-    if len(data.graphs) > 0:
-        # evaluation applies no dropout: a model trained with --dropout takes the same path (forward_logits binds the p = 0 plan);
-        # only a model the engine refuses to build for (a dropout model outside the one-call plan) keeps the module loop below
-        from .engine import FusedGcnSageStep
-        try:
-            engine = FusedGcnSageStep(model)
-        except ValueError:
-            if not config.TRAINING.dropout:
-                raise
-    if engine is not None:
-        # the shipped configuration: pages resident in HBM, batches assembled on the device one forward ahead, one host call per
-        # forward (predict_resident); one device -> host copy of all predictions at the end
-        from .loop import BatchPipeline
-        pipe = BatchPipeline(G.ResidentPages(data.graphs, device))
-        flat_pred = predict_resident(engine, pipe, bs, return_logits=want_logits)
-        if want_logits:
-            flat_pred, flat_logits = flat_pred
-        flat_pred = flat_pred.cpu().numpy()
-    else:
-        preds, kept = [], []
-        with torch.no_grad():
-            for b0 in range(0, len(data.graphs), bs):
-                logits = model(G.batch([g.to(device) for g in data.graphs[b0:b0 + bs]]))
-                if want_logits:
-                    kept.append(logits.float().clone())
-                preds.append(logits.argmax(dim=1).cpu().numpy())
-        flat_pred = np.concatenate(preds)
-        if kept:
-            flat_logits = torch.cat(kept)
+    run = _forward_pages(data, config, weights_path, want_logits)
+    device, n_classes, logs, out_root, bs = run['device'], run['n_classes'], run['logs'], run['out_root'], run['bs']
+    flat_pred, flat_logits = run['pred'], run['logits']
     all_pred, all_true = [], []
     mean_test_acc, off = 0.0, 0
     for g in data.graphs:
@@ -258,25 +243,11 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
     print("Mean Test Accuracy {:.4f}".format(acc))                                        # :163
     print(" -> node accuracy {:.4f} | macro-F1 {:.4f}".format(acc_nodes, float(f1.mean())))
     flat = [int(v) for a in all_pred for v in a.tolist()]
-
-    def write_json(sub, doc):                                                             # {output}/{sub}/{logs}.json
-        os.makedirs(os.path.join(out_root, sub), exist_ok=True)
-        with open(os.path.join(out_root, sub, f'{logs}.json'), 'w') as f:
-            json.dump(doc, f)
-
+    write_json = _json_writer(out_root, logs)
     if save_predictions:
-        ap_dir = os.path.join(out_root, 'all_pred')                                       # OUTPUT / 'all_pred' (:172)
-        os.makedirs(ap_dir, exist_ok=True)
-        with open(os.path.join(ap_dir, logs), 'wb') as f:
-            pickle.dump(flat, f)                                                          # the reference's artefact (:174)
-        pred_dir = os.path.join(out_root, 'predictions')
-        os.makedirs(pred_dir, exist_ok=True)
-        with open(os.path.join(pred_dir, f'{logs}.pkl'), 'wb') as f:
-            pickle.dump({'all_pred': [a.tolist() for a in all_pred], 'num_nodes': [len(a) for a in all_pred]}, f)
+        _save_predictions(out_root, logs, flat, all_pred)
     result = {'accuracy': acc, 'accuracy_nodes': acc_nodes, 'precision': p, 'recall': r, 'f1': f1, 'confusion': conf,
               'all_pred': all_pred, 'all_pred_flat': flat}
-    if want_logits and flat_logits is None:
-        flat_logits = torch.empty((0, n_classes), dtype=torch.float32, device=device)
     if regions:
         result['regions'] = PP.extract_regions(data, all_pred, batch_pages=bs, device=device, logits=flat_logits if region_scores else None)
         doc = PP.regions_json(data, result['regions']) if (save_predictions or box_eval) else None
@@ -304,4 +275,142 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
             ref, bank = ev['reference'], ev['docbank']
             print(f"class {c}: precision {ref['precision'][c]} - recall {ref['recall'][c]} - f1 {ref['f1'][c]}"
                   f" (DocBank: {bank['precision'][c]} - {bank['recall'][c]} - {bank['f1'][c]})")
+    return result
+
+
+def _json_writer(out_root, logs):
+    def write_json(sub, doc):                                                             # {output}/{sub}/{logs}.json
+        os.makedirs(os.path.join(out_root, sub), exist_ok=True)
+        with open(os.path.join(out_root, sub, f'{logs}.json'), 'w') as f:
+            json.dump(doc, f)
+    return write_json
+
+
+def _save_predictions(out_root, logs, flat, all_pred, extra=None):
+    """The two prediction artefacts of the module docstring; ``extra``: further keys of ``predictions/{logs}.pkl``."""
+    ap_dir = os.path.join(out_root, 'all_pred')                                           # OUTPUT / 'all_pred' (:172)
+    os.makedirs(ap_dir, exist_ok=True)
+    with open(os.path.join(ap_dir, logs), 'wb') as f:
+        pickle.dump(flat, f)                                                              # the reference's artefact (:174)
+    pred_dir = os.path.join(out_root, 'predictions')
+    os.makedirs(pred_dir, exist_ok=True)
+    with open(os.path.join(pred_dir, f'{logs}.pkl'), 'wb') as f:
+        pickle.dump(dict({'all_pred': [a.tolist() for a in all_pred], 'num_nodes': [len(a) for a in all_pred]}, **(extra or {})), f)
+
+
+def _forward_pages(data, config, weights_path, want_logits, head=False, want_prob=False):
+    """What ``test()`` and ``predict()`` share: the model rebuilt from the config with the best weights, and one forward over
+    every page -- the resident engine path, or the module loop for a model the engine refuses.  Reads no label.
+    -> dict: ``device``, ``n_classes``, ``logs``, ``out_root``, ``bs``; ``pred`` (host int64 [nodes], pages in ``data.graphs``
+    order); ``logits`` (device float32 [nodes, C], None unless ``want_logits``); with ``head`` (the arg-max through
+    ``ops.predict_head``) also ``conf`` (host float32 [nodes]) and, with ``want_prob``, ``prob`` (host float32 [nodes, C])."""
+    if not (config.TRAINING.gpu >= 0 and torch.cuda.is_available()):
+        raise RuntimeError("model_predict runs on the MI355X HIP path only (no CPU fallback)")
+    device = torch.device('cuda', config.TRAINING.gpu)
+    n_classes = data.num_classes
+    in_feats = get_in_feats_(config)
+    logs = logs_from_config(config)
+    out_root = config.GENERAL.get('output_dir', 'output')
+    weights_path = weights_path or os.path.join(out_root, 'weights', f'{logs}.pt')
+
+    model = GcnSAGE(in_feats, int(hidden_width(config, in_feats, n_classes)), n_classes, config.TRAINING.n_layers,
+                    F.relu, config.TRAINING.dropout)
+    model.load_state_dict(torch.load(weights_path, map_location='cpu'))
+    model = model.to(device).eval()
+
+    bs = max(1, int(config.TRAINING.batch_size))
+    engine = None
+    flat_logits = None                                     # region_scores: the logits of all nodes, pages in data.graphs order
+    flat_conf = flat_prob = None
+    if len(data.graphs) > 0:
+        # evaluation applies no dropout: a model trained with --dropout takes the same path (forward_logits binds the p = 0 plan);
+        # only a model the engine refuses to build for (a dropout model outside the one-call plan) keeps the module loop below
+        from .engine import FusedGcnSageStep
+        try:
+            engine = FusedGcnSageStep(model)
+        except ValueError:
+            if not config.TRAINING.dropout:
+                raise
+    if engine is not None:
+        # the shipped configuration: pages resident in HBM, batches assembled on the device one forward ahead, one host call per
+        # forward (predict_resident); one device -> host copy of all predictions at the end
+        from .loop import BatchPipeline
+        pipe = BatchPipeline(G.ResidentPages(data.graphs, device))
+        out = predict_resident(engine, pipe, bs, return_logits=want_logits, head=head, return_prob=want_prob)
+        out = list(out) if isinstance(out, tuple) else [out]
+        flat_pred = out.pop(0).cpu().numpy()
+        if head:
+            flat_conf = out.pop(0).cpu().numpy()
+        if want_prob:
+            flat_prob = out.pop(0).cpu().numpy()
+        if want_logits:
+            flat_logits = out.pop(0)
+    else:
+        preds, kept, confs, probs = [], [], [], []
+        with torch.no_grad():
+            for b0 in range(0, len(data.graphs), bs):
+                logits = model(G.batch([g.to(device) for g in data.graphs[b0:b0 + bs]]))
+                if want_logits:
+                    kept.append(logits.float().clone())
+                if head:
+                    hp = ops.predict_head(logits.float(), want_prob=want_prob)
+                    preds.append(hp[0].cpu().numpy())
+                    confs.append(hp[1].cpu().numpy())
+                    if want_prob:
+                        probs.append(hp[2].cpu().numpy())
+                else:
+                    preds.append(logits.argmax(dim=1).cpu().numpy())
+        flat_pred = np.concatenate(preds)
+        if kept:
+            flat_logits = torch.cat(kept)
+        if head:
+            flat_conf = np.concatenate(confs)
+            flat_prob = np.concatenate(probs) if want_prob else None
+    if want_logits and flat_logits is None:
+        flat_logits = torch.empty((0, n_classes), dtype=torch.float32, device=device)
+    return dict(device=device, n_classes=n_classes, logs=logs, out_root=out_root, bs=bs, pred=flat_pred, logits=flat_logits,
+                conf=flat_conf, prob=flat_prob)
+
+
+def predict(data, config, weights_path=None, save_predictions=True, probabilities=False, regions=False, region_scores=False,
+            blocks=False, block_scores=False):
+    """The label-free sibling of ``test()``: the classes of the words of pages WITHOUT ground truth
+    (``PrebuiltPages.from_boxes(..., unlabeled=True)``; the reference's ``GenericPapers2Graphs`` route), and a confidence per
+    word.  On a labelled set the labels are ignored.  The model, the weights, the resident engine path and its fallback are
+    ``test()``'s; the arg-max is ``ops.predict_head`` (gte_predict_head: one launch per batch for class, confidence and softmax
+    row).  Nothing is computed from labels and no accuracy is printed.
+
+    Returns ``'all_pred'`` (int arrays per page), ``'all_pred_flat'`` (one flat list), ``'confidence'`` (float32 arrays per
+    page: the softmax probability of the predicted class, NaN for a row of non-finite logits); ``probabilities=True``:
+    ``'probabilities'`` (float32 [n_p, C] per page); ``regions`` / ``region_scores`` / ``blocks`` / ``block_scores``: ``'regions'``
+    and ``'blocks'`` as in ``test()`` (the ``*_scores`` imply their route).  ``save_predictions`` writes what ``test()`` writes
+    (module docstring), ``predictions/{logs}.pkl`` with the further key ``'confidence'`` (per-page lists)."""
+    region_scores, block_scores = bool(region_scores), bool(block_scores)
+    regions = bool(regions or region_scores)
+    blocks = bool(blocks or block_scores)
+    run = _forward_pages(data, config, weights_path, region_scores or block_scores, head=True, want_prob=bool(probabilities))
+    device, logs, out_root, bs = run['device'], run['logs'], run['out_root'], run['bs']
+    all_pred, confidence, all_prob, off = [], [], [], 0
+    for g in data.graphs:
+        n = g.num_nodes()
+        all_pred.append(run['pred'][off:off + n])
+        confidence.append(run['conf'][off:off + n])
+        if probabilities:
+            all_prob.append(run['prob'][off:off + n])
+        off += n
+    flat = [int(v) for a in all_pred for v in a.tolist()]
+    write_json = _json_writer(out_root, logs)
+    if save_predictions:
+        _save_predictions(out_root, logs, flat, all_pred, extra={'confidence': [c.tolist() for c in confidence]})
+    result = {'all_pred': all_pred, 'all_pred_flat': flat, 'confidence': confidence}
+    if probabilities:
+        result['probabilities'] = all_prob
+    if regions:
+        result['regions'] = PP.extract_regions(data, all_pred, batch_pages=bs, device=device, logits=run['logits'] if region_scores else None)
+        if save_predictions:
+            write_json('regions', PP.regions_json(data, result['regions']))
+    if blocks:
+        result['blocks'] = PP.extract_blocks(data, all_pred, batch_pages=bs, device=device, logits=run['logits'] if block_scores else None)
+        if save_predictions:
+            write_json('blocks', PP.blocks_json(data, result['blocks']))
     return result

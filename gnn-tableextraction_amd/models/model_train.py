@@ -150,6 +150,8 @@ def _check_layout(saved, now, path):
 
 
 def train(data, config, name_time=None):
+    if not getattr(data, 'labeled', True):
+        raise ValueError("train(): the pages carry no labels (labeled == False, from_boxes(unlabeled=True)): training needs ground truth")
     rank, local_rank, world = D.env_world()
     distributed = world > 1
     n_classes = data.num_classes

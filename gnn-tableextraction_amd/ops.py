@@ -704,6 +704,38 @@ def cross_entropy(logits, labels, class_weight=None) -> Tuple[torch.Tensor, torc
     return _WeightedCE.apply(logits, labels, class_weight)
 
 
+def predict_head(logits: torch.Tensor, n: Optional[int] = None, want_prob: bool = False, out_pred: Optional[torch.Tensor] = None,
+                 out_conf: Optional[torch.Tensor] = None, out_prob: Optional[torch.Tensor] = None):
+    """Class, confidence and (``want_prob`` or ``out_prob``) softmax row of the first ``n`` rows (default: all) of ``logits``
+    float32 [rows, C <= 16], any row stride, in one launch (gte_predict_head: first-index arg-max as ``torch.argmax`` on the CPU,
+    softmax in float64) -> ``(pred int64 [n], conf float32 [n][, prob float32 [n, C]])``.  ``out_pred`` / ``out_conf`` /
+    ``out_prob`` may be views (slices of flat buffers; ``out_prob`` with any row stride); they are returned as given."""
+    require_device(logits, "predict_head")
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise TypeError("predict_head: logits must be a 2-D float32 tensor")
+    logits = _row_major(logits)
+    rows, c = logits.shape
+    n = rows if n is None else int(n)
+    if not 0 <= n <= rows:
+        raise ValueError(f"predict_head: n = {n} outside 0 .. {rows} rows of logits")
+    dev = logits.device
+    pred = torch.empty(n, dtype=torch.int64, device=dev) if out_pred is None else out_pred
+    conf = torch.empty(n, dtype=torch.float32, device=dev) if out_conf is None else out_conf
+    prob = out_prob if out_prob is not None else (torch.empty((n, c), dtype=torch.float32, device=dev) if want_prob else None)
+    for t, name, dtype in ((pred, "out_pred", torch.int64), (conf, "out_conf", torch.float32)):
+        require_device(t, "predict_head")
+        if t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or (n > 1 and t.stride(0) != 1):
+            raise ValueError(f"predict_head: {name} must be a packed {dtype} vector of {n} entries")
+    if prob is not None:
+        require_device(prob, "predict_head")
+        if (prob.dtype != torch.float32 or prob.dim() != 2 or tuple(prob.shape) != (n, c) or prob.stride(1) != 1
+                or (n > 1 and prob.stride(0) < c)):
+            raise ValueError(f"predict_head: out_prob must be float32 [{n}, {c}] with contiguous rows")
+    check(_lib.load().gte_predict_head(ptr(logits), _ld(logits), n, c, ptr(pred), ptr(conf), ptr(prob),
+                                       0 if prob is None else _ld(prob), current_stream()), "gte_predict_head")
+    return (pred, conf) if prob is None else (pred, conf, prob)
+
+
 GEMM_F32, GEMM_SPLIT_BF16 = 0, 1
 
 

@@ -471,6 +471,22 @@ int gte_token_pool_max_dim(void);     /* 4096 */
 int gte_token_pool_access_bytes(const float* table, int dim, const float* out, int64_t ldo);   /* 16 or 4; host arithmetic only */
 int gte_token_pool_f32(const int32_t* tok, int64_t n_words, int width, const float* table, int64_t n_vocab, int dim, int mode,
                        const int64_t* row_map, float* out, int64_t ldo, void* stream);
+/* The per-word head of label-free prediction (model_predict.predict): class, confidence and, on request, the softmax row of every
+ * node in ONE pass over logits float [n_nodes, n_classes] (row i at logits + i * ld_logits, ld_logits >= n_classes,
+ * 1 <= n_classes <= 16: the step engine's class limit).  Per row, with l_j its entries:
+ *   m    = the row's maximum; pred[i] = the FIRST index that holds it.  A NaN counts as greater than every number and the first NaN
+ *          wins; infinities compare as numbers: what torch.argmax(logits, 1) returns on the CPU ([1, nan, 3, nan] -> 1, a row
+ *          of -inf -> 0).
+ *   in float64, in index order j = 0 .. C-1:  e_j = exp((double)l_j - (double)m);  S = e_0 + e_1 + ...;
+ *   conf[i] = (float)(e_pred / S);  prob != NULL: prob[i * ld_prob + j] = (float)(e_j / S), ld_prob >= n_classes.
+ * A row that holds NaN or +inf, or -inf only, yields NaN in conf and in its prob row (inf - inf; torch.softmax does the same).
+ * Columns n_classes .. ld_logits-1 of logits are never read; nothing is written past row n_nodes-1 or past column n_classes-1 of
+ * prob.  pred int64 [n_nodes], conf float [n_nodes], packed.  One launch, a lane per node, grid-stride (n_nodes is not bounded by
+ * the grid); no atomics, no LDS, no workspace, no synchronisation: deterministic.  n_nodes == 0 is GTE_OK with nothing launched.
+ * n_classes outside 1 .. 16, ld_logits < n_classes, prob != NULL with ld_prob < n_classes, n_nodes < 0, and with n_nodes > 0 a
+ * NULL logits / pred / conf or a misaligned pointer return GTE_ERR_INVALID_ARGUMENT before any launch. */
+int gte_predict_head(const float* logits, int64_t ld_logits, int64_t n_nodes, int n_classes, int64_t* pred, float* conf,
+                     float* prob /* may be NULL */, int64_t ld_prob, void* stream);
 /* inv_deg[v] = 1/(indptr[v+1]-indptr[v]) or 0  (models.py:74-78 as a standalone vector) */
 int gte_inv_degree(const int32_t* indptr, float* inv_deg, int64_t n_nodes, void* stream);
 
