@@ -67,6 +67,10 @@ SIGNATURES = {
     "gte_block_vote_max_categories": (c_int, []),
     "gte_block_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    # rows, columns and cells of named tables (csrc/table_grid.hip)
+    "gte_table_grid_max_extent": (c_int, []),
+    "gte_table_grid_max_gap": (c_int, []),
+    "gte_table_grid": (c_int, [c_void_p, c_void_p, c_int64, c_int64] + [c_void_p] * 5 + [c_int64, c_uint32, c_uint32] + [c_void_p] * 7),
     # word labels and figure nodes from page annotations (csrc/word_labels.hip)
     "gte_word_labels_chunk": (c_int, []),
     "gte_word_labels": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_uint32, c_int,

@@ -1,12 +1,15 @@
 """From node predictions to page objects: the reference's ``components/graphs/postprocessing*.py``.
 
-Two routes, each an entry point that is three public stages in a row -- host packing, ONE launch per ``batch_pages`` pages, host
+Three routes, each an entry point that is public stages in a row -- host packing, ONE launch per ``batch_pages`` pages, host
 unpacking -- so that the host stages run (and are tested) without a device, with a CPU oracle in place of the launch:
   ``extract_regions`` = ``region_batches`` -> ``page_regions`` (gte_page_regions[_scored]) -> ``region_tuples``
   ``extract_blocks``  = ``pack_blocks`` -> ``block_vote`` (gte_block_vote) -> ``blocks_to_pages`` (with ``assemble_tables``)
                         and, with ``logits``: -> ``pack_final_blocks`` -> ``block_scores`` (gte_block_scores) -> ``attach_block_scores``
-``regions_json`` / ``regions_gt_json`` / ``blocks_json`` / ``blocks_gt_json`` lay the results out as the documents the reference's
-box-level evaluation reads (``utils.metrics.evaluate_regions``; the block documents hold floats: ``float_boxes=True``).
+  ``extract_tables``  = ``region_batches`` -> ``page_regions`` -> ``table_batch`` -> ``table_grids`` (gte_table_grid) ->
+                        ``tables_from_grids``: what is IN a predicted table -- rows, columns, cells, texts (``table_csv``)
+``regions_json`` / ``regions_gt_json`` / ``blocks_json`` / ``blocks_gt_json`` / ``table_structure_json`` lay the results out as the
+documents the reference's box-level evaluation reads (``utils.metrics.evaluate_regions``; the block documents hold floats:
+``float_boxes=True``).
 """
 from __future__ import annotations
 
@@ -655,3 +658,264 @@ def blocks_gt_json(data):
                 raise ValueError(f"blocks_gt_json: page {i} ({name}): {row!r} is no [x0, y0, x1, y1, category]")
             found.setdefault(int(row[4]), {}).setdefault(name, []).append([float(v) for v in row[:4]])
     return {CATEGORY_NAMES[c]: found[c] for c in sorted(found)}
+
+
+# ---- the grid of a predicted table: rows, columns, cells (no reference counterpart; the projection profile on the device) --------
+DEFAULT_COL_ROLES = (_COLH, _TCELL)                       # words that build the column profile: a spanning cell would bridge columns
+DEFAULT_ROW_ROLES = (_COLH, _SP, _TCELL)
+
+
+class TableGrids(NamedTuple):
+    """Result of :func:`table_grids` (gte_table_grid; the rule: include/gte.h)."""
+    cell: torch.Tensor          # int32 [n, 4]  (r0, r1, c0, c1): the word's span in row / column bands; -1 on an axis it meets no band of
+    cell_box: torch.Tensor      # int32 [n, 4]  (start of column c0, start of row r0, end of column c1, end of row r1); 0 on such an axis
+    table_shape: torch.Tensor   # int32 [T, 2]  (n_rows, n_cols)
+    table_box: torch.Tensor     # int32 [T, 4]  union of the table's words
+    table_words: torch.Tensor   # int32 [T]
+    table_status: torch.Tensor  # int32 [T]     0 fine, 1 no word, 2 too large for a grid / bad gap, 3 bad page
+
+
+class TableBatch(NamedTuple):
+    """Result of :func:`table_batch`: the tables of one batch of pages, in ascending root order."""
+    table: torch.Tensor         # int32 [n]     root of the word's TABLE region, -1 for every other word
+    root: torch.Tensor          # int32 [T]
+    page: torch.Tensor          # int32 [T]     page of the batch
+    gap: torch.Tensor           # int32 [T, 2]  (gap_x, gap_y)
+    score: Optional[torch.Tensor] = None      # float32 [T]  the regions' confidences, where the regions carry them
+
+
+def role_mask(roles) -> int:
+    """Bit mask of a sequence of categories 0 .. 31 (an int is taken as the mask itself)."""
+    if isinstance(roles, (int, np.integer)):
+        mask = int(roles)
+    else:
+        roles = [int(r) for r in roles]
+        if any(not 0 <= r < 32 for r in roles):
+            raise ValueError(f"table grids: the roles {roles} must lie in 0 .. 31")
+        mask = sum({1 << r for r in roles})
+    if not 0 <= mask < 1 << 32:
+        raise ValueError(f"table grids: role mask {mask} does not fit 32 bits")
+    return mask
+
+
+def table_grids(table: torch.Tensor, bbox: torch.Tensor, role: torch.Tensor, node_off, table_root: torch.Tensor,
+                table_page: torch.Tensor, table_gap: torch.Tensor, col_roles=DEFAULT_COL_ROLES, row_roles=DEFAULT_ROW_ROLES) -> TableGrids:
+    """Rows, columns and cells of the listed tables (gte_table_grid: ONE launch, one workgroup per table; the rule is the contract
+    text in include/gte.h).  ``table`` int32 [n] the id of every word's table (< 0: none), ``bbox`` int32 [n, 4], ``role`` int32 [n]
+    the words' categories, pages concatenated; ``node_off`` host sequence [pages + 1]; ``table_root`` / ``table_page`` int32 [T]
+    and ``table_gap`` int32 [T, 2] on the device (:func:`table_batch` makes them); ``col_roles`` / ``row_roles``: the categories
+    (or a bit mask) whose words build the column / row profile.  ``cell`` is pre-filled with -1 and ``cell_box`` with 0: words of
+    no listed table keep that.  ``ValueError`` on shapes, dtypes or offsets that do not fit.  No synchronisation."""
+    lib, P = _lib.load(), _lib.ptr
+    named = {"table": table, "bbox": bbox, "role": role, "table_root": table_root, "table_page": table_page, "table_gap": table_gap}
+    for t in named.values():
+        _lib.require_device(t, "table_grids")
+    dev = bbox.device
+    if any(t.dtype != torch.int32 for t in named.values()) or any(t.device != dev for t in named.values()):
+        raise ValueError("table_grids: " + ", ".join(f"{k} {t.dtype} on {t.device}" for k, t in named.items()) + " must be int32 on one device")
+    n, nt = bbox.shape[0], table_root.numel()
+    if bbox.dim() != 2 or bbox.shape[1] != 4 or tuple(table.shape) != (n,) or tuple(role.shape) != (n,) or table_root.dim() != 1 \
+            or tuple(table_page.shape) != (nt,) or tuple(table_gap.shape) != (nt, 2):
+        raise ValueError("table_grids: " + ", ".join(f"{k} is {tuple(t.shape)}" for k, t in named.items()))
+    off_h, d_off = _lib.partition_offsets(node_off, n, "table_grids: the word offsets", dev)
+    cols, rows = role_mask(col_roles), role_mask(row_roles)
+    cell = torch.full((n, 4), -1, dtype=torch.int32, device=dev)
+    cell_box = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    shape = torch.empty((nt, 2), dtype=torch.int32, device=dev)
+    box = torch.empty((nt, 4), dtype=torch.int32, device=dev)
+    words = torch.empty(nt, dtype=torch.int32, device=dev)
+    status = torch.empty(nt, dtype=torch.int32, device=dev)
+    _lib.check(lib.gte_table_grid(P(bbox.contiguous()), P(d_off), off_h.size - 1, n, P(table.contiguous()), P(role.contiguous()),
+                                  P(table_root.contiguous()), P(table_page.contiguous()), P(table_gap.contiguous()), nt, cols, rows,
+                                  P(cell), P(cell_box), P(shape), P(box), P(words), P(status), _lib.current_stream()), "gte_table_grid")
+    return TableGrids(cell, cell_box, shape, box, words, status)
+
+
+def table_batch(reg: PageRegions, bbox: torch.Tensor, role: torch.Tensor, node_off, col_gap='auto', row_gap=0, col_gap_em=0.5,
+                table_group=_TABLE, min_words=1) -> TableBatch:
+    """The TABLE regions of a batch as the arguments of :func:`table_grids` (torch plumbing, no launch of the library's): the
+    regions of kind ``table_group`` with at least ``min_words`` words, in ascending root order -- one to one, in order, the
+    kind-4 tuples of ``region_tuples`` -- their pages, ``table`` (``reg.comp`` for the words of these regions, -1 elsewhere) and
+    the gaps.  ``bbox`` int [n, 4], ``role`` int [n] (checked against ``node_off``, the host offsets of the batch's pages).
+
+    A gap is an int, used as it is, or ``'auto'``: ``floor(col_gap_em * (sum / count))`` over the table's words of their heights
+    ``|y1 - y0|`` -- the sums exact integers, the quotient and the product in float64 -- clamped to ``0 .. gte_table_grid_max_gap()``.
+    Half a line height is meant to lie between the space inside a cell (a word space, about a quarter of the height) and the
+    gutter between two columns.  THE DEFAULT IS NOT VALIDATED ON ANY REAL PAGE: none has been seen; only synthetic tables
+    (tests/table_grid_ref.py) come back exactly under it.  Rows use gap 0 by default: lines of one row share their pixels."""
+    lib = _lib.load()
+    dev = reg.comp.device
+    n = reg.comp.numel()
+    off = np.asarray(node_off, dtype=np.int64).reshape(-1)
+    if tuple(bbox.shape) != (n, 4) or role.numel() != n or off.size < 1 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+        raise ValueError(f"table_batch: {n} nodes, bbox is {tuple(bbox.shape)}, role has {role.numel()} entries, node_off ends at "
+                         f"{int(off[-1]) if off.size else None}")
+    keep = (reg.group == int(table_group)) & (reg.n_words >= int(min_words))
+    root = reg.root[keep]
+    nt = root.numel()
+    is_root = torch.zeros(n + 1, dtype=torch.bool, device=dev)
+    is_root[root] = True
+    comp = reg.comp.long()
+    table = torch.where(is_root[comp.clamp(min=0)] & (comp >= 0), reg.comp, torch.full_like(reg.comp, -1))
+    max_gap = lib.gte_table_grid_max_gap()
+    gaps = []
+    for what, g in (("col_gap", col_gap), ("row_gap", row_gap)):
+        if isinstance(g, str):
+            if g != 'auto':
+                raise ValueError(f"table_batch: {what} = {g!r} is neither an int nor 'auto'")
+            member = table >= 0
+            height = (bbox[:, 3].long() - bbox[:, 1].long()).abs()
+            total = torch.zeros(n + 1, dtype=torch.int64, device=dev).index_add_(0, table[member].long(), height[member])
+            mean = total[root].double() / reg.n_words[keep].double()
+            gaps.append(torch.floor(float(col_gap_em) * mean).clamp(0, max_gap).to(torch.int32))
+        else:
+            gaps.append(torch.full((nt,), int(g), dtype=torch.int32, device=dev))
+    return TableBatch(table.to(torch.int32), root.to(torch.int32), reg.page[keep].to(torch.int32), torch.stack(gaps, dim=1).contiguous(),
+                      None if reg.score is None else reg.score[keep])
+
+
+def tables_from_grids(table, bbox, role, node_off, table_root, table_page, grids, texts, col_roles=DEFAULT_COL_ROLES,
+                      row_roles=DEFAULT_ROW_ROLES, score=None, header_role=_COLH):
+    """Stage five of :func:`extract_tables`: pure host code on numpy arrays (no device is touched) -- the launch's arguments and
+    its six outputs (``grids``: a :class:`TableGrids` of host arrays, or of a CPU oracle's) as per-page lists of tables, in
+    ascending root order.  ``texts``: per page the words' texts (None: every text is ``''``).  A table is a dict:
+
+    ``'box'``, ``'n_rows'``, ``'n_cols'``, ``'n_words'``, ``'status'`` (gte_table_grid's; a table with a status other than 0 has
+    no bands and all its words are ``'loose'``), ``'score'`` when ``score`` [T] is given;
+    ``'rows'`` / ``'cols'``: ``[lo, hi]`` per band;  ``'header_rows'``: the rows where strictly more than half of the row-profile
+    words are column headers (``header_role``);
+    ``'cells'``: one entry per distinct span ``(r0, r1, c0, c1)``, ordered by ``(r0, c0, r1, c1)`` -- ``'row': [r0, r1]``,
+    ``'col': [c0, c1]``, ``'role'`` (the lowest category with the most words), ``'words'`` (page-local indices ordered by
+    ``(y_lo, x_lo, index)``), ``'text'`` (their texts joined by one space), ``'box'`` (the span's ``cell_box``);
+    ``'loose'``: the words with -1 on an axis (page-local indices, ascending);
+    ``'grid'``: ``n_rows`` x ``n_cols`` strings, a cell's text at ``(r0, c0)`` and ``''`` elsewhere; cells that share a position
+    are joined by one space in cell order."""
+    table, role = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (table, role))
+    bbox = np.asarray(bbox, dtype=np.int64).reshape(-1, 4)
+    node_off = np.asarray(node_off, dtype=np.int64).reshape(-1)
+    table_root, table_page = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (table_root, table_page))
+    cell, cell_box, shape, tbox, n_words, status = (np.asarray(a, dtype=np.int64) for a in grids)
+    cols, rows = role_mask(col_roles), role_mask(row_roles)
+    in_mask = lambda r, mask: (r >= 0) & (r < 32) & (((mask >> np.clip(r, 0, 31)) & 1) == 1)
+    lo_y, lo_x = np.minimum(bbox[:, 1], bbox[:, 3]), np.minimum(bbox[:, 0], bbox[:, 2])
+    out = [[] for _ in range(node_off.size - 1)]
+    for t in np.argsort(table_root, kind='stable'):
+        p = int(table_page[t])
+        if not 0 <= p < len(out):
+            continue
+        n0, n1 = int(node_off[p]), int(node_off[p + 1])
+        v = n0 + np.nonzero(table[n0:n1] == table_root[t])[0] if table_root[t] >= 0 else np.zeros(0, dtype=np.int64)
+        words_text = (lambda i: '') if texts is None or texts[p] is None else (lambda i, tx=texts[p]: str(tx[i - n0]))
+        nr, nc = (int(s) for s in shape[t]) if status[t] == 0 else (0, 0)
+        entry = {'box': [int(c) for c in tbox[t]], 'n_rows': nr, 'n_cols': nc, 'n_words': int(n_words[t]), 'status': int(status[t])}
+        if score is not None:
+            entry['score'] = float(score[t])
+        row_band, col_band = [None] * nr, [None] * nc
+        head, total = [0] * nr, [0] * nr
+        if status[t] == 0:
+            for i in v[in_mask(role[v], cols)]:           # a profile word sits in one band and carries its extent
+                col_band[cell[i, 2]] = [int(cell_box[i, 0]), int(cell_box[i, 2])]
+            for i in v[in_mask(role[v], rows)]:
+                row_band[cell[i, 0]] = [int(cell_box[i, 1]), int(cell_box[i, 3])]
+                total[cell[i, 0]] += 1
+                head[cell[i, 0]] += int(role[i] == header_role)
+        entry['rows'], entry['cols'] = row_band, col_band
+        entry['header_rows'] = [r for r in range(nr) if 2 * head[r] > total[r]]
+        placed = v[(cell[v] >= 0).all(axis=1)] if status[t] == 0 else v[:0]
+        entry['loose'] = sorted(int(i - n0) for i in set(v.tolist()) - set(placed.tolist()))
+        by_span = {}
+        for i in sorted(placed.tolist(), key=lambda i: (lo_y[i], lo_x[i], i)):
+            by_span.setdefault((int(cell[i, 0]), int(cell[i, 2]), int(cell[i, 1]), int(cell[i, 3])), []).append(i)
+        grid = [['' for _ in range(nc)] for _ in range(nr)]
+        cells = []
+        for (r0, c0, r1, c1), ids in sorted(by_span.items()):
+            values, counts = np.unique(role[ids], return_counts=True)      # ascending: the first maximum is the lowest category
+            text = ' '.join(words_text(i) for i in ids)
+            cells.append({'row': [r0, r1], 'col': [c0, c1], 'role': int(values[counts.argmax()]),
+                          'words': [int(i - n0) for i in ids], 'text': text, 'box': [int(c) for c in cell_box[ids[0]]]})
+            grid[r0][c0] = text if not grid[r0][c0] else grid[r0][c0] + ' ' + text
+        entry['cells'], entry['grid'] = cells, grid
+        out[p].append(entry)
+    return out
+
+
+def extract_tables(data, all_pred, class_category=None, col_gap='auto', row_gap=0, col_gap_em=0.5, col_roles=DEFAULT_COL_ROLES,
+                   row_roles=DEFAULT_ROW_ROLES, min_words=1, batch_pages=64, device=None, logits=None):
+    """The grid of every predicted table: ``region_batches`` -> ``page_regions`` -> ``table_batch`` -> ``table_grids``
+    (gte_table_grid, ONE launch per ``batch_pages`` pages) -> ``tables_from_grids``.  The tables of a page correspond one to one,
+    in order, to the kind-4 tuples of ``extract_regions`` for the same arguments: a table is a connected region of words whose
+    predicted class is column header, spanning cell or table cell.  Inside it the words of the ``col_roles`` categories build the
+    column profile (default: headers and table cells -- a spanning cell would bridge the columns it spans; it still receives its
+    span ``'col': [c0, c1]``) and those of ``row_roles`` the row profile; ``role`` of a word is the original category of its
+    predicted class (``class_category``, default ``DEFAULT_CLASS_CATEGORY``).  Two profile words share a column when the free
+    space between them is at most ``col_gap`` pixels, ``'auto'``: ``floor(col_gap_em * mean word height of the table)``
+    (``table_batch``: NOT VALIDATED ON ANY REAL PAGE), and a row when it is at most ``row_gap``.
+
+    Texts from ``data.pages[i]['texts']`` (a page without them gets ``''``), boxes from ``data.pages[i]['bboxs']``.  ``logits``
+    as for ``extract_regions``: every table gains ``'score'``, its region's confidence.  Returns per page a list of table dicts
+    (``tables_from_grids``).  A table wider or higher than ``gte_table_grid_max_extent()`` pixels comes back with ``'status'`` 2
+    and no grid."""
+    device = _lib.default_device(device)
+    cat = np.asarray(DEFAULT_CLASS_CATEGORY if class_category is None else class_category, dtype=np.int64).reshape(-1)
+    group = [(_TABLE if int(k) in (_COLH, _SP, _TCELL) else (int(k) if int(k) in GROUP_NAMES and int(k) != _TABLE else -1)) for k in cat]
+    d_cat = torch.from_numpy(cat.astype(np.int32)).to(device)
+    node_off = _offsets([g.num_nodes() for g in data.graphs])
+    if logits is not None:
+        logits = torch.as_tensor(logits)
+        if logits.dim() != 2 or logits.shape[0] != int(node_off[-1]):
+            raise ValueError(f"extract_tables: logits of shape {tuple(logits.shape)} for {int(node_off[-1])} nodes")
+    for i, p in enumerate(all_pred):                      # on the host, before a class id becomes a device index
+        p = np.asarray(p, dtype=np.int64).reshape(-1)
+        if p.size and (p.min() < 0 or p.max() >= cat.size):
+            raise ValueError(f"extract_tables: page {i} holds a class outside the {cat.size} of class_category")
+    d_group = torch.as_tensor(group, dtype=torch.int32, device=device)
+    out = [[] for _ in data.graphs]
+    for ids, bg, grp, bbox in region_batches(data, all_pred, group, batch_pages, device):
+        rows = None if logits is None else logits[int(node_off[ids.start]):int(node_off[ids.stop])].to(device)
+        reg = page_regions(bg, grp, bbox, logits=rows, class_group=None if rows is None else d_group)
+        pred = np.concatenate(_page_words(data, all_pred, ids, "extract_tables")[0])
+        role = d_cat[torch.from_numpy(pred).to(device)]
+        off = node_off[ids.start:ids.stop + 1] - node_off[ids.start]
+        tb = table_batch(reg, bbox, role, off, col_gap, row_gap, col_gap_em, _TABLE, min_words)
+        grids = table_grids(tb.table, bbox, role, off, tb.root, tb.page, tb.gap, col_roles, row_roles)
+        texts = [data.pages[i].get('texts') for i in ids]
+        out[ids.start:ids.stop] = tables_from_grids(tb.table.cpu().numpy(), bbox.cpu().numpy(), role.cpu().numpy(), off,
+                                                    tb.root.cpu().numpy(), tb.page.cpu().numpy(), [a.cpu().numpy() for a in grids], texts,
+                                                    col_roles, row_roles, None if tb.score is None else tb.score.cpu().numpy())
+    return out
+
+
+def table_csv(table) -> str:
+    """A table's ``'grid'`` as CSV text (the ``csv`` module's default dialect: ``\\r\\n`` line ends, quotes where needed)."""
+    import csv
+    import io
+    buf = io.StringIO()
+    csv.writer(buf).writerows(table['grid'])
+    return buf.getvalue()
+
+
+def tables_json(data, tables):
+    """``{page_name: [table, ...]}`` of ``extract_tables``' result: every page of the set, the table dicts as they are (they
+    hold ints, floats, strings and lists only)."""
+    return {str(data.pages[i]['page']): list(page) for i, page in enumerate(tables)}
+
+
+def table_structure_json(data, tables):
+    """The tables' structure as a document in the layout of ``regions_json`` -- ``{kind: {page_name: {'bboxes': [...], 'scores':
+    [...]}}}`` -- with the kinds ``'table'`` (the table's box), ``'table-row'`` (``[box.x0, row.lo, box.x1, row.hi]`` per row
+    band) and ``'table-col'`` (``[col.lo, box.y0, col.hi, box.y1]`` per column band): what PubTables-1M annotates as TABLE,
+    TABLE_ROW and TABLE_COL (categories 4, 12 and 11 of ``blocks_gt_json``).  Every box of a table scores the table's
+    ``'score'``, or 1.0 where it has none."""
+    doc = {'table': {}, 'table-row': {}, 'table-col': {}}
+    for i, page in enumerate(tables):
+        name = str(data.pages[i]['page'])
+        for tab in page:
+            x0, y0, x1, y1 = tab['box']
+            boxes = {'table': [[x0, y0, x1, y1]], 'table-row': [[x0, lo, x1, hi] for lo, hi in tab['rows']],
+                     'table-col': [[lo, y0, hi, y1] for lo, hi in tab['cols']]}
+            for kind, found in boxes.items():
+                if found:
+                    entry = doc[kind].setdefault(name, {'bboxes': [], 'scores': []})
+                    entry['bboxes'] += [[int(c) for c in b] for b in found]
+                    entry['scores'] += [float(tab.get('score', 1.0))] * len(found)
+    return doc

@@ -18,6 +18,8 @@ the reference; ``test()`` only calls them.  Output contract (what post-processin
                                       the reference's box-level evaluation reads (``regions_json``)
                                       (``region_scores=True``: with the regions' confidences as scores; ``box_eval=True``: the
                                       result also holds that evaluation, ``metrics.evaluate_regions``)
+  ``{output}/tables/{logs}.json``     ``tables=True`` only: ``{page: [table, ...]}``, the grid of every predicted table
+                                      (``postprocessing.extract_tables`` / ``tables_json``)
 ``predict(data, config)`` is the label-free sibling (the reference's ``GenericPapers2Graphs`` route, loader.py:431-573): the same
 forward on pages without ground truth, a confidence per word, the same artefacts (``predictions/{logs}.pkl`` gains
 ``'confidence'``), no metric.
@@ -188,8 +190,17 @@ def predict_resident(engine, pipe, batch_pages: int, page_ids=None, return_logit
 
 
 def test(data, config, weights_path=None, save_predictions=True, regions=False, region_scores=False, box_eval=False, blocks=False,
-         block_scores=False, block_eval=False, doc_eval=False):
-    """``doc_eval=True``: the result gains ``'doc_eval'`` = ``metrics.evaluate_doc`` of the pages' labels, ``all_pred`` and the
+         block_scores=False, block_eval=False, doc_eval=False, tables=False, table_eval=False):
+    """``tables=True``: the result gains ``'tables'`` = ``extract_tables(data, all_pred)`` -- per page the grid of every predicted
+    table: rows, columns, cells and their texts (gte_table_grid; the default column gap is not validated on real pages, see
+    ``postprocessing.table_batch``) -- and with ``save_predictions`` ``{output}/tables/{logs}.json`` is written (``tables_json``).
+
+    ``table_eval=True`` (implies ``tables``): the result gains ``'table_eval'`` = ``evaluate_regions(table_structure_json(...),
+    gt, float_boxes=True)``, gt = the ``'table'``, ``'table-row'`` and ``'table-col'`` kinds of ``blocks_gt_json(data)`` (the pages
+    carry ``'annotations'``; PubTables-1M's TABLE, TABLE_ROW and TABLE_COL): AP at IoU 0.50 .. 0.95 of the predicted table, row
+    and column boxes.
+
+    ``doc_eval=True``: the result gains ``'doc_eval'`` = ``metrics.evaluate_doc`` of the pages' labels, ``all_pred`` and the
     word boxes ``data.pages[i]['bboxs']``: area-weighted precision / recall / F1 per class (the reference's ``evaluate_doc``,
     models/evaluate.py:142-209), both as the reference computes them (``'reference'``) and by the DocBank formula (``'docbank'``);
     one line per class is printed.  A page without ``'bboxs'`` raises ``ValueError``.
@@ -265,6 +276,12 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
         if want_block_eval:
             gt = PP.blocks_gt_json(data) if block_eval is True else block_eval
             result['block_eval'] = metrics.evaluate_regions(doc, gt, device=device, float_boxes=True)
+    if tables or table_eval:
+        _add_tables(result, data, all_pred, bs, device, write_json if save_predictions else None)
+        if table_eval:
+            gt = {kind: pages for kind, pages in PP.blocks_gt_json(data).items() if kind in ('table', 'table-row', 'table-col')}
+            result['table_eval'] = metrics.evaluate_regions(PP.table_structure_json(data, result['tables']), gt, device=device,
+                                                            float_boxes=True)
     if doc_eval:
         for i, page in enumerate(data.pages):
             if 'bboxs' not in page:
@@ -276,6 +293,13 @@ def test(data, config, weights_path=None, save_predictions=True, regions=False, 
             print(f"class {c}: precision {ref['precision'][c]} - recall {ref['recall'][c]} - f1 {ref['f1'][c]}"
                   f" (DocBank: {bank['precision'][c]} - {bank['recall'][c]} - {bank['f1'][c]})")
     return result
+
+
+def _add_tables(result, data, all_pred, bs, device, write_json):
+    """``tables=True`` of ``test()`` and ``predict()``: ``result['tables']`` and, with a writer, ``tables/{logs}.json``."""
+    result['tables'] = PP.extract_tables(data, all_pred, batch_pages=bs, device=device)
+    if write_json is not None:
+        write_json('tables', PP.tables_json(data, result['tables']))
 
 
 def _json_writer(out_root, logs):
@@ -373,7 +397,7 @@ def _forward_pages(data, config, weights_path, want_logits, head=False, want_pro
 
 
 def predict(data, config, weights_path=None, save_predictions=True, probabilities=False, regions=False, region_scores=False,
-            blocks=False, block_scores=False):
+            blocks=False, block_scores=False, tables=False):
     """The label-free sibling of ``test()``: the classes of the words of pages WITHOUT ground truth
     (``PrebuiltPages.from_boxes(..., unlabeled=True)``; the reference's ``GenericPapers2Graphs`` route), and a confidence per
     word.  On a labelled set the labels are ignored.  The model, the weights, the resident engine path and its fallback are
@@ -383,8 +407,9 @@ def predict(data, config, weights_path=None, save_predictions=True, probabilitie
     Returns ``'all_pred'`` (int arrays per page), ``'all_pred_flat'`` (one flat list), ``'confidence'`` (float32 arrays per
     page: the softmax probability of the predicted class, NaN for a row of non-finite logits); ``probabilities=True``:
     ``'probabilities'`` (float32 [n_p, C] per page); ``regions`` / ``region_scores`` / ``blocks`` / ``block_scores``: ``'regions'``
-    and ``'blocks'`` as in ``test()`` (the ``*_scores`` imply their route).  ``save_predictions`` writes what ``test()`` writes
-    (module docstring), ``predictions/{logs}.pkl`` with the further key ``'confidence'`` (per-page lists)."""
+    and ``'blocks'`` as in ``test()`` (the ``*_scores`` imply their route); ``tables``: ``'tables'`` as in ``test()``.
+    ``save_predictions`` writes what ``test()`` writes (module docstring), ``predictions/{logs}.pkl`` with the further key
+    ``'confidence'`` (per-page lists)."""
     region_scores, block_scores = bool(region_scores), bool(block_scores)
     regions = bool(regions or region_scores)
     blocks = bool(blocks or block_scores)
@@ -413,4 +438,6 @@ def predict(data, config, weights_path=None, save_predictions=True, probabilitie
         result['blocks'] = PP.extract_blocks(data, all_pred, batch_pages=bs, device=device, logits=run['logits'] if block_scores else None)
         if save_predictions:
             write_json('blocks', PP.blocks_json(data, result['blocks']))
+    if tables:
+        _add_tables(result, data, all_pred, bs, device, write_json if save_predictions else None)
     return result

@@ -342,6 +342,53 @@ int gte_block_scores(const int32_t* bbox, const int32_t* node_off, const float* 
                      int n_cat, int64_t n_pages, int64_t n_nodes, int64_t n_blocks, int64_t max_page_words, int64_t max_page_blocks,
                      float* score, int32_t* n_words, void* stream);
 
+/* ---- table grids: rows, columns and cells of the tables another stage has named (no reference counterpart: the reference stops at
+ * where a table is; graphs/utils.py get_subgraph_bbox() is a stub) -- the projection profile as exact integer arithmetic ----
+ * Inputs, pages concatenated: bbox int32 [n_nodes, 4] the word boxes (x0, y0, x1, y1); node_off[n_pages + 1]; table int32 [n_nodes]
+ * the id of every word's table (by convention the root of its region, gte_page_regions' comp; < 0: none); role int32 [n_nodes] the
+ * category of every word.  The T = n_tables LISTED tables: table_root[t] the id, table_page[t] the page whose words are scanned for
+ * table[v] == table_root[t] (its MEMBERS), table_gap[2 t], table_gap[2 t + 1] = (gap_x, gap_y).  col_roles / row_roles: bit k set =
+ * words of category k build the column / row profile.
+ * The rule, per table, for the x axis with gap = gap_x and roles = col_roles (the y axis: y0 / y1, gap_y, row_roles):
+ *   interval   a member has lo = min(x0, x1), hi = max(x0, x1), hi1 = max(hi, lo + 1) (a zero-width word still occupies one pixel);
+ *              origin = min lo over all members.
+ *   status 2   max hi1 - origin > gte_table_grid_max_extent() on either axis, a gap outside 0 .. gte_table_grid_max_gap(), or a
+ *              member coordinate outside -2^30 .. 2^30: no grid -- shape (0, 0), the members' rows get cell = -1, cell_box = 0.
+ *   profile    a member is a PROFILE WORD of the axis when 0 <= role < 32 and bit role of roles is set; it occupies the pixels
+ *              [lo, hi1 + gap).
+ *   bands      the maximal runs of occupied pixels, numbered from 0 in ascending coordinate (two neighbouring profile words share a
+ *              band exactly when the free space between them is <= gap); the EXTENT of a band is [run start, run end - gap).
+ *   span       of EVERY member, profile word or not: c0 / c1 = the bands of the first / last occupied pixel inside [lo, hi1);
+ *              (-1, -1) when no pixel inside is occupied.  (A profile word has c0 == c1; a word that is none and lies within gap
+ *              pixels behind a band's last word meets that band, as a profile word there would have joined it.)
+ * With r0 / r1 the span on the y axis:
+ *   cell[v]         (r0, r1, c0, c1)
+ *   cell_box[v]     (start of band c0, start of band r0, end of band c1, end of band r1), page coordinates; an axis with span
+ *                   (-1, -1) gives 0 for both of its entries.
+ *   table_shape[t]  (n_rows, n_cols) = the band counts of the y / x axis.
+ *   table_box[t]    (min lo_x, min lo_y, max hi1_x, max hi1_y) over the members.
+ *   table_words[t]  the member count.
+ *   table_status[t] 0: fine (an axis without profile words simply has 0 bands);  1: no member on that page (a negative
+ *                   table_root names no table) -- shape (0, 0), box 0;  2: as above (box as stated, but 0 when a coordinate is out
+ *                   of range);  3: table_page[t] lies outside [0, n_pages) or its offsets leave [0, n_nodes] or descend -- shape
+ *                   (0, 0), box 0, words 0.
+ * Rows of cell / cell_box of words that are members of no listed table are NOT touched (the caller pre-fills: -1 / 0); the four
+ * per-table outputs are written for every listed table.  A table listed twice writes the same values twice.
+ * One launch for the batch, one workgroup per listed table; static LDS only (two occupancy bitmaps of max_extent + max_gap bits
+ * with their run-start words and scans: < 7 KB), so a page may hold any number of words.  Integer work on LDS atomic min / max /
+ * add / or: deterministic.  No allocation, no workspace, no synchronisation; n_tables == 0 returns GTE_OK without a launch.
+ * bbox, cell, cell_box and table_box 16-byte aligned. */
+int gte_table_grid_max_extent(void);   /* 8192 pixels per axis */
+int gte_table_grid_max_gap(void);      /* 1024 */
+int gte_table_grid(const int32_t* bbox, const int32_t* node_off, int64_t n_pages, int64_t n_nodes,
+                   const int32_t* table,        /* [n_nodes] root id of the word's table, < 0: none */
+                   const int32_t* role,         /* [n_nodes] category of the word; outside 0..31: in no profile */
+                   const int32_t* table_root, const int32_t* table_page, const int32_t* table_gap /* [T, 2] = (gap_x, gap_y) */,
+                   int64_t n_tables, uint32_t col_roles, uint32_t row_roles,
+                   int32_t* cell /* [n_nodes, 4] */, int32_t* cell_box /* [n_nodes, 4] */,
+                   int32_t* table_shape /* [T, 2] */, int32_t* table_box /* [T, 4] */, int32_t* table_words /* [T] */,
+                   int32_t* table_status /* [T] */, void* stream);
+
 /* ---- area-weighted confusion of node predictions: the sums of the DocBank token metric and of the reference's evaluate_doc
  * (models/evaluate.py:182-202) ----
  * Inputs: gt, pred int32 [n_nodes], all pages concatenated; bbox int32 [n_nodes, 4] (x0, y0, x1, y1), 16-byte aligned;
