@@ -103,6 +103,11 @@ SIGNATURES = {
     "gte_token_pool_max_dim": (c_int, []),
     "gte_token_pool_access_bytes": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "gte_token_pool_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    # all-pairs weighted Levenshtein distance (csrc/lev_matrix.hip)
+    "gte_lev_max_len": (c_int, []),
+    "gte_lev_max_alphabet": (c_int, []),
+    "gte_lev_matrix_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_void_p, c_int64, c_void_p]),
     # class, confidence and softmax row per node (csrc/predict_head.hip)
     "gte_predict_head": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_inv_degree": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -753,6 +753,60 @@ def repr_features(node_tok: torch.Tensor, embeddings: torch.Tensor, centers: tor
     return out
 
 
+def lev_matrix(src_chars: torch.Tensor, src_off: torch.Tensor, dst_chars: torch.Tensor, dst_off: torch.Tensor,
+               ins_cost: torch.Tensor, del_cost: torch.Tensor, sub_cost: torch.Tensor, max_len: Optional[int] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """All-pairs weighted Levenshtein distance as float64 [n_src, n_dst] in one launch of gte_lev_matrix_f64 (the recurrence is
+    stated in include/gte.h): the double loop of src/components/tables/levenshtein.py:50-63.  ``src_chars`` / ``dst_chars`` uint16
+    [total]: the compact character ids of all words, concatenated; ``src_off`` / ``dst_off`` int32 [n + 1]: word p is
+    ``chars[off[p]:off[p+1]]``; ``ins_cost`` / ``del_cost`` float64 [A], ``sub_cost`` float64 [A, A].  Making the ids and the tables
+    is string work and stays on the host (components/tables/levenshtein.py).
+    ``max_len``: the longest word the kernel is to expect (longer ones are cut there); None: the library's limit.
+    ``out``: a float64 [n_src, n_dst] device tensor with unit column stride to write into, of which nothing outside the slice is
+    touched; None allocates one.  That the last offset of either list does not pass the end of its character tensor is checked
+    here (one read-back of two numbers): the kernel trusts that number and clamps everything else against it."""
+    lib = _lib.load()
+    _lib.require_device(src_chars, "lev_matrix")
+    words = (("src", src_chars, src_off), ("dst", dst_chars, dst_off))
+    for name, chars, off in words:
+        _lib.require_device(chars, f"lev_matrix: {name}_chars")
+        _lib.require_device(off, f"lev_matrix: {name}_off")
+        if chars.dtype != torch.uint16 or chars.dim() != 1:
+            raise ValueError(f"lev_matrix: {name}_chars must be a uint16 vector, got {chars.dtype} {tuple(chars.shape)}")
+        if off.dtype != torch.int32 or off.dim() != 1 or off.shape[0] < 1:
+            raise ValueError(f"lev_matrix: {name}_off must be int32 [n + 1], got {off.dtype} {tuple(off.shape)}")
+    costs = (("ins_cost", ins_cost), ("del_cost", del_cost), ("sub_cost", sub_cost))
+    for name, t in costs:
+        _lib.require_device(t, f"lev_matrix: {name}")
+        if t.dtype != torch.float64:
+            raise ValueError(f"lev_matrix: {name} must be float64, got {t.dtype}")
+    n_alpha = ins_cost.shape[0] if ins_cost.dim() == 1 else -1
+    if n_alpha < 1 or tuple(del_cost.shape) != (n_alpha,) or tuple(sub_cost.shape) != (n_alpha, n_alpha):
+        raise ValueError(f"lev_matrix: ins_cost {tuple(ins_cost.shape)}, del_cost {tuple(del_cost.shape)} and sub_cost "
+                         f"{tuple(sub_cost.shape)} do not fit together ([A], [A], [A, A], A >= 1)")
+    max_len = lib.gte_lev_max_len() if max_len is None else int(max_len)
+    src_chars, src_off, dst_chars, dst_off = (t.contiguous() for t in (src_chars, src_off, dst_chars, dst_off))
+    ins_cost, del_cost, sub_cost = (t.contiguous() for _, t in costs)
+    n_src, n_dst = src_off.shape[0] - 1, dst_off.shape[0] - 1
+    if out is None:
+        out = torch.empty((n_src, n_dst), dtype=torch.float64, device=src_chars.device)
+    else:
+        _lib.require_device(out, "lev_matrix: out")
+        if out.dtype != torch.float64 or tuple(out.shape) != (n_src, n_dst) or (n_src > 0 and n_dst > 0 and out.stride(1) != 1):
+            raise ValueError(f"lev_matrix: out must be float64 [{n_src}, {n_dst}] with unit column stride, got {out.dtype} "
+                             f"{tuple(out.shape)} strides {out.stride()}")
+    if n_src > 0 and n_dst > 0:
+        ends = torch.stack((src_off[-1], dst_off[-1])).tolist()
+        for (name, chars, _), end in zip(words, ends):
+            if end > chars.shape[0]:
+                raise ValueError(f"lev_matrix: {name}_off ends at {end}, {name}_chars holds {chars.shape[0]} characters")
+    ldo = out.stride(0) if n_src > 1 else max(n_dst, 1)
+    _lib.check(lib.gte_lev_matrix_f64(_lib.ptr(src_chars), _lib.ptr(src_off), n_src, _lib.ptr(dst_chars), _lib.ptr(dst_off), n_dst,
+                                      max_len, _lib.ptr(ins_cost), _lib.ptr(del_cost), _lib.ptr(sub_cost), n_alpha, _lib.ptr(out),
+                                      ldo, _lib.current_stream()), "gte_lev_matrix_f64")
+    return out
+
+
 def token_pool(tok: torch.Tensor, table: torch.Tensor, mode: str = "mean", row_map: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Pooled table rows per word in one launch of gte_token_pool_f32 (the rule is stated in include/gte.h): the embedding lookup

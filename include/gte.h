@@ -518,6 +518,37 @@ int gte_token_pool_max_dim(void);     /* 4096 */
 int gte_token_pool_access_bytes(const float* table, int dim, const float* out, int64_t ldo);   /* 16 or 4; host arithmetic only */
 int gte_token_pool_f32(const int32_t* tok, int64_t n_words, int width, const float* table, int64_t n_vocab, int dim, int mode,
                        const int64_t* row_map, float* out, int64_t ldo, void* stream);
+/* All-pairs weighted Levenshtein distance (replaces the double loop of LevenshteinSimilitudes.calculate_similarity,
+ * tables/levenshtein.py:50-63, called by Preprocessor.train_repr, tables/preprocessor.py:303-305): n_src * n_dst independent
+ * dynamic programmes in one launch.  Words are concatenated COMPACT character ids (uint16, 0 <= id < n_alpha) with n + 1 int32
+ * offsets: word p is chars[off[p] .. off[p+1]).  ins_cost, del_cost double [n_alpha]; sub_cost double [n_alpha, n_alpha], row-major:
+ * sub_cost[x * n_alpha + y] is the cost of replacing x (of the src word) by y (of the dst word).
+ * out[p * ldo + q] = lev(src[p] -> dst[q]) = d[|a|][|b|] for a = src[p], b = dst[q], all in float64, by exactly this recurrence
+ * (that of the weighted_levenshtein library the reference calls):
+ *   d[0][0] = 0
+ *   d[i][0] = d[i-1][0] + del[a[i-1]]
+ *   d[0][j] = d[0][j-1] + ins[b[j-1]]
+ *   d[i][j] = d[i-1][j-1]                                   if a[i-1] == b[j-1]   (a copy: NO minimum is taken)
+ *           = min(d[i-1][j]   + del[a[i-1]],
+ *                 d[i][j-1]   + ins[b[j-1]],
+ *                 d[i-1][j-1] + sub[a[i-1]][b[j-1]])        otherwise
+ * Every cell is one of three correctly rounded sums or a copy, so the result does not depend on the order the cells are visited
+ * in and equals a host evaluation of the recurrence bit for bit.  The equal-characters rule is NOT "substitution cost 0": with
+ * insert + delete cheaper than the detour, the two differ.
+ * Only out[p * ldo + q] for p < n_src, q < n_dst is written (ldo >= n_dst: a column slice of a wider matrix stays untouched).
+ * One launch, one wave per workgroup, one dst word per lane, the rolling column in LDS; no atomics, no workspace, no allocation.
+ * The kernel clamps every word's start into [0, off[n]], its length to max_len and to what off[n] leaves, and a character id to
+ * n_alpha - 1: given truthful off[n] and table sizes, no offsets or ids can take a read outside the buffers (a clamped word gives
+ * the distance of the clamped word).  A character buffer may be NULL when its list holds only empty words.
+ * Negative sizes (n_src, n_dst, max_len), ldo < n_dst, null or misaligned pointers return GTE_ERR_INVALID_ARGUMENT; max_len >
+ * gte_lev_max_len() or n_alpha outside 1 .. gte_lev_max_alphabet() GTE_ERR_UNSUPPORTED; n_src == 0 or n_dst == 0 is GTE_OK with
+ * nothing launched.  All of these come before any launch, in this order: sizes and ldo, limits, the empty call, pointers. */
+int gte_lev_max_len(void);        /* 64 characters per word */
+int gte_lev_max_alphabet(void);   /* 1024 distinct characters */
+int gte_lev_matrix_f64(const uint16_t* src_chars, const int32_t* src_off, int64_t n_src,
+                       const uint16_t* dst_chars, const int32_t* dst_off, int64_t n_dst, int max_len,
+                       const double* ins_cost, const double* del_cost, const double* sub_cost, int n_alpha,
+                       double* out, int64_t ldo, void* stream);
 /* The per-word head of label-free prediction (model_predict.predict): class, confidence and, on request, the softmax row of every
  * node in ONE pass over logits float [n_nodes, n_classes] (row i at logits + i * ld_logits, ld_logits >= n_classes,
  * 1 <= n_classes <= 16: the step engine's class limit).  Per row, with l_j its entries:
