@@ -108,6 +108,12 @@ SIGNATURES = {
     "gte_lev_max_alphabet": (c_int, []),
     "gte_lev_matrix_f64": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                    c_void_p, c_int64, c_void_p]),
+    # affinity propagation sweeps (csrc/affprop.hip)
+    "gte_affprop_max_n": (c_int, []),
+    "gte_affprop_max_convergence_iter": (c_int, []),
+    "gte_affprop_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "gte_affprop_iterate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_int64, c_void_p, c_void_p]),
     # class, confidence and softmax row per node (csrc/predict_head.hip)
     "gte_predict_head": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_inv_degree": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -1,6 +1,7 @@
 """REPR prototypes and embeddings from representation counts: ``Preprocessor.train_repr`` of the reference
 (src/components/tables/preprocessor.py:282-342).  The all-pairs similarity matrix comes from one HIP launch
-(components/tables/levenshtein.py); affinity propagation and t-SNE are scikit-learn's, on the host, as in the reference.
+(components/tables/levenshtein.py); affinity propagation is scikit-learn's on the host, as in the reference, or -- with
+``affinity='device'`` -- HIP sweeps with the same result (components/tables/affinity.py); t-SNE is scikit-learn's, on the host.
 
 What this does NOT produce is ``i_embedding`` (the [C, P] output rows of the prototypes): the reference trains it with the
 ``tblemb`` package, which it does not ship.  It stays the caller's."""
@@ -26,7 +27,7 @@ def repr_words(rc: Dict[str, int], limit: int = 2000, align: bool = False) -> Li
 
 
 def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, device=None, similarity=None, random_state=None,
-               tsne_kwargs: Optional[dict] = None, align: bool = False) -> dict:
+               tsne_kwargs: Optional[dict] = None, align: bool = False, affinity: str = "host") -> dict:
     """``{'centers', 'labels', 'words', 'embeddings'}`` as the reference pickles them (preprocessor.py:335-340):
     ``words`` numpy str [n], n = min(limit, len(rc)); ``centers`` the indices into ``words`` of the affinity-propagation
     exemplars; ``labels`` int [n], the cluster of every word; ``embeddings`` float [n, n_components], the t-SNE embedding.
@@ -48,7 +49,12 @@ def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, dev
         its neighbour's row.  The default keeps that.  ``align=True`` works on ``idx2repr`` order throughout (``repr_words(rc,
         limit, align=True)``), so row ``repr2idx[t]`` of ``embeddings`` is token ``t``'s and ``centers`` / ``labels`` index the
         same order: a deviation from the reference.
+    ``affinity``: where the clustering runs.  'host' (the default) is scikit-learn's ``AffinityPropagation``; 'device' is
+    ``components/tables/affinity.affinity_propagation`` with the same damping and ``random_state`` -- the sweeps in HIP kernels on
+    ``device``, centres and labels equal to scikit-learn's -- which leaves t-SNE as the one scikit-learn stage.
     scikit-learn is imported here, not at module level: nothing else in the package needs it."""
+    if affinity not in ("host", "device"):
+        raise ValueError(f"train_repr: affinity must be 'host' or 'device', got {affinity!r}")
     words = repr_words(rc, limit, align=align)
     n = len(words)
     if similarity is None:
@@ -57,14 +63,23 @@ def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, dev
         matrix = np.array(similarity, dtype=np.float64)
     if matrix.shape != (n, n):
         raise ValueError(f"train_repr: the similarity matrix is {matrix.shape}, {n} words need ({n}, {n})")
-    try:
-        from sklearn.cluster import AffinityPropagation
-        from sklearn.manifold import TSNE
-    except ImportError as e:
-        raise ImportError("train_repr: scikit-learn is needed for two stages that stay on the host, the affinity propagation "
-                          "(sklearn.cluster.AffinityPropagation) and the t-SNE embedding (sklearn.manifold.TSNE)") from e
-    affprop = AffinityPropagation(affinity="precomputed", damping=0.9, random_state=random_state).fit(matrix)
-    centers, labels = affprop.cluster_centers_indices_, affprop.labels_
+    if affinity == "device":
+        from .affinity import affinity_propagation
+        centers, labels = affinity_propagation(matrix, damping=0.9, random_state=random_state, device=device)
+        try:
+            from sklearn.manifold import TSNE
+        except ImportError as e:
+            raise ImportError("train_repr: scikit-learn is needed for the one stage that stays on the host, the t-SNE embedding "
+                              "(sklearn.manifold.TSNE)") from e
+    else:
+        try:
+            from sklearn.cluster import AffinityPropagation
+            from sklearn.manifold import TSNE
+        except ImportError as e:
+            raise ImportError("train_repr: scikit-learn is needed for two stages that stay on the host, the affinity propagation "
+                              "(sklearn.cluster.AffinityPropagation) and the t-SNE embedding (sklearn.manifold.TSNE)") from e
+        affprop = AffinityPropagation(affinity="precomputed", damping=0.9, random_state=random_state).fit(matrix)
+        centers, labels = affprop.cluster_centers_indices_, affprop.labels_
 
     matrix = np.square(matrix)
     finite = matrix[matrix != np.inf]

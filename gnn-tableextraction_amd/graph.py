@@ -807,6 +807,41 @@ def lev_matrix(src_chars: torch.Tensor, src_off: torch.Tensor, dst_chars: torch.
     return out
 
 
+def affprop_workspace(n: int, convergence_iter: int, device) -> torch.Tensor:
+    """The zeroed uint8 workspace (column sums and exemplar ring) that ``affprop_iterate`` wants for an n x n problem."""
+    need = _lib.load().gte_affprop_workspace_bytes(int(n), int(convergence_iter))
+    return torch.zeros(max(int(need), 8), dtype=torch.uint8, device=device)
+
+
+def affprop_iterate(S: torch.Tensor, A: torch.Tensor, R: torch.Tensor, damping: float, convergence_iter: int, max_iter: int,
+                    n_sweeps: int, exemplar: torch.Tensor, workspace: torch.Tensor, state: torch.Tensor) -> None:
+    """Enqueues ``n_sweeps`` sweeps of affinity propagation (gte_affprop_iterate; the sweep is stated in include/gte.h) on the
+    current stream and returns without synchronising.  ``S`` float64 [n, n] with the preference on its diagonal and the noise
+    added (components/tables/affinity.py: prepare); ``A``, ``R`` float64 [n, n], ``exemplar`` uint8 [n], ``workspace`` uint8
+    (``affprop_workspace``) and ``state`` int32 [4] = (n_iter_done, stopped, converged, K) are updated in place and carry the
+    iteration from call to call: all contiguous device tensors, zeroed by the caller before the first call.  Sweeps enqueued
+    after the device has stopped change nothing.  ``1 - damping`` is computed here, in float64."""
+    lib = _lib.load()
+    _lib.require_device(S, "affprop_iterate")
+    n = S.shape[0] if S.dim() == 2 else -1
+    for name, t in (("S", S), ("A", A), ("R", R)):
+        _lib.require_device(t, f"affprop_iterate: {name}")
+        if t.dtype != torch.float64 or tuple(t.shape) != (n, n) or not t.is_contiguous():
+            raise ValueError(f"affprop_iterate: {name} must be a contiguous float64 [{n}, {n}] matrix, got {t.dtype} {tuple(t.shape)} "
+                             f"strides {t.stride()}")
+    for name, t, dtype, size in (("exemplar", exemplar, torch.uint8, n), ("state", state, torch.int32, 4)):
+        _lib.require_device(t, f"affprop_iterate: {name}")
+        if t.dtype != dtype or tuple(t.shape) != (size,) or not t.is_contiguous():
+            raise ValueError(f"affprop_iterate: {name} must be a contiguous {dtype} [{size}] vector, got {t.dtype} {tuple(t.shape)}")
+    _lib.require_device(workspace, "affprop_iterate: workspace")
+    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+        raise ValueError(f"affprop_iterate: workspace must be a contiguous uint8 vector, got {workspace.dtype} {tuple(workspace.shape)}")
+    damping = float(damping)
+    _lib.check(lib.gte_affprop_iterate(_lib.ptr(S), _lib.ptr(A), _lib.ptr(R), n, damping, 1.0 - damping, int(convergence_iter),
+                                       int(max_iter), int(n_sweeps), _lib.ptr(exemplar), _lib.ptr(workspace), workspace.numel(),
+                                       _lib.ptr(state), _lib.current_stream()), "gte_affprop_iterate")
+
+
 def token_pool(tok: torch.Tensor, table: torch.Tensor, mode: str = "mean", row_map: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Pooled table rows per word in one launch of gte_token_pool_f32 (the rule is stated in include/gte.h): the embedding lookup

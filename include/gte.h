@@ -549,6 +549,45 @@ int gte_lev_matrix_f64(const uint16_t* src_chars, const int32_t* src_off, int64_
                        const uint16_t* dst_chars, const int32_t* dst_off, int64_t n_dst, int max_len,
                        const double* ins_cost, const double* del_cost, const double* sub_cost, int n_alpha,
                        double* out, int64_t ldo, void* stream);
+/* Affinity propagation sweeps (the loop of sklearn/cluster/_affinity_propagation.py: _affinity_propagation, which
+ * Preprocessor.train_repr runs through src/utils/matrixes.py: affinity) on row-major float64 S, A, R [n, n].  S carries the
+ * preference on its diagonal and the degeneracy noise: both are host work (components/tables/affinity.py: prepare).
+ * d = damping, omd = one_minus_damping: the host computes 1 - damping in float64 and passes it in.  Every product, sum and
+ * difference below is one correctly rounded float64 operation; nothing is contracted into a fused multiply-add.  Sweep `it`:
+ *   row pass, row i:   t[k] = A[i,k] + S[i,k];  I = the FIRST index of the maximum of t (ties go to the lowest k, as np.argmax);
+ *                      Y = t[I];  Y2 = max over k != I of t[k] (-inf for n == 1);
+ *                      new[k] = S[i,k] - Y for k != I, new[I] = S[i,I] - Y2;   R[i,k] = (R[i,k] * d) + (new[k] * omd)
+ *   Rp:                Rp[i,k] = max(R[i,k], 0) for k != i, Rp[i,i] = R[i,i]
+ *   column sums:       cs[k] = (((Rp[0,k] + Rp[1,k]) + Rp[2,k]) + ...) + Rp[n-1,k], STRICTLY in row order: what np.sum(axis=0) does
+ *                      on a C-contiguous matrix.  The order is part of the contract; a tree or a split over row blocks is a
+ *                      different function.
+ *   A update:          u = Rp[i,k] - cs[k];  off the diagonal u = max(u, 0), the diagonal keeps u;   A[i,k] = (A[i,k] * d) - (u * omd)
+ *   exemplars, stop:   E[i] = (A[i,i] + R[i,i]) > 0 from the new A and R, written to exemplar[i] and to slot it % convergence_iter of a
+ *                      ring of the last convergence_iter vectors E;  K = sum(E).  If it >= convergence_iter, every node's ring
+ *                      is all ones or all zeros, and K > 0: stop after this sweep with converged = 1, n_iter = it + 1.  If
+ *                      max_iter sweeps pass without that: stop with converged = 0, n_iter = max_iter (scikit-learn's
+ *                      never_converged).
+ * Equality with the host evaluation is equality by value (==); the sign of a zero is not pinned.
+ * state int32 [4] in device memory = {n_iter_done, stopped, converged, K of the last sweep}.  The call ENQUEUES n_sweeps sweeps on
+ * `stream` and continues from `state`; it neither allocates nor synchronises.  The stop is decided on the device: every kernel of a
+ * sweep reads the state first and returns without touching A, R, exemplar or the ring when `stopped` is set or n_iter_done ==
+ * max_iter, so the matrices are frozen after the stopping sweep however many sweeps were enqueued behind it, and how the caller
+ * cuts max_iter into calls changes no output bit.  Before the first call the caller zeroes A, R, the workspace (column sums,
+ * ring and flags, gte_affprop_workspace_bytes(n, convergence_iter) bytes) and state.
+ * One sweep is four launches: the row pass (a workgroup per row, any n); the column sums (a lane per column adds in row order
+ * while a workgroup stages tiles of rows through LDS to keep loads in flight; Rp is formed on the fly, never stored in memory);
+ * the elementwise A update, whose diagonal lanes also write E, the ring slot and a "ring is uniform" flag per node; and one
+ * workgroup that counts K and the uniform nodes (integers: deterministic) and writes the state.  64-bit indexing throughout.
+ * Checks, all before any launch, in this order: n < 0, convergence_iter < 1, max_iter < 1, n_sweeps < 0, damping or
+ * one_minus_damping outside [0, 1] GTE_ERR_INVALID_ARGUMENT; n > gte_affprop_max_n() or convergence_iter >
+ * gte_affprop_max_convergence_iter() GTE_ERR_UNSUPPORTED; n == 0 or n_sweeps == 0 GTE_OK with nothing launched; null or misaligned
+ * pointers GTE_ERR_INVALID_ARGUMENT; a workspace below the size query GTE_ERR_WORKSPACE_TOO_SMALL. */
+int gte_affprop_max_n(void);                  /* 8192 */
+int gte_affprop_max_convergence_iter(void);   /* 256 */
+int64_t gte_affprop_workspace_bytes(int64_t n, int convergence_iter);
+int gte_affprop_iterate(const double* S, double* A, double* R, int64_t n, double damping, double one_minus_damping,
+                        int convergence_iter, int max_iter, int n_sweeps, uint8_t* exemplar /* [n] */, void* workspace,
+                        int64_t workspace_bytes, int32_t* state /* [4] */, void* stream);
 /* The per-word head of label-free prediction (model_predict.predict): class, confidence and, on request, the softmax row of every
  * node in ONE pass over logits float [n_nodes, n_classes] (row i at logits + i * ld_logits, ld_logits >= n_classes,
  * 1 <= n_classes <= 16: the step engine's class limit).  Per row, with l_j its entries:
