@@ -297,7 +297,7 @@ extern "C" int gte_spmm_dropout_p3(const int32_t* indptr, const int32_t* indices
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_p3: bad sizes or site");
     GTE_DROP_TRY(check_rows(n_rows, "spmm_dropout_p3"));
     if (n_rows == 0) return GTE_OK;
-    if (!indptr || !indices || !step_counter || !selfp3 || !aggp3 || (!x == !xp))
+    if (!indptr || !step_counter || !selfp3 || !aggp3 || (!x == !xp))          // indices may be NULL for an edgeless graph
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_p3: null pointer (exactly one of x / xp is the input)");
     if (x && ldx < n_feat) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_p3: ldx < n_feat");
     if (xp && (ldpx < p3::row_bytes(n_feat) || ldpx % 16 != 0 || (x_rows && n_res_rows <= 0)))
@@ -327,7 +327,8 @@ extern "C" int gte_spmm_dropout_bwd(const int32_t* rindptr, const int32_t* rindi
         return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_bwd: bad sizes or site");
     GTE_DROP_TRY(check_rows(n_rows, "spmm_dropout_bwd"));
     if (n_rows == 0) return GTE_OK;
-    if (!rindptr || !rindices || !w_out || !g || !step_counter || !dx) return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_bwd: null pointer");
+    if (!rindptr || !g || !step_counter || !dx)                                // rindices, w_out may be NULL for an edgeless graph
+        return gte::fail(GTE_ERR_INVALID_ARGUMENT, "spmm_dropout_bwd: null pointer");
     const int64_t n4 = gte::round_up(n_feat, 4);
     if (agg_col % 4 != 0 || ldg % 4 != 0 || agg_col < n4 || ldg < agg_col + n4 || lddx % 4 != 0 || lddx < n4 ||
         reinterpret_cast<uintptr_t>(g) % 16 != 0 || reinterpret_cast<uintptr_t>(dx) % 16 != 0)

@@ -264,19 +264,24 @@ def spmm_csr_p3(indptr, indices, weight, x: torch.Tensor, n_rows: int, mean: boo
 
 
 # ---- dropout (csrc/dropout.hip; keep bits of csrc/dropout.h) -------------------------------------------------------------
-def dropout_mask(p: float, seed: int, rank: int, step: int, site: int, n_rows: int, n_cols: int, device=None) -> torch.Tensor:
+def dropout_mask(p: float, seed: int, rank: int, step: int, site: int, n_rows: int, n_cols: int, device=None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Keep mask (uint8 [n_rows, n_cols], 1 = kept) of one mask site at one step -- on ``device`` through gte_dropout_mask, or
     with ``device`` None on the host through gte_dropout_mask_host (no GPU needed).  site 0 = the model's input dropout, i + 1 =
-    hidden layer i's mask over cat(h, ah * norm) (2 fin columns); step = completed optimiser steps at the step that drew it."""
+    hidden layer i's mask over cat(h, ah * norm) (2 fin columns); step = completed optimiser steps at the step that drew it.
+    ``out``: a uint8 [n_rows, n_cols] view (any row stride ldm >= n_cols, on the device or, for the host form, in host memory) to
+    write instead of a new tensor."""
     lib = _lib.load()
     seed = int(seed) & ((1 << 64) - 1)
-    if device is None:
-        m = torch.zeros(n_rows, n_cols, dtype=torch.uint8)
-        check(lib.gte_dropout_mask_host(float(p), seed, int(rank), int(step), int(site), n_rows, n_cols, m.data_ptr(), n_cols),
+    if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (n_rows, n_cols) or (n_cols > 1 and out.stride(1) != 1)):
+        raise ValueError("dropout_mask: out must be a uint8 [n_rows, n_cols] view with contiguous rows")
+    if device is None and (out is None or not out.is_cuda):
+        m = torch.zeros(n_rows, n_cols, dtype=torch.uint8) if out is None else out
+        check(lib.gte_dropout_mask_host(float(p), seed, int(rank), int(step), int(site), n_rows, n_cols, m.data_ptr(), max(_ld(m), n_cols)),
               "gte_dropout_mask_host")
         return m
-    m = torch.zeros(n_rows, n_cols, dtype=torch.uint8, device=device)
-    check(lib.gte_dropout_mask(float(p), seed, int(rank), int(step), int(site), n_rows, n_cols, ptr(m), n_cols, current_stream()),
+    m = torch.zeros(n_rows, n_cols, dtype=torch.uint8, device=device) if out is None else out
+    check(lib.gte_dropout_mask(float(p), seed, int(rank), int(step), int(site), n_rows, n_cols, ptr(m), max(_ld(m), n_cols), current_stream()),
           "gte_dropout_mask")
     return m
 

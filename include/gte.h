@@ -884,7 +884,10 @@ int gte_dropout_get_wide(void);
  * as two P3 images [n_rows][n_feat] (columns up to the next multiple of 16 written as zeros), the mask of the agg half at columns
  * n_feat + c.  The aggregation is gte_spmm_csr_p3's (same weights, norm, CSR summation order).  Input: fp32 rows x (ldx) OR a P3
  * image xp (ldpx bytes per row) whose row u is resident row x_rows[u] (x_rows NULL: row u) -- the resident feature images of the
- * train loop, decoded exactly.  step = *step_counter (device memory: captured replays draw fresh masks).  site >= 1. */
+ * train loop, decoded exactly.  step = *step_counter (device memory: captured replays draw fresh masks).  site >= 1.
+ * EDGELESS GRAPH (indptr all zero, e.g. a batch of one-word pages): indices may be NULL, as for gte_spmm_csr_p3 -- the kernel reads
+ * indices / eweight only inside a row's edge range; selfp3 is the masked input and aggp3 all zeros.  With any edge, indices must
+ * point at them (a NULL eweight is unit weights at any size). */
 int gte_spmm_dropout_p3(const int32_t* indptr, const int32_t* indices, const float* eweight, const float* x, int64_t ldx,
                         const void* xp, int64_t ldpx, const int32_t* x_rows, int64_t n_res_rows, int in_dropout, float p, uint64_t seed,
                         int rank, const int64_t* step_counter, int site, void* selfp3, int64_t ldp_self, void* aggp3, int64_t ldp_agg,
@@ -893,7 +896,9 @@ int gte_spmm_dropout_p3(const int32_t* indptr, const int32_t* indices, const flo
  * (columns 0 .. n_feat the self half, agg_col .. agg_col + n_feat the aggregate half),
  *     dx[v] = D_site(G[v, self]) + sum_{v -> u} w_out D_site(G[u, agg])   (out-edge CSR, w_out = w / in_degree(dst); row u's mask)
  * dx [n_rows][lddx] fp32, columns n_feat .. round_up(n_feat, 4) written as zeros.  g, dx 16-byte aligned; agg_col, ldg, lddx
- * multiples of 4; agg_col >= round_up(n_feat, 4), ldg >= agg_col + round_up(n_feat, 4). */
+ * multiples of 4; agg_col >= round_up(n_feat, 4), ldg >= agg_col + round_up(n_feat, 4).
+ * EDGELESS GRAPH (rindptr all zero): rindices and w_out may be NULL -- neither is read outside a row's edge range -- and
+ * dx = D_site(G[:, self]).  With any edge both must point at one entry per edge (there is no unit-weight default here). */
 int gte_spmm_dropout_bwd(const int32_t* rindptr, const int32_t* rindices, const float* w_out, const float* g, int64_t ldg,
                          int64_t agg_col, float p, uint64_t seed, int rank, const int64_t* step_counter, int site, float* dx,
                          int64_t lddx, int64_t n_rows, int64_t n_feat, void* stream);

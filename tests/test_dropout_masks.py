@@ -7,34 +7,7 @@ import torch
 
 import gnn_tableextraction_amd as gte
 from gnn_tableextraction_amd import ops
-
-M32 = 0xFFFFFFFF
-
-
-def philox4x32_10(c0, c1, c2, c3, k0, k1):
-    """Philox4x32 with 10 rounds (Salmon et al. 2011, the Random123 constants) on uint32 arrays."""
-    c = [np.asarray(v, dtype=np.uint64) & M32 for v in (c0, c1, c2, c3)]
-    c = list(np.broadcast_arrays(*c))
-    k0, k1 = np.uint64(k0 & M32), np.uint64(k1 & M32)
-    for _ in range(10):
-        p0 = np.uint64(0xD2511F53) * c[0]
-        p1 = np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & np.uint64(M32), (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & np.uint64(M32)]
-        k0 = (k0 + np.uint64(0x9E3779B9)) & np.uint64(M32)
-        k1 = (k1 + np.uint64(0xBB67AE85)) & np.uint64(M32)
-    return [v.astype(np.uint32) for v in c]
-
-
-def numpy_mask(p, seed, rank, step, site, n_rows, n_cols):
-    """keep(seed, rank, step, site, row, col) of include/gte.h: counter {col / 4, row, step, site}, key {seed_lo, seed_hi ^ rank
-    0x9E3779B9}, word col % 4 kept iff >= round(p 2^32)."""
-    thr = min(int(float(np.float32(p)) * 4294967296.0 + 0.5), M32)
-    k0, k1 = seed & M32, ((seed >> 32) & M32) ^ ((rank * 0x9E3779B9) & M32)
-    rows = np.arange(n_rows, dtype=np.uint64)[:, None]
-    cols = np.arange(n_cols, dtype=np.uint64)[None, :]
-    words = philox4x32_10(cols >> np.uint64(2), rows, step, site, k0, k1)
-    u = np.choose((cols & np.uint64(3)).astype(np.int64) + 0 * rows.astype(np.int64), words)
-    return (u >= thr).astype(np.uint8)
+from tests.dropout_ref import keep as numpy_mask, philox4x32_10
 
 
 def host_mask(p, seed, rank, step, site, n_rows, n_cols):
