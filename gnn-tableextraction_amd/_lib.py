@@ -114,6 +114,14 @@ SIGNATURES = {
     "gte_affprop_workspace_bytes": (c_int64, [c_int64, c_int]),
     "gte_affprop_iterate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_int64, c_void_p, c_void_p]),
+    # exact t-SNE on a precomputed distance matrix (csrc/tsne.hip)
+    "gte_tsne_max_n": (c_int, []),
+    "gte_tsne_max_components": (c_int, []),
+    "gte_tsne_workspace_bytes": (c_int64, [c_int64]),
+    "gte_tsne_cond_p": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "gte_tsne_joint_p": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gte_tsne_iterate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_double, c_double, c_int, c_double,
+                                 c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     # class, confidence and softmax row per node (csrc/predict_head.hip)
     "gte_predict_head": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_inv_degree": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

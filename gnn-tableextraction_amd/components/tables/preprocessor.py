@@ -1,7 +1,8 @@
 """REPR prototypes and embeddings from representation counts: ``Preprocessor.train_repr`` of the reference
 (src/components/tables/preprocessor.py:282-342).  The all-pairs similarity matrix comes from one HIP launch
 (components/tables/levenshtein.py); affinity propagation is scikit-learn's on the host, as in the reference, or -- with
-``affinity='device'`` -- HIP sweeps with the same result (components/tables/affinity.py); t-SNE is scikit-learn's, on the host.
+``affinity='device'`` -- HIP sweeps with the same result (components/tables/affinity.py); t-SNE is scikit-learn's on the host or
+-- with ``tsne='device'`` -- the exact method in HIP kernels (components/tables/tsne.py).
 
 What this does NOT produce is ``i_embedding`` (the [C, P] output rows of the prototypes): the reference trains it with the
 ``tblemb`` package, which it does not ship.  It stays the caller's."""
@@ -27,7 +28,7 @@ def repr_words(rc: Dict[str, int], limit: int = 2000, align: bool = False) -> Li
 
 
 def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, device=None, similarity=None, random_state=None,
-               tsne_kwargs: Optional[dict] = None, align: bool = False, affinity: str = "host") -> dict:
+               tsne_kwargs: Optional[dict] = None, align: bool = False, affinity: str = "host", tsne: str = "host") -> dict:
     """``{'centers', 'labels', 'words', 'embeddings'}`` as the reference pickles them (preprocessor.py:335-340):
     ``words`` numpy str [n], n = min(limit, len(rc)); ``centers`` the indices into ``words`` of the affinity-propagation
     exemplars; ``labels`` int [n], the cluster of every word; ``embeddings`` float [n, n_components], the t-SNE embedding.
@@ -51,10 +52,19 @@ def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, dev
         same order: a deviation from the reference.
     ``affinity``: where the clustering runs.  'host' (the default) is scikit-learn's ``AffinityPropagation``; 'device' is
     ``components/tables/affinity.affinity_propagation`` with the same damping and ``random_state`` -- the sweeps in HIP kernels on
-    ``device``, centres and labels equal to scikit-learn's -- which leaves t-SNE as the one scikit-learn stage.
+    ``device``, centres and labels equal to scikit-learn's.
+    ``tsne``: where the embedding is computed.  'host' (the default) is scikit-learn's ``TSNE`` as above (Barnes-Hut:
+    ``n_components`` <= 3).  'device' is ``components/tables/tsne.tsne`` on the same cleaned squared matrix with ``random_state`` and
+    ``tsne_kwargs`` passed on: scikit-learn's EXACT method (conditional and joint probabilities and the 1000 iterations in HIP
+    kernels on ``device``, float64), which takes the reference's own ``n_components=4``.  The descent is chaotic, so its
+    coordinates are not scikit-learn's; the quality reached (the KL divergence) is.  ``tsne_kwargs`` there: ``perplexity``,
+    ``early_exaggeration``, ``learning_rate``, ``max_iter``, ``n_iter_without_progress``, ``min_grad_norm``, ``init``.
+    With ``affinity='device', tsne='device'`` scikit-learn is not imported at all.
     scikit-learn is imported here, not at module level: nothing else in the package needs it."""
     if affinity not in ("host", "device"):
         raise ValueError(f"train_repr: affinity must be 'host' or 'device', got {affinity!r}")
+    if tsne not in ("host", "device"):
+        raise ValueError(f"train_repr: tsne must be 'host' or 'device', got {tsne!r}")
     words = repr_words(rc, limit, align=align)
     n = len(words)
     if similarity is None:
@@ -66,18 +76,21 @@ def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, dev
     if affinity == "device":
         from .affinity import affinity_propagation
         centers, labels = affinity_propagation(matrix, damping=0.9, random_state=random_state, device=device)
-        try:
-            from sklearn.manifold import TSNE
-        except ImportError as e:
-            raise ImportError("train_repr: scikit-learn is needed for the one stage that stays on the host, the t-SNE embedding "
-                              "(sklearn.manifold.TSNE)") from e
+        if tsne == "host":
+            try:
+                from sklearn.manifold import TSNE
+            except ImportError as e:
+                raise ImportError("train_repr: scikit-learn is needed for the one stage that stays on the host, the t-SNE embedding "
+                                  "(sklearn.manifold.TSNE); tsne='device' needs none") from e
     else:
         try:
             from sklearn.cluster import AffinityPropagation
-            from sklearn.manifold import TSNE
+            if tsne == "host":
+                from sklearn.manifold import TSNE
         except ImportError as e:
-            raise ImportError("train_repr: scikit-learn is needed for two stages that stay on the host, the affinity propagation "
-                              "(sklearn.cluster.AffinityPropagation) and the t-SNE embedding (sklearn.manifold.TSNE)") from e
+            raise ImportError("train_repr: scikit-learn is needed for the stages that stay on the host, the affinity propagation "
+                              "(sklearn.cluster.AffinityPropagation) and, with tsne='host', the t-SNE embedding "
+                              "(sklearn.manifold.TSNE)") from e
         affprop = AffinityPropagation(affinity="precomputed", damping=0.9, random_state=random_state).fit(matrix)
         centers, labels = affprop.cluster_centers_indices_, affprop.labels_
 
@@ -85,8 +98,12 @@ def train_repr(rc: Dict[str, int], n_components: int = 3, limit: int = 2000, dev
     finite = matrix[matrix != np.inf]
     mean_, max_ = np.nanmean(finite), np.nanmax(finite)                    # (preprocessor.py:317-320)
     matrix = np.nan_to_num(matrix, nan=mean_, posinf=max_, neginf=max_)
-    tsne = TSNE(n_components=n_components, metric="precomputed", init="random", random_state=random_state, **(tsne_kwargs or {}))
-    embeddings = tsne.fit_transform(matrix)
+    if tsne == "device":
+        from .tsne import tsne as device_tsne
+        embeddings = device_tsne(matrix, n_components, random_state=random_state, device=device, **(tsne_kwargs or {}))
+    else:
+        embeddings = TSNE(n_components=n_components, metric="precomputed", init="random", random_state=random_state,
+                          **(tsne_kwargs or {})).fit_transform(matrix)
     return {"centers": centers, "labels": labels, "words": np.asarray(words), "embeddings": embeddings}
 
 

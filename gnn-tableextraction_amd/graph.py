@@ -842,6 +842,67 @@ def affprop_iterate(S: torch.Tensor, A: torch.Tensor, R: torch.Tensor, damping: 
                                        _lib.ptr(state), _lib.current_stream()), "gte_affprop_iterate")
 
 
+def _tsne_tensor(t: torch.Tensor, what: str, dtype, shape) -> None:
+    _lib.require_device(t, what)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {dtype} {list(shape)} tensor, got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+
+
+def tsne_workspace(n: int, device) -> torch.Tensor:
+    """The uint8 workspace (partial sums) that ``tsne_joint_p`` and ``tsne_iterate`` want for n samples."""
+    need = _lib.load().gte_tsne_workspace_bytes(int(n))
+    return torch.zeros(max(int(need), 8), dtype=torch.uint8, device=device)
+
+
+def tsne_cond_p(sq_dist: torch.Tensor, perplexity: float):
+    """The conditional probabilities of t-SNE's perplexity search in one launch (gte_tsne_cond_p; the search is stated in
+    include/gte.h).  ``sq_dist`` float32 [n, n], squared distances.  Returns ``(C float64 [n, n], beta float64 [n])``."""
+    n = sq_dist.shape[0] if sq_dist.dim() == 2 else -1
+    _tsne_tensor(sq_dist, "tsne_cond_p: sq_dist", torch.float32, (n, n))
+    C = torch.empty((n, n), dtype=torch.float64, device=sq_dist.device)
+    beta = torch.empty(n, dtype=torch.float64, device=sq_dist.device)
+    _lib.check(_lib.load().gte_tsne_cond_p(_lib.ptr(sq_dist), n, float(perplexity), _lib.ptr(C), _lib.ptr(beta), _lib.current_stream()),
+               "gte_tsne_cond_p")
+    return C, beta
+
+
+def tsne_joint_p(cond_p: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The symmetric joint probabilities P float64 [n, n] of ``cond_p`` float64 [n, n] (gte_tsne_joint_p): zero diagonal, every
+    other entry at least eps.  ``workspace``: ``tsne_workspace(n, device)``; None allocates one."""
+    n = cond_p.shape[0] if cond_p.dim() == 2 else -1
+    _tsne_tensor(cond_p, "tsne_joint_p: cond_p", torch.float64, (n, n))
+    if workspace is None:
+        workspace = tsne_workspace(n, cond_p.device)
+    _tsne_tensor(workspace, "tsne_joint_p: workspace", torch.uint8, (workspace.numel(),))
+    P = torch.empty((n, n), dtype=torch.float64, device=cond_p.device)
+    _lib.check(_lib.load().gte_tsne_joint_p(_lib.ptr(cond_p), n, _lib.ptr(P), _lib.ptr(workspace), workspace.numel(),
+                                            _lib.current_stream()), "gte_tsne_joint_p")
+    return P
+
+
+def tsne_iterate(P: torch.Tensor, Y: torch.Tensor, update: torch.Tensor, gains: torch.Tensor, lr: float, momentum: float,
+                 exaggeration: float, n_iter_without_progress: int, min_grad_norm: float, max_iter: int, n_iters: int,
+                 workspace: torch.Tensor, state: torch.Tensor) -> None:
+    """Enqueues ``n_iters`` iterations of one phase of exact t-SNE (gte_tsne_iterate; the iteration, the stop rule and the state
+    block are stated in include/gte.h) on the current stream and returns without synchronising.  ``P`` float64 [n, n]
+    (``tsne_joint_p``); ``Y`` float64 [2, n, d], the two embedding buffers; ``update``, ``gains`` float64 [n, d]; ``workspace``
+    uint8 (``tsne_workspace``); ``state`` float64 [8] = (next iteration, stopped, reason, best_iter, current buffer, error,
+    best_error, grad_norm): all contiguous device tensors, updated in place, set up by the caller at the start of a phase
+    (components/tables/tsne.py: run).  Iterations enqueued after the device has stopped change nothing.  The numbers are passed
+    on as they are: only the tensors are checked here."""
+    n, d = (P.shape[0], Y.shape[2]) if P.dim() == 2 and Y.dim() == 3 else (-1, -1)
+    _tsne_tensor(P, "tsne_iterate: P", torch.float64, (n, n))
+    _tsne_tensor(Y, "tsne_iterate: Y", torch.float64, (2, n, d))
+    _tsne_tensor(update, "tsne_iterate: update", torch.float64, (n, d))
+    _tsne_tensor(gains, "tsne_iterate: gains", torch.float64, (n, d))
+    _tsne_tensor(state, "tsne_iterate: state", torch.float64, (8,))
+    _tsne_tensor(workspace, "tsne_iterate: workspace", torch.uint8, (workspace.numel(),))
+    _lib.check(_lib.load().gte_tsne_iterate(_lib.ptr(P), _lib.ptr(Y), _lib.ptr(update), _lib.ptr(gains), n, d, float(lr), float(momentum),
+                                            float(exaggeration), int(n_iter_without_progress), float(min_grad_norm), int(max_iter),
+                                            int(n_iters), _lib.ptr(workspace), workspace.numel(), _lib.ptr(state),
+                                            _lib.current_stream()), "gte_tsne_iterate")
+
+
 def token_pool(tok: torch.Tensor, table: torch.Tensor, mode: str = "mean", row_map: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Pooled table rows per word in one launch of gte_token_pool_f32 (the rule is stated in include/gte.h): the embedding lookup

@@ -588,6 +588,67 @@ int64_t gte_affprop_workspace_bytes(int64_t n, int convergence_iter);
 int gte_affprop_iterate(const double* S, double* A, double* R, int64_t n, double damping, double one_minus_damping,
                         int convergence_iter, int max_iter, int n_sweeps, uint8_t* exemplar /* [n] */, void* workspace,
                         int64_t workspace_bytes, int32_t* state /* [4] */, void* stream);
+/* Exact t-SNE on a precomputed distance matrix (csrc/tsne.hip): the numerical stages of scikit-learn 1.7.2's TSNE(method='exact',
+ * metric='precomputed') -- sklearn/manifold/_utils.pyx: _binary_search_perplexity, _t_sne.py: _joint_probabilities, _kl_divergence,
+ * _gradient_descent, _tsne -- which Preprocessor.train_repr runs on the host.  Checks, the squaring of the distances, the float32
+ * cast and the initial embedding are host work (components/tables/tsne.py: prepare).  All matrices row-major; eps =
+ * np.finfo(np.double).eps = 2^-52.  The order of every sum is free but fixed (csrc/tsne.hip states it): two runs give the same bits,
+ * no floating-point atomics.  Every product, sum and quotient is one rounded float64 operation, nothing is contracted.
+ *
+ * gte_tsne_cond_p -- conditional probabilities.  sq_dist float32 [n, n] (scikit-learn casts the squared distances to float32 ahead
+ * of the search), perplexity float32.  Row i: beta = 1, beta_min = -inf, beta_max = +inf; at most 100 steps of
+ *     p_j = exp(-(double)d_ij * beta) for j != i, p_i = 0;   s = sum_j p_j, s = (double)1e-8f if the sum is 0;   p_j = p_j / s;
+ *     H = log(s) + beta * sum_j (double)d_ij * p_j;   diff = H - log((double)perplexity);
+ *     |diff| <= (double)1e-5f: leave the loop (beta unchanged);
+ *     diff > 0:  beta_min = beta;  beta = beta_max == +inf ? beta * 2 : (beta + beta_max) / 2
+ *     else:      beta_max = beta;  beta = beta_min == -inf ? beta / 2 : (beta + beta_min) / 2
+ * cond_p[i, :] = the p of the last step that ran, beta[i] = beta as the loop leaves it (after 100 steps without a hit: the value the
+ * 101st step would have used, as the .pyx leaves its variable).
+ *
+ * gte_tsne_joint_p -- P = (C + C^T) / max(sum_ij (C_ij + C_ji), eps); off the diagonal P_ij = max(P_ij, eps); P_ii = 0.  P is the
+ * full symmetric float64 [n, n] (scikit-learn's condensed vector is an implementation detail).
+ *
+ * gte_tsne_iterate -- ENQUEUES n_iters iterations of _gradient_descent on _kl_divergence and continues from `state`; it neither
+ * allocates nor synchronises.  d = n_components, alpha = max(d - 1, 1), e = exaggeration.  Iteration `it`, from the current
+ * embedding y (Y holds TWO [n, d] buffers; state names the current one):
+ *     dist_ij = ((y_i0 - y_j0)^2 + (y_i1 - y_j1)^2) + ...  in component order;   num_ij = (1 + dist_ij / alpha)^(-(alpha + 1) / 2), i != j
+ *     Z = sum_{i != j} num_ij;   Q_ij = max(num_ij / Z, eps)
+ *     grad_ic = (2 (alpha + 1) / alpha) * sum_j (e * P_ij - Q_ij) * num_ij * (y_ic - y_jc)
+ *     KL = sum_{i != j} e * P_ij * log(max(e * P_ij, eps) / Q_ij)         only when (it + 1) % 50 == 0 or it == max_iter - 1
+ *   update, per component:
+ *     gains = (update * grad < 0) ? gains + 0.2 : gains * 0.8;   gains = max(gains, 0.01);   g = grad * gains;
+ *     update = (momentum * update) - (learning_rate * g);   y_new = y + update   (written to the OTHER buffer, which becomes current)
+ *   check, when (it + 1) % 50 == 0, with error = KL and grad_norm = ||g||_2 over all n * d components:
+ *     error < best_error: best_error = error, best_iter = it;   else if it - best_iter > n_iter_without_progress: stop (reason 1);
+ *     then, unless stopped: grad_norm <= min_grad_norm: stop (reason 2).
+ * The power is an integer or a half-integer: it is evaluated with products, one sqrt and one division (a few ulp), never pow.
+ * state float64 [8] in device memory, integers held exactly: {it = the next iteration, stopped, reason, best_iter, current buffer
+ * (0 / 1), error = the last KL computed, best_error, grad_norm of the last check}.  Every kernel of an iteration reads it first and
+ * returns without a write when `stopped` is set or it >= max_iter, so iterations enqueued behind the stop change nothing and how
+ * the caller cuts a phase into calls changes no bit.  One call is one PHASE of scikit-learn's _tsne, which the caller sets up as
+ * two calls of _gradient_descent do: update = 0, gains = 1, state = {first iteration, 0, 0, first iteration, current buffer,
+ * DBL_MAX, DBL_MAX, 0}.  Phase 1: iterations 0 .. 249, momentum 0.5, e = early_exaggeration, n_iter_without_progress = 250;
+ * phase 2: from the iteration after phase 1's last one to max_iter, momentum 0.8, e = 1.  n_iter = it - 1 = the last iteration run.
+ * Deliberate deviations from scikit-learn: (1) y, update and gains are float64 throughout (there the float32 random init makes the
+ * parameters float32 while, under numpy 2, the np.float64 learning rate makes `update` float64); (2) e * P is formed on the fly
+ * (there P is scaled in place and scaled back); (3) the results are deterministic.
+ * One iteration is three launches: partial sums of Z per block of rows; the gradient pass (a workgroup owns a block of rows, adds
+ * the Z partials in a fixed order, walks the columns in tiles, reduces per row and updates its own rows; on check iterations it
+ * leaves partial sums of KL and ||g||^2); one workgroup that finishes those sums, applies the stop rule and advances the state.
+ * The workspace starts with the ceil(n / 16) float64 partial sums of Z, followed by Z itself as the last iteration used it.
+ * Checks, all before any launch, in this order: negative sizes (n, max_iter, n_iters), n_components < 1, a perplexity that is not
+ * positive and finite GTE_ERR_INVALID_ARGUMENT; n > gte_tsne_max_n() or n_components > gte_tsne_max_components()
+ * GTE_ERR_UNSUPPORTED; n == 0 (or n_iters == 0) GTE_OK with nothing launched; null or misaligned pointers
+ * GTE_ERR_INVALID_ARGUMENT; a workspace below gte_tsne_workspace_bytes(n) (joint_p and iterate) GTE_ERR_WORKSPACE_TOO_SMALL.
+ * That 2 <= n and perplexity < n is the host's to check: the kernels take n = 1 (an empty sum) without a fault. */
+int gte_tsne_max_n(void);            /* 8192 */
+int gte_tsne_max_components(void);   /* 8 */
+int64_t gte_tsne_workspace_bytes(int64_t n);
+int gte_tsne_cond_p(const float* sq_dist, int64_t n, float perplexity, double* cond_p /* [n, n] */, double* beta /* [n] */, void* stream);
+int gte_tsne_joint_p(const double* cond_p, int64_t n, double* P /* [n, n] */, void* workspace, int64_t workspace_bytes, void* stream);
+int gte_tsne_iterate(const double* P, double* Y /* [2, n, n_components] */, double* update, double* gains, int64_t n, int n_components,
+                     double learning_rate, double momentum, double exaggeration, int n_iter_without_progress, double min_grad_norm,
+                     int max_iter, int n_iters, void* workspace, int64_t workspace_bytes, double* state /* [8] */, void* stream);
 /* The per-word head of label-free prediction (model_predict.predict): class, confidence and, on request, the softmax row of every
  * node in ONE pass over logits float [n_nodes, n_classes] (row i at logits + i * ld_logits, ld_logits >= n_classes,
  * 1 <= n_classes <= 16: the step engine's class limit).  Per row, with l_j its entries:
