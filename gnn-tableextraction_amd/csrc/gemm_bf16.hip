@@ -23,7 +23,8 @@ __device__ __forceinline__ u16 f2bf(float x) {
     return *reinterpret_cast<u16*>(&b);
 }
 
-// y[r, 0:cols_pad] = bf16(act(x[r, 0:cols])), zero padded to cols_pad (multiple of 8).  act: 0 none, 1 ELU(alpha = 1)
+// y[r, 0:cols_pad] = bf16(act(x[r, 0:cols])), zero padded to cols_pad (multiple of 8).  act: 0 none, 1 ELU(alpha = 1).
+// Contract (include/gte.h, pinned by tests/test_gpu_bf16_projection.py): the rounding torch.bfloat16 does, ELU(+-0) = +-0.
 __global__ void __launch_bounds__(256)
 cast_bf16_kernel(const float* __restrict__ x, int64_t ldx, u16* __restrict__ y, int64_t ldy, int64_t rows, int cols, int cols_pad,
                  int act) {
@@ -36,7 +37,7 @@ cast_bf16_kernel(const float* __restrict__ x, int64_t ldx, u16* __restrict__ y, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         float v = (c0 + j < cols) ? x[r * ldx + c0 + j] : 0.f;
-        if (act == 1) v = v > 0.f ? v : expm1f(v);
+        if (act == 1) v = v >= 0.f ? v : expm1f(v);              // >= : -0 stays -0 (expm1f(-0.f) came back as +0); NaN -> expm1f -> NaN
         o[j] = f2bf(v);
     }
     *reinterpret_cast<uint4*>(y + r * ldy + c0) = *reinterpret_cast<const uint4*>(o);

@@ -135,7 +135,22 @@ int gte_batch_csr(const int32_t* pages, int64_t n_batch, const int32_t* node_off
  *                   multiple of 8 columns; y 16-byte aligned, ldy a multiple of 8.
  * gte_gemm_bf16_nt  C[M, N] (fp32) = A[M, K] B[N, K]^T with bf16 operands on v_mfma_f32_32x32x16_bf16, fp32 accumulation
  *                   (z = X W^T of a GAT layer; W stored [heads * dim, in_feats] like nn.Linear).  Operands 16-byte aligned, K and
- *                   the leading dimensions multiples of 8 (gte_cast_bf16 produces exactly that). */
+ *                   the leading dimensions multiples of 8 (gte_cast_bf16 produces exactly that).
+ * Contract (tests/test_gpu_bf16_projection.py against tests/bf16_ref.py):
+ *   rounding   fp32 -> bf16 is round to nearest, ties to the even mantissa, as torch.bfloat16 converts: fp32 and bf16 subnormals are
+ *              kept (nothing is flushed), +-0 keeps its sign, NaN -> NaN, |x| >= 0x7F7F8000 (above the largest bf16's tie) -> +-inf.
+ *   padding    columns [cols, round_up(cols, 8)) of y are +0 whatever x holds past cols (ldx > cols); columns from there to ldy and
+ *              rows >= rows are not written.
+ *   ELU        act 1: v for v >= 0 (so ELU(-0) = -0, ELU(+inf) = +inf), expm1f(v) below (ELU(-inf) = -1, and -1 from about v <= -17),
+ *              NaN -> NaN; the fp32 value is then rounded as above.  Against expm1 in float64 the bf16 result can differ (by one bf16
+ *              neighbour) only where that value lies within a few fp32 ulps of a bf16 rounding midpoint.
+ *   product    K = 0 writes zeros.  Exactly the [M, N] window of C is written for any ldc >= N and any alignment of C: rows >= M and
+ *              columns >= N of the tiles are dropped (also where 0 * inf made them NaN), on the buffer-descriptor stores taken while
+ *              (M + 128) * ldc * 4 < 2^31 and on the plain guarded stores beyond.  Non-finite operands follow IEEE (0 * inf = NaN,
+ *              inf - inf = NaN) and reach only the outputs whose dot product holds them.
+ *   accuracy   products of bf16 values are exact in fp32 and partial sums are rounded fp32 additions (subnormals kept):
+ *              |C - A B^T| <= K * 2^-24 * sum_k |a_k b_k|, bit-exact where every partial sum is representable; measured <= 2 of
+ *              these units up to K = 1024, not above the fp32 MFMA kernel's error + 1. */
 int gte_cast_bf16(const float* x, int64_t ldx, uint16_t* y, int64_t ldy, int64_t rows, int64_t cols, int activation, void* stream);
 int gte_gemm_bf16_nt(const uint16_t* A, int64_t lda, const uint16_t* B, int64_t ldb, float* C, int64_t ldc, int64_t M, int64_t N,
                      int64_t K, void* stream);
