@@ -122,6 +122,13 @@ SIGNATURES = {
     "gte_tsne_joint_p": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_tsne_iterate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_double, c_double, c_int, c_double,
                                  c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    # EM for a one-dimensional Gaussian mixture (csrc/gmm.hip)
+    "gte_gmm_max_components": (c_int, []),
+    "gte_gmm_workgroup_samples": (c_int, []),
+    "gte_gmm_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "gte_gmm_iterate": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_double, c_double, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                c_void_p]),
+    "gte_gmm_posterior": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # class, confidence and softmax row per node (csrc/predict_head.hip)
     "gte_predict_head": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "gte_inv_degree": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

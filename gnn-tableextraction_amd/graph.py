@@ -903,6 +903,52 @@ def tsne_iterate(P: torch.Tensor, Y: torch.Tensor, update: torch.Tensor, gains: 
                                             _lib.current_stream()), "gte_tsne_iterate")
 
 
+def gmm_workspace(n: int, n_components: int, device) -> torch.Tensor:
+    """The uint8 workspace (lse, labels, per-workgroup partial sums) that ``gmm_iterate`` wants for n samples and K components.
+    ``ValueError`` for sizes outside the kernels' limits."""
+    lib = _lib.load()
+    n, K = int(n), int(n_components)
+    if not 1 <= K <= lib.gte_gmm_max_components():
+        raise ValueError(f"gmm_workspace: {K} components, the kernels take 1 .. {lib.gte_gmm_max_components()}")
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"gmm_workspace: {n} samples, the kernels take 1 .. 2^31 - 1")
+    return torch.zeros(max(int(lib.gte_gmm_workspace_bytes(n, K)), 8), dtype=torch.uint8, device=device)
+
+
+def gmm_iterate(x: torch.Tensor, P: torch.Tensor, hard: bool, tol: float, reg_covar: float, max_iter: int, n_iters: int,
+                workspace: torch.Tensor, state: torch.Tensor) -> None:
+    """Enqueues ``n_iters`` EM iterations of a one-dimensional Gaussian mixture (gte_gmm_iterate; the iteration, the addition order,
+    the stop rule and the state block are stated in include/gte.h) on the current stream and returns without synchronising.
+    ``x`` float64 [n]; ``P`` float64 [4, K] = (weights, means, covariances, precisions_cholesky), rewritten in place;
+    ``workspace`` uint8 (``gmm_workspace``); ``state`` float64 [8] = (iterations done, stopped, converged, error, lower bound,
+    previous lower bound, change, reserved), set to (0, 0, 0, 0, -inf, -inf, 0, 0) by the caller ahead of the first call: all
+    contiguous device tensors.  Iterations enqueued after the device has stopped change nothing."""
+    n, K = (x.shape[0], P.shape[1]) if x.dim() == 1 and P.dim() == 2 else (-1, -1)
+    _tsne_tensor(x, "gmm_iterate: x", torch.float64, (n,))
+    _tsne_tensor(P, "gmm_iterate: P", torch.float64, (4, K))
+    _tsne_tensor(state, "gmm_iterate: state", torch.float64, (8,))
+    _tsne_tensor(workspace, "gmm_iterate: workspace", torch.uint8, (workspace.numel(),))
+    _lib.check(_lib.load().gte_gmm_iterate(_lib.ptr(x), n, K, _lib.ptr(P), int(bool(hard)), float(tol), float(reg_covar), int(max_iter),
+                                           int(n_iters), _lib.ptr(workspace), workspace.numel(), _lib.ptr(state),
+                                           _lib.current_stream()), "gte_gmm_iterate")
+
+
+def gmm_posterior(x: torch.Tensor, P: torch.Tensor, resp: bool = True, lse: bool = False, label: bool = False):
+    """The E step alone for ``x`` float64 [m] under ``P`` float64 [4, K] in one launch (gte_gmm_posterior, the device function of
+    the fit's pass A).  Returns ``(resp float64 [m, K], lse float64 [m], label int32 [m])``, None for what was not asked for."""
+    m, K = (x.shape[0], P.shape[1]) if x.dim() == 1 and P.dim() == 2 else (-1, -1)
+    _tsne_tensor(x, "gmm_posterior: x", torch.float64, (m,))
+    _tsne_tensor(P, "gmm_posterior: P", torch.float64, (4, K))
+    if not (resp or lse or label):
+        raise ValueError("gmm_posterior: no output asked for")
+    r = torch.empty((m, K), dtype=torch.float64, device=x.device) if resp else None
+    s = torch.empty(m, dtype=torch.float64, device=x.device) if lse else None
+    lab = torch.empty(m, dtype=torch.int32, device=x.device) if label else None
+    _lib.check(_lib.load().gte_gmm_posterior(_lib.ptr(x), m, K, _lib.ptr(P), _lib.ptr(r), _lib.ptr(s), _lib.ptr(lab),
+                                             _lib.current_stream()), "gte_gmm_posterior")
+    return r, s, lab
+
+
 def token_pool(tok: torch.Tensor, table: torch.Tensor, mode: str = "mean", row_map: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Pooled table rows per word in one launch of gte_token_pool_f32 (the rule is stated in include/gte.h): the embedding lookup

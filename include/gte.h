@@ -664,6 +664,56 @@ int gte_tsne_joint_p(const double* cond_p, int64_t n, double* P /* [n, n] */, vo
 int gte_tsne_iterate(const double* P, double* Y /* [2, n, n_components] */, double* update, double* gains, int64_t n, int n_components,
                      double learning_rate, double momentum, double exaggeration, int n_iter_without_progress, double min_grad_norm,
                      int max_iter, int n_iters, void* workspace, int64_t workspace_bytes, double* state /* [8] */, void* stream);
+/* EM for a one-dimensional Gaussian mixture (csrc/gmm.hip): the loop body of scikit-learn 1.7.2's BaseMixture.fit_predict with
+ * covariance_type='full' and ONE feature (sklearn/mixture/_base.py, _gaussian_mixture.py), which Preprocessor.train_gmm of the
+ * reference runs on the host through GaussianMixture ("soft") or its HardEMGaussianMixture ("hard").  For one feature every matrix is
+ * a scalar.  Checks and the initial parameters are host work (components/tables/gmm.py: prepare).  eps = DBL_EPSILON = 2^-52.
+ * x float64 [n], the samples.  P float64 [4, K] row-major = (weights w, means mu, covariances cov, precisions_cholesky pc), read and
+ * rewritten by every iteration.  Every product, sum, difference and quotient below is one rounded float64 operation, nothing is
+ * contracted into a fused multiply-add; exp, log and sqrt are the device library's (exp and log within 1 - 2 ulp).
+ *
+ * One iteration, from the current P:
+ *   E step      y = x_i * pc_k - mu_k * pc_k;   wlp[i,k] = ((-0.5 * (log(2 pi) + y * y)) + log(pc_k)) + log(w_k)
+ *               m_i = max_k wlp[i,k], 0 if that is not finite;   lse_i = log(sum_k exp(wlp[i,k] - m_i)) + m_i, the sum in k order
+ *               (scipy's logsumexp up to that order);   log_resp[i,k] = wlp[i,k] - lse_i
+ *               soft: resp[i,k] = exp(log_resp[i,k]).   hard: resp[i,:] = the one-hot of the FIRST index of the maximum of the rounded
+ *               log_resp[i,:] -- not of wlp: the subtraction can create ties, and np.argmax takes the first.
+ *   M step      nk_k = sum_i resp[i,k] + 10 eps;   mean_k = (sum_i resp[i,k] * x_i) / nk_k
+ *               cov_k = (sum_i (resp[i,k] * (x_i - mean_k)) * (x_i - mean_k)) / nk_k + reg_covar: two passes, around the NEW mean, as
+ *               scikit-learn's _estimate_gaussian_covariances_full; never sum r x^2 - nk mean^2 (numerals reach 1e6 with tiny spreads)
+ *               pc_k = 1 / sqrt(cov_k);   soft: w_k = nk_k / (nk_0 + nk_1 + ... in k order);   hard: w_k = nk_k / n
+ *   bound, stop lb = (sum_i lse_i) / n, the E step's, for both types;   change = lb - prev, prev = the lb of the iteration before,
+ *               -inf ahead of the first.   |change| < tol: converged = 1, stopped = 1; the M step of that iteration is kept.
+ *   error       a cov_k that is not finite or not > 0: error = 1, stopped = 1 (scikit-learn raises "ill-defined empirical covariance").
+ * Sums over the samples: the order is free but fixed, a function of n alone -- never of the device -- and csrc/gmm.hip states it with
+ * its longest chain L(n) = 23 + ceil(ceil(n / gte_gmm_workgroup_samples()) / 64): a lane adds its own samples in index order, a wave
+ * butterfly and then the waves in order merge the workgroup, per-workgroup partials go to the workspace, ONE finalising workgroup adds
+ * them (lane l the workgroups l, l + 64, ... in that order, then a butterfly).  No floating-point atomics: two runs give the same bits.
+ * Two passes over x per iteration, a finalising launch behind each: pass A (E step; partials of nk, sum resp * x and sum lse; stores
+ * lse[i] and, hard, label[i] in the workspace), finalise A (nk, means), pass B (resp[i,k] recomputed as exp(wlp[i,k] - lse_i) from the
+ * stored lse and the still-old P, or read from label; partials of the covariance sums), finalise B (cov, pc, w into P; lb and the stop
+ * into the state).  No [n, K] buffer exists.
+ * state float64 [8] in device memory, integers held exactly: {iterations done, stopped, converged, error, lb, prev, change, reserved}.
+ * Before the first call the caller sets it to {0, 0, 0, 0, -inf, -inf, 0, 0}.  gte_gmm_iterate ENQUEUES n_iters iterations on `stream`
+ * and continues from `state`; it neither allocates nor synchronises.  Every kernel reads the state first and returns without a write
+ * when `stopped` is set or max_iter iterations are done, so iterations enqueued behind the stop change nothing and how the caller
+ * cuts max_iter into calls changes no bit.  The workspace (gte_gmm_workspace_bytes(n, K) bytes) needs no initialisation.
+ *
+ * gte_gmm_posterior -- the E step alone, by the same device function as pass A, for m points: resp float64 [m, K] = exp(wlp - lse)
+ * (the soft responsibilities whatever the type of the fit), lse float64 [m] (score_samples), label int32 [m] = the first-index
+ * arg-max of the rounded wlp - lse (predict).  Each output may be NULL, not all three.
+ *
+ * Limits: 1 <= K <= gte_gmm_max_components() = 64, 1 <= n < 2^31.  Checks, all before any launch: n (m) < 1, K outside 1 .. 64,
+ * max_iter < 1, n_iters < 0, tol or reg_covar negative or NaN GTE_ERR_INVALID_ARGUMENT; n >= 2^31 GTE_ERR_UNSUPPORTED; null or
+ * misaligned pointers GTE_ERR_INVALID_ARGUMENT; a workspace below the size query GTE_ERR_WORKSPACE_TOO_SMALL; n_iters == 0 GTE_OK with
+ * nothing launched.  gte_gmm_workspace_bytes returns 0 for sizes outside the limits. */
+int gte_gmm_max_components(void);      /* 64 */
+int gte_gmm_workgroup_samples(void);   /* 2048: the samples one workgroup adds; ceil(n / this) partials per sum */
+int64_t gte_gmm_workspace_bytes(int64_t n, int K);
+int gte_gmm_iterate(const double* x, int64_t n, int K, double* P /* [4, K] */, int hard, double tol, double reg_covar, int max_iter,
+                    int n_iters, void* workspace, int64_t workspace_bytes, double* state /* [8] */, void* stream);
+int gte_gmm_posterior(const double* x, int64_t m, int K, const double* P /* [4, K] */, double* resp /* [m, K] or NULL */,
+                      double* lse /* [m] or NULL */, int32_t* label /* [m] or NULL */, void* stream);
 /* The per-word head of label-free prediction (model_predict.predict): class, confidence and, on request, the softmax row of every
  * node in ONE pass over logits float [n_nodes, n_classes] (row i at logits + i * ld_logits, ld_logits >= n_classes,
  * 1 <= n_classes <= 16: the step engine's class limit).  Per row, with l_j its entries:
