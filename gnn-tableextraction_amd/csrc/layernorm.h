@@ -16,6 +16,19 @@ __device__ __forceinline__ float wave_sum(float v) { return gte_group_sum<64>(v)
 // tests/test_gpu_layernorm.py).
 __device__ __forceinline__ float ln_affine(float xhat, float g, float b) { return fmaf(xhat, g, b); }
 
+// mean = sum / n ROUNDED to float32, i.e. the value the statistics store, for a forward whose backward recomputes z and must find the
+// mask the forward took (sage_smallk_fwd_kernel / gte_smallk_bwd_step).  Written as `sum * inv_n` next to `z - mean` the product is
+// contracted into fma(-inv_n, sum, z): an unrounded mean, and on a constant row (where z - mean is nothing but that rounding) an xhat
+// the backward cannot rebuild from the stats -- tests/test_gpu_smallk_bwd.py found y > 0 on such rows at n = 100, 200, 252 where the
+// backward's mask was false.  At n = 2^k the product is exact and both forms are the same bits.  The empty asm makes the rounded
+// product opaque, so no contraction setting can fuse it: a `#pragma clang fp contract(off)` is ignored under -ffp-contract=fast, and
+// this toolchain's __fmul_rn is a plain `x * y` that is contracted like any other once inlined.
+__device__ __forceinline__ float ln_mean_rounded(float sum, float inv_n) {
+    float mean = sum * inv_n;
+    asm volatile("" : "+v"(mean));
+    return mean;
+}
+
 }  // namespace gte_ln
 
 // ---- LayerNorm(+ReLU) backward of four columns of one row (device) ------------------------------------------------------------

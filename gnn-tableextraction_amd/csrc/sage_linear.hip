@@ -909,7 +909,8 @@ int64_t gemm_workspace(int64_t M, int64_t N, int64_t K1, int64_t K2, int64_t Nse
 // ([64][Kp], Kp = K rounded up to 4, padding zero) are staged in LDS once -- every global latency of the workgroup is paid in
 // that prologue; lane l owns output columns 4 l .. 4 l + 3 of four rows at a time, a k step of four is 4 + 4 ds_read_b128
 // (the input reads are same-address broadcasts) and 32 packed FMAs; LayerNorm statistics, affine and ReLU follow in
-// registers with the arithmetic of ln_relu_fwd_vec_kernel (layernorm.hip).  HBM-bound in principle (N (K + 2 n_out) 4 bytes = 50 MB at 24.5 k x
+// registers with the arithmetic of ln_relu_fwd_vec_kernel (layernorm.hip), except that z - mean takes the ROUNDED mean the statistics
+// store (ln_mean_rounded: the one-pass backward rebuilds xhat from them).  HBM-bound in principle (N (K + 2 n_out) 4 bytes = 50 MB at 24.5 k x
 // 256); measured 24 us (GEMM + LayerNorm launches: 32 us) -- the per-workgroup transposing fill of W^T (each of 383
 // workgroups walks all 256 rows of W) and the short dependent phases of a 16-rows-per-wave workgroup are what is left.
 constexpr int SMALLK_MAX = 64;
@@ -1021,7 +1022,7 @@ sage_smallk_fwd_kernel(const float* __restrict__ a1, int64_t lda1, int k1, const
             float sm_ = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) sm_ += ok ? acc[u][e] : 0.f;
-            const float mean = wave_sum(sm_) * inv_n;
+            const float mean = ln_mean_rounded(wave_sum(sm_), inv_n);  // the stored value: the backward recomputes xhat from it
             float q = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float d = ok ? acc[u][e] - mean : 0.f; q = fmaf(d, d, q); }

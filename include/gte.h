@@ -1291,7 +1291,10 @@ int gte_ln_relu_fwd_p3(const float* z, int64_t ldz, const float* gamma, const fl
  * The ReLU mask is DEFINED on the stored stats: xhat = (z - stats.mean) * stats.rstd, pre = fma(xhat, gamma, beta), gradient where
  * pre > 0 and 0 at pre == 0 (torch.relu).  A forward form that subtracts the mean as fma(-1 / n, sum, z) (gte_ln_relu_fwd_p3,
  * gte_gemm_p3_nt_ln_fwd) can round an element whose |pre| is within about |mean| / std * 2^-24 * |gamma| of zero to the other side;
- * tests/test_gpu_layernorm.py counts those elements and holds every other one to the float64 reference.
+ * tests/test_gpu_layernorm.py counts those elements and holds every other one to the float64 reference.  The one-pass short-input
+ * forward (gte_sage_linear_fwd / _p3 where gte_sage_linear_fwd_fuses_ln) subtracts the ROUNDED mean it stores, so its y > 0 IS this
+ * mask at every element and every n_out: gte_sage_smallk_bwd and gte_gemm_p3_nt_smallk_bwd, which rebuild xhat from the stats, rest
+ * on that (tests/test_gpu_smallk_bwd.py asserts it with nothing exempted).
  * workspace: gte_ln_relu_bwd_workspace_bytes(M, n_out). */
 int64_t gte_ln_relu_bwd_workspace_bytes(int64_t M, int64_t n_out);
 int gte_ln_relu_bwd(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* stats,
